@@ -2,7 +2,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]
                     [--model hifigan|fargan] [--dtype f16|bf16|fp32]
-                    [--batch B] [--seconds S]
+                    [--batch B] [--seconds S] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of `Generator.forward` (feature preparation + vocoder,
 the scope of the reference's 'generate' timer,
@@ -12,19 +12,32 @@ each), inputs resident in HBM, plus - for N > 1 - the all-gather of the
 generated audio over xGMI (RCCL). Weights are random-init (no checkpoint is
 reachable offline), broadcast from rank 0. Prints ONE JSON line on rank 0.
 
+A plain run sets up, runs W warm-up and K timed steps and prints the line:
+`value` (samples/s over the K steps) and `ms_per_step`. `--dump-outputs DIR`
+then also writes the audio of the last timed step (rank 0's) as
+DIR/audio.npy, float32; inputs and weights are seeded, so two runs with the
+same arguments are comparable output for output.
+
+`--full` adds everything else the line can carry: the per-kernel table (a
+pass of its own) and the dominant kernel's roofline (HIP events around its
+launches inside the timed region, the sustained MFMA rate, the rocprofv3 PMC
+traffic passes), the `--sustain` steady-state loop, the N > 1 compute-only /
+gather-only diagnosis, the `secondary` block and the CPU baseline.
+
 `--gpus N` with N > 1 and no torchrun environment re-launches this script as
 N ranks (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1 ...`); under torchrun it uses the environment it is
 given. Other BASELINE.json configs: `--dtype fp32 --batch 8 --seconds 5`
 (config 2), `--model fargan` (config 5).
 
-At N = 1 the line also carries a `secondary` block, measured in the same run
-after the headline region (about 20 s of GPU time; `--no-secondary` skips it):
-the library-default 'checkpoint' operand mode on the headline workload, config
-2 (fp32, 8 x 5 s), config 5 (FARGAN, 'mixed' and 'fp32' weight storage), the
-three preprocess transforms through the C ABI, and the latency of the
-graph-replayed `packed_inference` at nn~ chunk sizes - each with its time, its
-throughput and (where one kernel dominates) that kernel's roofline fraction.
+With `--full` at N = 1 the line also carries a `secondary` block, measured in
+the same run after the headline region (about 20 s of GPU time;
+`--no-secondary` skips it): the library-default 'checkpoint' operand mode on
+the headline workload, config 2 (fp32, 8 x 5 s), config 5 (FARGAN, 'mixed' and
+'fp32' weight storage), the three preprocess transforms through the C ABI,
+and the latency of the graph-replayed `packed_inference` at nn~ chunk sizes -
+each with its time, its throughput and (where one kernel dominates) that
+kernel's roofline fraction.
 
 `--stand-in` (tests/test_cpu_bench_multi_rank.py) replaces the HIP engine by a
 trivial torch function so that the N > 1 harness itself - self-launch,
@@ -90,8 +103,17 @@ def parse_args():
                         help='utterances per GPU')
     parser.add_argument('--seconds', type=float, default=10.)
     parser.add_argument('--sustain', type=float, default=5.,
-                        help='seconds of back-to-back steps timed after the '
-                             'K official ones (steady-state clocks); 0 = off')
+                        help='--full: seconds of back-to-back steps timed '
+                             'after the K official ones (steady-state '
+                             'clocks); 0 = off')
+    parser.add_argument('--full', action='store_true',
+                        help='also measure what the headline figure does not '
+                             'need: per-kernel table and roofline, sustained '
+                             'loop, N > 1 diagnosis, secondary block, CPU '
+                             'baseline (the --no-* options below trim it)')
+    parser.add_argument('--dump-outputs', metavar='DIR', default=None,
+                        help='write the audio of the last timed step (rank '
+                             '0) to DIR/audio.npy, float32')
     parser.add_argument('--no-cpu-baseline', action='store_true')
     parser.add_argument('--no-traffic', action='store_true',
                         help='skip the two rocprofv3 PMC passes that measure '
@@ -105,7 +127,10 @@ def parse_args():
                         help='plumbing test of the N > 1 harness: a trivial '
                              'torch function instead of the HIP engine (runs '
                              'without a GPU, over gloo); not a measurement')
-    return parser.parse_args()
+    args = parser.parse_args()
+    if args.steps < 1:
+        parser.error('--steps must be at least 1')
+    return args
 
 
 def self_launch(args):
@@ -736,6 +761,32 @@ def secondary_block(device, budget=45.):
     return out
 
 
+def dump_outputs(directory, arrays, budget=64 << 20):
+    """`--dump-outputs`: every array as DIR/<name>.npy (float32 / float64).
+    Past `budget` bytes in all, an array is replaced by a fixed sample of its
+    flattened elements (DIR/<name>_sample.npy, seed 0) and the indices it took
+    (DIR/<name>_sample_index.npy, float64)."""
+    import numpy as np
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, array in arrays.items():
+        if array.dtype not in (np.float32, np.float64):
+            array = array.astype(np.float32)
+        if total <= budget:
+            np.save(directory / f'{name}.npy', array)
+            continue
+        flat = array.reshape(-1)
+        # (this array's share of the budget, values and indices together)
+        keep = max(1, int(budget * array.nbytes / total) //
+                   (array.itemsize + 8))
+        index = np.sort(np.random.default_rng(0).choice(
+            flat.size, size=min(keep, flat.size), replace=False))
+        np.save(directory / f'{name}_sample.npy', flat[index])
+        np.save(directory / f'{name}_sample_index.npy',
+                index.astype(np.float64))
+
+
 def main():
     args = parse_args()
     if args.dtype is None:
@@ -833,7 +884,7 @@ def main():
         for _ in range(args.warmup):
             step()
         kernel_table = None
-        if hifigan:
+        if hifigan and args.full:
             # Per-kernel table: a separate pass of K steps with HIP events
             # around EVERY launch (not part of `value`: 34 event pairs per step
             # cost 0.7 % of it). The timed region then brackets only the
@@ -859,20 +910,24 @@ def main():
         guarded('timed region')
         start = time.perf_counter()
         for _ in range(args.steps):
-            if fargan:
+            if fargan and args.full:
                 # HIP events on the launch stream (torch's current stream is
                 # the one the C ABI is handed) around the forward's launches
                 e0 = torch.cuda.Event(enable_timing=True)
                 e1 = torch.cuda.Event(enable_timing=True)
                 e0.record()
-                step()
+                audio = step()
                 e1.record()
                 forward_events.append((e0, e1))
             else:
-                step()
+                audio = step()
         fence()
         elapsed = time.perf_counter() - start
-        if hifigan:
+        # (what the last timed step returned, copied out before any later
+        # step can reuse its buffers)
+        outputs = {'audio': audio.float().cpu().numpy()} \
+            if args.dump_outputs and rank == 0 else None
+        if hifigan and args.full:
             library.pm_hifigan_profile_enable(engine, 0)
             library.pm_hifigan_profile_collect(engine)
             timed_profile = parse_profile(
@@ -882,7 +937,7 @@ def main():
         # power-cap settling time, so also time >= `sustain` seconds of
         # back-to-back steps (reported beside, never instead of, `value`)
         sustained = None
-        if args.sustain > 0:
+        if args.full and args.sustain > 0:
             per_step = max(elapsed / args.steps, 1e-4)
             count = max(args.steps, int(math.ceil(args.sustain / per_step)))
             count = min(count, int(60. / per_step) + 1)
@@ -904,7 +959,7 @@ def main():
         # K steps WITHOUT the collective (compute alone, per rank) and the
         # collective alone (submitted and drained, nothing to hide under)
         diagnosis = None
-        if world > 1:
+        if world > 1 and args.full:
             guarded('compute-only steps')
             fence()
             begin = time.perf_counter()
@@ -928,18 +983,20 @@ def main():
         watchdog.arm('timing reduction')
         # (host doubles over the gloo control group)
         own = torch.tensor(
-            [elapsed, sustained[0] if sustained else 0., diagnosis[0],
-             diagnosis[1]], dtype=torch.float64)
+            [elapsed, sustained[0] if sustained else 0.] +
+            list(diagnosis or (0., 0.)), dtype=torch.float64)
         every = [torch.empty_like(own) for _ in range(world)]
         dist.all_gather(every, own)
         every = torch.stack(every)                            # (world, 4)
         rank_step_ms = (every[:, 0] / args.steps * 1e3).tolist()
-        rank_compute_ms = (every[:, 2] / args.steps * 1e3).tolist()
         elapsed = every[:, 0].max().item()
         if sustained:
             sustained = (every[:, 1].max().item(), sustained[1])
-        compute_ms = every[:, 2].max().item() / args.steps * 1e3
-        gather_ms = every[:, 3].max().item() / args.steps * 1e3
+        rank_compute_ms, compute_ms, gather_ms = None, None, None
+        if diagnosis:
+            rank_compute_ms = (every[:, 2] / args.steps * 1e3).tolist()
+            compute_ms = every[:, 2].max().item() / args.steps * 1e3
+            gather_ms = every[:, 3].max().item() / args.steps * 1e3
 
     if rank == 0:
         total_samples = world * samples_per_step * args.steps
@@ -1036,7 +1093,8 @@ def main():
                 'rccl_version': rccl,
                 'compute_ms_per_step': compute_ms,
                 'gather_alone_ms_per_step': gather_ms,
-                'exposed_gather_ms': elapsed / args.steps * 1e3 - compute_ms,
+                'exposed_gather_ms': elapsed / args.steps * 1e3 - compute_ms
+                                     if diagnosis else None,
                 'rank_ms_per_step': rank_step_ms,
                 'rank_ms_per_step_min': min(rank_step_ms),
                 'rank_ms_per_step_max': max(rank_step_ms),
@@ -1050,7 +1108,7 @@ def main():
             result['sustained_steps'] = count
             result['sustained_value'] = \
                 world * samples_per_step * count / seconds
-        if fargan:
+        if fargan and args.full:
             times = [a.elapsed_time(b) for a, b in forward_events]
             result['roofline'] = fargan_roofline(
                 promonet_amd.FARGAN_WEIGHT_DTYPE, args.batch, frames,
@@ -1078,7 +1136,7 @@ def main():
         elif stand_in:
             result['stand_in'] = True
             result['roofline'] = None
-        else:
+        elif hifigan and args.full:
             # dominant kernel family: HIP events around its launches, on the
             # launch stream, inside the timed region; every other kernel's row
             # comes from the separate per-kernel pass (`profile`, per
@@ -1198,13 +1256,16 @@ def main():
                 for k, v in sorted(profile.items())}
         # (the secondary block rides on the HiFi-GAN headline line only: it
         # builds its own models under the default configuration)
-        if world == 1 and hifigan and not args.no_secondary:
+        if world == 1 and hifigan and args.full and not args.no_secondary:
             # (the headline model's workspace goes back to the allocator first)
             del model, inputs
             torch.cuda.empty_cache()
             result['secondary'] = secondary_block(device)
-        if world == 1 and not stand_in and not args.no_cpu_baseline:
+        if world == 1 and not stand_in and args.full and \
+                not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline(args.model)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(result))
 
     if world > 1:

@@ -39,10 +39,63 @@ def variant_config_file(which):
     return file
 
 
+def layout():
+    """What `promonet_amd.patch(promonet)` reads and replaces in the reference
+    package, as data: its upper-case constants (names only for the
+    filesystem-valued ones), the kind of every attribute the patch swaps, and
+    the size of `Generator().state_dict()`. tests/test_cpu_host.py rebuilds a
+    stand-in package of this shape."""
+    import json
+    import reference_import
+
+    promonet = reference_import.load()
+    constants, opaque = {}, []
+    for name in sorted(dir(promonet)):
+        if not name.isupper():
+            continue
+        value = getattr(promonet, name)
+        try:
+            text = json.dumps(value)
+        except TypeError:
+            opaque.append(name)
+            continue
+        if '/' in text:
+            opaque.append(name)
+        else:
+            constants[name] = value
+    attributes = {}
+    for path in (
+            'model.Generator', 'model.HiFiGAN', 'model.FARGAN',
+            'synthesize.core', 'preprocess.spectrogram.from_audio',
+            'preprocess.spectrogram.linear_to_mel',
+            'preprocess.loudness.from_audio') + tuple(
+                f'synthesize{core}.{name}' for core in ('', '.core')
+                for name in ('from_features', 'from_file', 'from_file_to_file',
+                             'from_files_to_files', 'generate')):
+        target = promonet
+        for part in path.split('.'):
+            target = getattr(target, part)
+        attributes[path] = ('module' if isinstance(target, type(promonet))
+                            else 'class' if isinstance(target, type)
+                            else 'function')
+    GOLDEN.mkdir(parents=True, exist_ok=True)
+    (GOLDEN / 'reference_layout.json').write_text(json.dumps({
+        'constants': constants,
+        'opaque_constants': opaque,
+        'attributes': attributes,
+        'generator_state_dict_entries':
+            len(promonet.model.Generator().state_dict())},
+        indent=1, sort_keys=True) + '\n')
+
+
 def run(which):
     import torch
     import reference_import
     import restatement as oracle
+
+    if which == 'layout':
+        layout()
+        return
 
     configs = {
         'small': [small_config_file()],
@@ -329,7 +382,7 @@ if __name__ == '__main__':
         run(sys.argv[1])
     else:
         for which in ('small', 'default', 'fargan', 'zero_shot',
-                      'sparse_none', 'edit_voiced'):
+                      'sparse_none', 'edit_voiced', 'layout'):
             subprocess.run(
                 [sys.executable, __file__, which], check=True)
         for file in sorted(GOLDEN.iterdir()):

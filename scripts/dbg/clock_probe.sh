@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 V=$1; PAT=$2
 OUT=$ROOT/gpurun_out/clock$V
 mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-BENCH="python $ROOT/bench.py --no-cpu-baseline --no-traffic --no-secondary --sustain 0 --steps 4 --warmup 1"
+BENCH="python $ROOT/bench.py --full --no-cpu-baseline --no-traffic --no-secondary --sustain 0 --steps 4 --warmup 1"
 PROMONET_HIP_LIB=$ROOT/promonet_amd/lib/libpromonet_hip$V.so timeout 300 rocprofv3 --output-format csv --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU \
    --kernel-trace -d $OUT -o p -- $BENCH > $OUT/log 2>&1
 python - <<PY

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/fargan
 mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 for storage in fp32 mixed; do
-  timeout 600 python $ROOT/bench.py --model fargan --dtype $storage --steps 5 --warmup 2 --sustain 0 --no-cpu-baseline --no-secondary > $OUT/bench_$storage.json 2> $OUT/bench_$storage.err
+  timeout 600 python $ROOT/bench.py --full --model fargan --dtype $storage --steps 5 --warmup 2 --sustain 0 --no-cpu-baseline --no-secondary > $OUT/bench_$storage.json 2> $OUT/bench_$storage.err
   timeout 300 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_$storage -o stats -- python $ROOT/bench.py --model fargan --dtype $storage --steps 5 --warmup 2 --sustain 0 --no-cpu-baseline --no-secondary --no-traffic > $OUT/stats_$storage.log 2>&1
   f=$(find $OUT/stats_$storage -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/kernel_stats_$storage.csv
   rm -rf $OUT/stats_$storage

@@ -5,9 +5,9 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=${1:-r05}; OUT=$ROOT/gpurun_out/$TAG; mkdir
 PM_RECORD_ERRORS=1 timeout 2400 python -m pytest tests -m gpu -q --durations=15 > $OUT/pytest_gpu.log 2>&1; echo "pytest rc $?" | tee -a $OUT/pytest_gpu.log
 tail -3 $OUT/pytest_gpu.log
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc $?" | tee -a $OUT/smoke.log
-timeout 900 python bench.py > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "bench default rc $?"
-timeout 600 python bench.py --gpus 2 --no-cpu-baseline --no-traffic --no-secondary > $OUT/bench_bf16_2ranks.json 2> $OUT/bench_bf16_2ranks.err; echo "bench 2 ranks rc $?"; grep -h WARNING $OUT/bench_bf16_2ranks.err | head -2
-timeout 600 python bench.py --model fargan --steps 3 --warmup 1 > $OUT/bench_fargan.json 2> $OUT/bench_fargan.err; echo "bench fargan rc $?"
+timeout 900 python bench.py --full > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "bench default rc $?"
+timeout 600 python bench.py --full --gpus 2 --no-cpu-baseline --no-traffic --no-secondary > $OUT/bench_bf16_2ranks.json 2> $OUT/bench_bf16_2ranks.err; echo "bench 2 ranks rc $?"; grep -h WARNING $OUT/bench_bf16_2ranks.err | head -2
+timeout 600 python bench.py --full --model fargan --steps 3 --warmup 1 > $OUT/bench_fargan.json 2> $OUT/bench_fargan.err; echo "bench fargan rc $?"
 python - $OUT <<'PY'
 import json, sys
 out = sys.argv[1]

@@ -5,12 +5,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=${1:-r06}; OUT=$ROOT/gpurun_out/$TAG; mkdir
 PM_RECORD_ERRORS=1 timeout 2400 python -m pytest tests -m gpu -q --durations=15 > $OUT/pytest_gpu.log 2>&1; echo "pytest rc $?" | tee -a $OUT/pytest_gpu.log
 tail -3 $OUT/pytest_gpu.log; cp gpurun_out/measured_errors.json $OUT/ 2>/dev/null
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc $?" | tee -a $OUT/smoke.log
-timeout 900 python bench.py > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "bench default rc $?"
-timeout 600 python bench.py --dtype checkpoint --no-cpu-baseline --no-secondary > $OUT/bench_checkpoint.json 2> $OUT/bench_checkpoint.err; echo "bench checkpoint rc $?"
-timeout 600 python bench.py --dtype f16 --no-cpu-baseline --no-secondary --no-traffic > $OUT/bench_f16.json 2> $OUT/bench_f16.err
-timeout 600 python bench.py --dtype fp32 --batch 8 --seconds 5 --no-cpu-baseline --no-secondary --no-traffic > $OUT/bench_fp32_config2.json 2> $OUT/bench_fp32_config2.err
-timeout 600 python bench.py --gpus 2 --no-cpu-baseline --no-traffic --no-secondary > $OUT/bench_bf16_2ranks.json 2> $OUT/bench_bf16_2ranks.err; echo "bench 2 ranks rc $?"
-timeout 600 python bench.py --model fargan --steps 3 --warmup 1 --no-secondary > $OUT/bench_fargan.json 2> $OUT/bench_fargan.err; echo "bench fargan rc $?"
+timeout 900 python bench.py --full > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "bench default rc $?"
+timeout 600 python bench.py --full --dtype checkpoint --no-cpu-baseline --no-secondary > $OUT/bench_checkpoint.json 2> $OUT/bench_checkpoint.err; echo "bench checkpoint rc $?"
+timeout 600 python bench.py --full --dtype f16 --no-cpu-baseline --no-secondary --no-traffic > $OUT/bench_f16.json 2> $OUT/bench_f16.err
+timeout 600 python bench.py --full --dtype fp32 --batch 8 --seconds 5 --no-cpu-baseline --no-secondary --no-traffic > $OUT/bench_fp32_config2.json 2> $OUT/bench_fp32_config2.err
+timeout 600 python bench.py --full --gpus 2 --no-cpu-baseline --no-traffic --no-secondary > $OUT/bench_bf16_2ranks.json 2> $OUT/bench_bf16_2ranks.err; echo "bench 2 ranks rc $?"
+timeout 600 python bench.py --full --model fargan --steps 3 --warmup 1 --no-secondary > $OUT/bench_fargan.json 2> $OUT/bench_fargan.err; echo "bench fargan rc $?"
 timeout 900 python scripts/checkpoint_schedule.py > $OUT/checkpoint_schedule.txt 2>&1
 timeout 900 python scripts/precision_seeds.py 5 > $OUT/precision_seeds.txt 2>&1
 python - $OUT <<'PY'

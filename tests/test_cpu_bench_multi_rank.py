@@ -10,6 +10,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -33,7 +34,7 @@ def run_bench(world, extra=(), env=None, timeout=600):
 
 
 def test_eight_ranks_self_launched():
-    done = run_bench(8)
+    done = run_bench(8, ['--full'])
     assert done.returncode == 0, done.stderr[-3000:]
     lines = [l for l in done.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1                       # rank 0 alone prints
@@ -115,3 +116,45 @@ def test_a_stalled_rank_fails_the_job_fast():
     assert time.perf_counter() - begin < 200
     assert 'collective hang' in done.stderr
     assert not [l for l in done.stdout.splitlines() if l.startswith('{')]
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline figure alone (no
+    sustained loop, no N > 1 diagnosis); --dump-outputs writes the last timed
+    step's audio, the same in two runs with the same arguments."""
+    dumps = []
+    for run in range(2):
+        directory = tmp_path / f'run{run}'
+        done = run_bench(2, ['--dump-outputs', str(directory)])
+        assert done.returncode == 0, done.stderr[-3000:]
+        lines = [l for l in done.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        result = json.loads(lines[0])
+        assert result['steps'] == 3 and result['ms_per_step'] > 0
+        assert 'sustained_steps' not in result
+        assert result['multi_gpu']['compute_ms_per_step'] is None
+        assert sorted(p.name for p in directory.iterdir()) == ['audio.npy']
+        dumps.append(np.load(directory / 'audio.npy'))
+    assert dumps[0].dtype == np.float32
+    assert dumps[0].shape == (4, 1, 86 * 256)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_dump_outputs_samples_past_its_budget(tmp_path):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench', ROOT / 'bench.py')
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    audio = np.random.default_rng(1).standard_normal(
+        (8, 1, 4096)).astype(np.float32)
+    bench.dump_outputs(tmp_path / 'all', {'audio': audio})
+    assert np.array_equal(np.load(tmp_path / 'all' / 'audio.npy'), audio)
+    bench.dump_outputs(tmp_path / 'cut', {'audio': audio}, budget=12_000)
+    values = np.load(tmp_path / 'cut' / 'audio_sample.npy')
+    index = np.load(tmp_path / 'cut' / 'audio_sample_index.npy')
+    assert values.dtype == np.float32 and index.dtype == np.float64
+    assert values.nbytes + index.nbytes <= 12_000 and len(values) == 1000
+    assert np.array_equal(values, audio.reshape(-1)[index.astype(np.int64)])
+    again = tmp_path / 'again'
+    bench.dump_outputs(again, {'audio': audio}, budget=12_000)
+    assert np.array_equal(np.load(again / 'audio_sample_index.npy'), index)

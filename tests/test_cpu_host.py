@@ -245,16 +245,57 @@ def test_fargan_engine_validation():
     assert mixed not in (_lib.PM_F32, _lib.PM_F16, _lib.PM_BF16, _lib.PM_F16X3)
 
 
+def reference_stand_in():
+    """A package object of the reference's shape, rebuilt from the layout
+    oracle/make_golden.py recorded from the real one
+    (tests/golden/reference_layout.json): its constants, and a placeholder
+    for every module, class and function the patch replaces."""
+    import json
+    import types
+    layout = json.loads(
+        (ROOT / 'tests' / 'golden' / 'reference_layout.json').read_text())
+    promonet = types.ModuleType('promonet')
+    promonet.__dict__.update(layout['constants'])
+    for name in layout['opaque_constants']:
+        setattr(promonet, name, object())
+    for path, kind in sorted(layout['attributes'].items()):
+        *parents, leaf = path.split('.')
+        owner = promonet
+        for part in parents:
+            if not hasattr(owner, part):
+                setattr(owner, part, types.ModuleType(part))
+            owner = getattr(owner, part)
+        if not hasattr(owner, leaf):
+            setattr(owner, leaf, types.ModuleType(leaf) if kind == 'module'
+                    else type(leaf, (), {}) if kind == 'class'
+                    else lambda *args, **kwargs: None)
+    return promonet, layout
+
+
 def test_patch_swaps_into_the_real_reference():
-    """Only where /root/reference exists (the build container): the literal
-    drop-in of INTEGRATION.md section 1."""
-    import reference_import
-    if not reference_import.available():
-        pytest.skip('reference not present on this machine')
-    promonet = reference_import.load()
+    """The literal drop-in of INTEGRATION.md section 1, on a stand-in of the
+    reference package recorded from the real one: every constant agrees (the
+    patch reconfigures nothing), and everything it swaps in is an attribute
+    the reference has."""
+    promonet, layout = reference_stand_in()
+    before = {n: getattr(promonet_amd, n) for n in dir(promonet_amd.config)
+              if n.isupper()}
+    modules = {
+        path: set(vars(module)) for path, module in (
+            ('', promonet), ('model', promonet.model),
+            ('synthesize', promonet.synthesize),
+            ('synthesize.core', promonet.synthesize.core),
+            ('preprocess.spectrogram', promonet.preprocess.spectrogram),
+            ('preprocess.loudness', promonet.preprocess.loudness))}
     original = promonet.synthesize.from_features
     promonet_amd.patch(promonet)
     try:
+        assert before == {n: getattr(promonet_amd, n) for n in before}
+        for path, names in modules.items():
+            module = promonet
+            for part in filter(None, path.split('.')):
+                module = getattr(module, part)
+            assert set(vars(module)) == names, path
         assert promonet.model.Generator is promonet_amd.model.Generator
         assert promonet.model.HiFiGAN is promonet_amd.model.HiFiGAN
         assert promonet.synthesize.from_features is \
@@ -265,7 +306,8 @@ def test_patch_swaps_into_the_real_reference():
             promonet_amd.preprocess.spectrogram.from_audio
         # same constructor contract: no arguments, reference state-dict keys
         model = promonet.model.Generator()
-        assert len(model.state_dict()) == 238
+        assert len(model.state_dict()) == 238 == \
+            layout['generator_state_dict_entries']
         assert promonet_amd.NUM_FEATURES == promonet.NUM_FEATURES
     finally:
         promonet.synthesize.from_features = original

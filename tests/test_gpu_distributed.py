@@ -104,7 +104,7 @@ def test_bench_self_launches_two_ranks(device):
     done = subprocess.run(
         [sys.executable, str(root / 'bench.py'), '--gpus', '2', '--steps', '2',
          '--warmup', '1', '--batch', '4', '--seconds', '2', '--sustain', '0',
-         '--no-cpu-baseline'],
+         '--no-cpu-baseline', '--full'],
         capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert done.returncode == 0, done.stderr[-2000:]
     lines = [l for l in done.stdout.splitlines() if l.startswith('{')]
@@ -148,7 +148,7 @@ def test_bench_eight_folded_ranks_real_engine(device):
     done = subprocess.run(
         [sys.executable, str(root / 'bench.py'), '--gpus', '8', '--steps', '2',
          '--warmup', '1', '--batch', '4', '--seconds', '2', '--sustain', '0.2',
-         '--no-cpu-baseline'],
+         '--no-cpu-baseline', '--full'],
         capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert done.returncode == 0, done.stderr[-3000:]
     lines = [l for l in done.stdout.splitlines() if l.startswith('{')]
