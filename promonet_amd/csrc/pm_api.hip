@@ -66,138 +66,78 @@ static inline int up_dtype(int code) {
 }
 
 // ---------------------------------------------------------------------------
-// dtype dispatch
+// dtype dispatch: f(ET()) with ET the Elem* type of the operand code `dtype`
 // ---------------------------------------------------------------------------
+template <class F> static hipError_t with_elem(int dtype, F&& f) {
+    switch (dtype) {
+        case PM_F32: return f(ElemF32());
+        case PM_F16: return f(ElemF16());
+        case PM_BF16: return f(ElemBF16());
+        case PM_F16X3: return f(ElemF16X3());
+        case PM_F16A2: return f(ElemF16A2());
+    }
+    return hipErrorInvalidValue;
+}
+
 static hipError_t launch_pair(
     int dtype, int C, int K, const PairArgs& a0, hipStream_t s) {
     PairArgs a = a0;
 #ifdef PM_TUNING
     a.timeline = g_timeline;
 #endif
-    switch (dtype) {
-        case PM_F32: return pm_launch_pair<ElemF32>(C, K, a, s);
-        case PM_F16: return pm_launch_pair<ElemF16>(C, K, a, s);
-        case PM_BF16: return pm_launch_pair<ElemBF16>(C, K, a, s);
-        case PM_F16X3: return pm_launch_pair<ElemF16X3>(C, K, a, s);
-        case PM_F16A2: return pm_launch_pair<ElemF16A2>(C, K, a, s);
-    }
-    return hipErrorInvalidValue;
+    return with_elem(dtype, [&](auto et) {
+        typedef decltype(et) ET;
+        return pm_launch_pair<ET>(C, K, pm_plan_pair<ET>(C, K, a.B, a.L), a, s);
+    });
+}
+
+static hipError_t plan_stage(int dtype, const PmStage& st, int fusion, PmPlan* p) {
+    return with_elem(dtype, [&](auto et) {
+        *p = pm_plan_stage<decltype(et)>(st, fusion);
+        return hipSuccess;
+    });
 }
 
 static hipError_t launch_block3(
-    int dtype, int C, int K, const Block3Args& a0, hipStream_t s) {
-    Block3Args a = a0;
-#ifdef PM_TUNING
-    a.timeline = g_timeline;
-#endif
-    switch (dtype) {
-        case PM_F32: return pm_launch_block3<ElemF32>(C, K, a, s);
-        case PM_F16: return pm_launch_block3<ElemF16>(C, K, a, s);
-        case PM_BF16: return pm_launch_block3<ElemBF16>(C, K, a, s);
-        case PM_F16X3: return pm_launch_block3<ElemF16X3>(C, K, a, s);
-        case PM_F16A2: return pm_launch_block3<ElemF16A2>(C, K, a, s);
-    }
-    return hipErrorInvalidValue;
+    int dtype, const PmLaunch& l, const PmStage& st, int j, hipStream_t s) {
+    return with_elem(dtype, [&](auto et) {
+        return pm_launch_block3<decltype(et)>(l, st, j, s);
+    });
 }
 
 static hipError_t launch_mrf(
-    int dtype, int C, const Block3Args (&a0)[3], hipStream_t s) {
-    Block3Args a[3] = {a0[0], a0[1], a0[2]};
+    int dtype, const PmLaunch& l, const PmStage& st, hipStream_t s) {
+    return with_elem(dtype, [&](auto et) {
+        return pm_launch_mrf<decltype(et)>(l, st, s);
+    });
+}
+
+// An MRF stage description (pm_launch.h) with what its Blocks share
+static PmStage stage_desc(int C, const float* x, float* out, int B, int L,
+                          int mode, float scale, int nblocks, int niter) {
+    PmStage d = {};
+    d.C = C; d.x = x; d.out = out; d.B = B; d.L = L; d.mode = mode;
+    d.scale = scale; d.nblocks = nblocks; d.niter = niter;
 #ifdef PM_TUNING
-    a[0].timeline = g_timeline;      // (the skewed whole-MRF walk's phase totals)
+    d.timeline = g_timeline;
 #endif
-    switch (dtype) {
-        case PM_F32: return pm_launch_mrf<ElemF32>(C, a, s);
-        case PM_F16: return pm_launch_mrf<ElemF16>(C, a, s);
-        case PM_BF16: return pm_launch_mrf<ElemBF16>(C, a, s);
-        case PM_F16X3: return pm_launch_mrf<ElemF16X3>(C, a, s);
-        case PM_F16A2: return pm_launch_mrf<ElemF16A2>(C, a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-// Fusion level: 2 = whole-MRF launches where they exist, 1 = one kernel per
-// Block, 0 = one kernel per Block iteration. The shipped library always runs
-// level 2; a -DPM_TUNING build reads PM_FUSION=pair|block for A/B runs.
-static int fusion_level() {
-#ifdef PM_TUNING
-    static const int level = [] {
-        const char* e = getenv("PM_FUSION");
-        return (e && !strcmp(e, "pair")) ? 0 : (e && !strcmp(e, "block")) ? 1 : 2;
-    }();
-    return level;
-#else
-    return 2;
-#endif
-}
-static bool block3_enabled() {
-    return fusion_level() >= 1;
-}
-
-static int pair_chunk(int dtype, int C) {
-    switch (dtype) {
-        case PM_F32: return pm_pair_chunk<ElemF32>(C);
-        case PM_F16: return pm_pair_chunk<ElemF16>(C);
-        case PM_BF16: return pm_pair_chunk<ElemBF16>(C);
-        case PM_F16X3: return pm_pair_chunk<ElemF16X3>(C);
-        case PM_F16A2: return pm_pair_chunk<ElemF16A2>(C);
-    }
-    return 0;
-}
-
-static bool block3_supported(int dtype, int C, int K) {
-    if (!block3_enabled()) return false;
-    switch (dtype) {
-        case PM_F32: return pm_block3_supported<ElemF32>(C, K);
-        case PM_F16: return pm_block3_supported<ElemF16>(C, K);
-        case PM_BF16: return pm_block3_supported<ElemBF16>(C, K);
-        case PM_F16X3: return pm_block3_supported<ElemF16X3>(C, K);
-        case PM_F16A2: return pm_block3_supported<ElemF16A2>(C, K);
-    }
-    return false;
-}
-
-// Chunk size the MRF conv weights of a (C, K) layer are packed with: the
-// whole-Block kernel streams 64-channel chunks, the pair kernel its own CH.
-static int mrf_chunk(int dtype, int C, int K, int ndil) {
-    if (ndil <= 3 && block3_supported(dtype, C, K)) return C < 64 ? C : 64;
-    return pair_chunk(dtype, C);
+    return d;
 }
 
 static hipError_t launch_single(
     int dtype, int kind, int ch, int cfg, const SingleArgs& a, hipStream_t s) {
-    switch (dtype) {
-        case PM_F32: return pm_launch_single<ElemF32>(kind, ch, cfg, a, s);
-        case PM_F16: return pm_launch_single<ElemF16>(kind, ch, cfg, a, s);
-        case PM_BF16: return pm_launch_single<ElemBF16>(kind, ch, cfg, a, s);
-        case PM_F16X3: return pm_launch_single<ElemF16X3>(kind, ch, cfg, a, s);
-        case PM_F16A2: return pm_launch_single<ElemF16A2>(kind, ch, cfg, a, s);
-    }
-    return hipErrorInvalidValue;
+    return with_elem(dtype, [&](auto et) {
+        return pm_launch_single<decltype(et)>(kind, ch, cfg, a, s);
+    });
 }
 
 static hipError_t launch_pack(int dtype, const PackArgs& a, hipStream_t s) {
     const unsigned grid = (unsigned)((a.total + 255) / 256);
-    switch (dtype) {
-        case PM_F32:
-            hipLaunchKernelGGL(pm_pack_kernel<ElemF32>, dim3(grid), dim3(256), 0, s, a);
-            break;
-        case PM_F16:
-            hipLaunchKernelGGL(pm_pack_kernel<ElemF16>, dim3(grid), dim3(256), 0, s, a);
-            break;
-        case PM_BF16:
-            hipLaunchKernelGGL(pm_pack_kernel<ElemBF16>, dim3(grid), dim3(256), 0, s, a);
-            break;
-        case PM_F16X3:
-            hipLaunchKernelGGL(pm_pack_kernel<ElemF16X3>, dim3(grid), dim3(256), 0, s, a);
-            break;
-        case PM_F16A2:
-            hipLaunchKernelGGL(pm_pack_kernel<ElemF16A2>, dim3(grid), dim3(256), 0, s, a);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_elem(dtype, [&](auto et) {
+        hipLaunchKernelGGL(pm_pack_kernel<decltype(et)>, dim3(grid), dim3(256),
+                           0, s, a);
+        return hipGetLastError();
+    });
 }
 
 // Geometry of one packed convolution
@@ -235,31 +175,11 @@ static hipError_t pack_bias_step(
     const int mtiles = g.M / 32;
     const long long per_mt = (long long)g.weight_elems() / mtiles;
     const dim3 grid((mtiles * 512 + 255) / 256), block(256);
-    switch (dtype) {
-        case PM_F32:
-            hipLaunchKernelGGL(pm_pack_bias_step_kernel<ElemF32>, grid, block,
-                               0, s, bias, out, g.cout, mtiles, per_mt);
-            break;
-        case PM_F16:
-            hipLaunchKernelGGL(pm_pack_bias_step_kernel<ElemF16>, grid, block,
-                               0, s, bias, out, g.cout, mtiles, per_mt);
-            break;
-        case PM_BF16:
-            hipLaunchKernelGGL(pm_pack_bias_step_kernel<ElemBF16>, grid, block,
-                               0, s, bias, out, g.cout, mtiles, per_mt);
-            break;
-        case PM_F16X3:
-            hipLaunchKernelGGL(pm_pack_bias_step_kernel<ElemF16X3>, grid, block,
-                               0, s, bias, out, g.cout, mtiles, per_mt);
-            break;
-        case PM_F16A2:
-            hipLaunchKernelGGL(pm_pack_bias_step_kernel<ElemF16A2>, grid, block,
-                               0, s, bias, out, g.cout, mtiles, per_mt);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_elem(dtype, [&](auto et) {
+        hipLaunchKernelGGL(pm_pack_bias_step_kernel<decltype(et)>, grid, block,
+                           0, s, bias, out, g.cout, mtiles, per_mt);
+        return hipGetLastError();
+    });
 }
 
 static hipError_t pad_bias(
@@ -450,7 +370,7 @@ extern "C" int pm_hifigan_create(
                     q.k = c->resblock_kernel_sizes[j];
                     q.cout_pad = q.cin_pad = q.M = s.cout_pad;
                     q.kt = q.k;
-                    q.ch = mrf_chunk(s.dtype, s.cout_pad, q.k, c->num_dilations);
+                    q.ch = std::min(s.cout_pad, 64);   // (pm_launch.h: one packing)
                     q.bias_step = true;
                 }
     }
@@ -698,9 +618,13 @@ static Plan make_plan(pm_hifigan_t h, int B, int T) {
     p.off_gbias = align256((size_t)B * T * h->cfp * sizeof(float));
     p.off_buf = p.off_gbias + align256((size_t)B * h->c0p * sizeof(float));
     p.off_scratch = p.off_buf + 4 * p.buf_elems * sizeof(float);
-    // (the skewed walk is only taken with >= 4 steps of >= 256 columns per
-    // segment, max(1, CUs / B) segments per utterance: short calls - a
-    // streaming frame, a single 2 s utterance - carry no scratch)
+    // (the skewed walks are only planned with >= 4 steps per segment,
+    // max(1, CUs / B) segments per utterance: short calls - a streaming
+    // frame, a single 2 s utterance - carry no scratch. The planner tests
+    // each stage against its own geometry's step; the workspace, sized once
+    // for all stages, takes the longest stage and the narrowest step the
+    // production heuristics skew, 256 columns - C = 128, and the 4-byte
+    // layouts at C = 64 -, so that no stage the planner would skew lacks it)
     {
         const int cus = pm_device_cus();
         const size_t nseg = std::max(1, (cus > 0 ? cus : 256) / B);
@@ -803,118 +727,70 @@ static int forward_impl(
         L *= st.r;
         rate *= st.r;
         const int si = xi;   // stage input is dead after the upsampler
-        // whole MRF (Blocks k = 3, 7, 11) in one launch: U -> S
-        bool mrf_done = false;
-        // (split-f16 operands on a batch long enough for the skewed walk: Block
-        // by Block - three launches that recompute nothing beat the fused
-        // whole-MRF launch and its 23 % halo there, pm_launch.h)
-        const bool x3_skew = pm_x3skew_id(st.dtype) && st.cout_pad == 32 &&
-            p.scratch && pm_device_cus() > 0 &&
-            (L / 512) / std::max(1, pm_device_cus() / B) >= 4;
-        if (fusion_level() >= 2 && h->cfg.num_resblocks == 3 &&
-            h->cfg.num_dilations <= 3 && st.cout_pad <= 64 &&
-            h->cfg.resblock_kernel_sizes[0] == 3 &&
-            h->cfg.resblock_kernel_sizes[1] == 7 &&
-            h->cfg.resblock_kernel_sizes[2] == 11) {
-            Block3Args blocks[3] = {};
-            double flops = 0;
-            for (int j = 0; j < 3; ++j) {
-                Block3Args& a = blocks[j];
-                a.x = buf[ui]; a.out = buf[si];
-                a.niter = h->cfg.num_dilations;
-                for (int n = 0; n < a.niter; ++n) {
-                    a.w1[n] = st.c1[j][n].w;
-                    a.w2[n] = st.c2[j][n].w;
-                    a.dil[n] = h->cfg.resblock_dilations[j][n];
-                    flops += 4.0 * st.cout * st.cout *
-                             h->cfg.resblock_kernel_sizes[j] * B * L;
-                }
-                a.B = B; a.L = L; a.mode = j == 0 ? 1 : 2; a.scale = scale;
-                a.lengths = lengths; a.len_scale = rate;
-                // (4-byte operand layouts on a long batch: the skewed
-                // whole-MRF walk, or Block by Block on the skewed walk - never
-                // the two-sided tiling of the fused launch, pm_launch.h)
-                a.scratch = p.scratch ? base + p.off_scratch : nullptr;
-                a.scratch_bytes = p.scratch;
-                a.skew_only = x3_skew ? 1 : 0;
+        // the MRF: U -> S, planned once (pm_launch.h)
+        const int nb = h->cfg.num_resblocks, ni = h->cfg.num_dilations;
+        PmStage d = stage_desc(st.cout_pad, buf[ui], buf[si], B, L, 1, scale,
+                               nb, ni);
+        d.lengths = lengths; d.len_scale = rate;
+        d.scratch = p.scratch ? base + p.off_scratch : nullptr;
+        d.scratch_bytes = p.scratch;
+        for (int j = 0; j < nb; ++j) {
+            d.blk[j].K = h->cfg.resblock_kernel_sizes[j];
+            for (int n = 0; n < ni; ++n) {
+                d.blk[j].w1[n] = st.c1[j][n].w;
+                d.blk[j].w2[n] = st.c2[j][n].w;
+                d.blk[j].dil[n] = h->cfg.resblock_dilations[j][n];
             }
+        }
+        // The stage's last Block completes `out`, whose only reader is the
+        // next stage's upsampler - which stages cvt(lrelu(out)): let the
+        // kernel write exactly that (half the bytes out, half the bytes in,
+        // no staging VALU) when the upsampler is the conv_single_kernel of a
+        // 16-bit stage.
+        const size_t next = &st - &h->stages[0] + 1;
+        if (nb > 1 && next < h->stages.size() &&
+            esz(h->stages[next].up.dtype) == 2 && h->stages[next].up.cfg != 4) {
+            d.act16 = buf[ai];      // (free: no pair iterations)
+            d.act16_type = h->stages[next].up.dtype;
+        }
+        PmPlan plan;
+        HIP_TRY(plan_stage(st.dtype, d, pm_fusion_level(), &plan));
+        if (plan.mrf) {
+            double flops = 0;
+            for (int j = 0; j < nb; ++j)
+                flops += ni * 4.0 * st.cout * st.cout * d.blk[j].K * B * L;
             char label[64];
             snprintf(label, sizeof(label), "mrf_c%d", st.cout);
-            hipError_t e = hipSuccess;
-            const size_t marks_before = h->marks.size();
             PROF(h, s, label, flops, (double)B * L * st.cout * 4 * 2, {
-                e = launch_mrf(st.dtype, st.cout_pad, blocks, s);
-                if (e != hipSuccess && e != hipErrorNotSupported) HIP_TRY(e);
+                HIP_TRY(launch_mrf(st.dtype, plan.block[0], d, s));
             });
-            mrf_done = e == hipSuccess;
-            if (!mrf_done && h->marks.size() > marks_before)
-                h->marks.pop_back();
         }
-        for (int j = 0; !mrf_done && j < h->cfg.num_resblocks; ++j) {
-            const int K = h->cfg.resblock_kernel_sizes[j];
-            bool fused = false;
-            if (h->cfg.num_dilations <= 3 &&
-                block3_supported(st.dtype, st.cout_pad, K)) {
+        for (int j = 0; !plan.mrf && j < nb; ++j) {
+            const int K = d.blk[j].K;
+            const double bytes = (double)B * L * st.cout * 4 * (j ? 3 : 2);
+            char label[64];
+            if (plan.block[j].kernel != PM_PAIRS) {
                 // whole Block (all dilations) in one kernel: U -> S
-                Block3Args a = {};
-                a.x = buf[ui]; a.out = buf[si];
-                a.niter = h->cfg.num_dilations;
-                double flops = 0;
-                for (int n = 0; n < a.niter; ++n) {
-                    a.w1[n] = st.c1[j][n].w;
-                    a.w2[n] = st.c2[j][n].w;
-                    a.dil[n] = h->cfg.resblock_dilations[j][n];
-                    flops += 4.0 * st.cout * st.cout * K * B * L;
-                }
-                a.B = B; a.L = L; a.mode = j == 0 ? 1 : 2; a.scale = scale;
-                a.lengths = lengths; a.len_scale = rate;
-                a.scratch = p.scratch ? base + p.off_scratch : nullptr;
-                a.scratch_bytes = p.scratch;
-                // The stage's last Block launch completes `out`, whose only
-                // reader is the next stage's upsampler - which stages
-                // cvt(lrelu(out)): let the kernel write exactly that (half the
-                // bytes out, half the bytes in, no staging VALU) when the
-                // upsampler is the conv_single_kernel of a 16-bit stage.
-                int act16_done = 0;
-                const size_t si_index = &st - &h->stages[0];
-                if (j == h->cfg.num_resblocks - 1 && a.mode == 2 &&
-                    si_index + 1 < h->stages.size()) {
-                    const Stage& next = h->stages[si_index + 1];
-                    if (esz(next.up.dtype) == 2 && next.up.cfg != 4) {
-                        a.act16 = buf[ai];      // (free: no pair iterations)
-                        a.act16_type = next.up.dtype;
-                        a.act16_done = &act16_done;
-                    }
-                }
-                char label[64];
                 snprintf(label, sizeof(label), "block_c%d_k%d", st.cout, K);
-                hipError_t e = hipSuccess;
-                const size_t marks_before = h->marks.size();
-                PROF(h, s, label, flops,
-                     (double)B * L * st.cout * 4 * (a.mode == 2 ? 3 : 2), {
-                    e = launch_block3(st.dtype, st.cout_pad, K, a, s);
-                    if (e != hipSuccess && e != hipErrorNotSupported) HIP_TRY(e);
+                PROF(h, s, label, ni * 4.0 * st.cout * st.cout * K * B * L, bytes, {
+                    HIP_TRY(launch_block3(st.dtype, plan.block[j], d, j, s));
                 });
-                fused = e == hipSuccess;
-                if (!fused && h->marks.size() > marks_before)
-                    h->marks.pop_back();
-                if (fused && act16_done) x16 = buf[ai];
+                if (plan.block[j].act16) x16 = buf[ai];
+                continue;
             }
-            if (fused) continue;
             const float* src = buf[ui];
-            for (int n = 0; n < h->cfg.num_dilations; ++n) {
-                const bool last = n == h->cfg.num_dilations - 1;
+            for (int n = 0; n < ni; ++n) {
+                const bool last = n == ni - 1;
                 float* dst = last ? buf[si] : ((n & 1) ? buf[bi] : buf[ai]);
                 PairArgs a = {};
                 a.x = src; a.out = dst;
-                a.w1 = st.c1[j][n].w;
-                a.w2 = st.c2[j][n].w;
+                a.w1 = d.blk[j].w1[n];
+                a.w2 = d.blk[j].w2[n];
                 a.B = B; a.L = L;
-                a.dilation = h->cfg.resblock_dilations[j][n];
+                a.dilation = d.blk[j].dil[n];
                 a.mode = last ? (j == 0 ? 1 : 2) : 0;
                 a.scale = scale;
                 a.lengths = lengths; a.len_scale = rate;
-                char label[64];
                 snprintf(label, sizeof(label), "pair_c%d_k%d", st.cout, K);
                 PROF(h, s, label, 4.0 * st.cout * st.cout * K * B * L,
                      (double)B * L * st.cout * 4 * (a.mode == 2 ? 3 : 2), {
@@ -1128,6 +1004,31 @@ extern "C" size_t pm_op_workspace_bytes(int c_in, int c_out, int k) {
            2 * align256(co * 64 * 4);
 }
 
+// Pack one Block iteration - conv1 and conv2 weights (C, C, K) and biases (C)
+// - into the pm_op_workspace_bytes(C, C, K) at `base`; *p1 / *p2: the two
+// packed streams, their bias steps included
+static int pack_iteration(
+    int dtype, int C, int K, const float* w1, const float* b1, const float* w2,
+    const float* b2, char* base, hipStream_t s, const void** p1,
+    const void** p2) {
+    const int Cp = pad32(C);
+    ConvGeom g;
+    g.mode = 0; g.cout = g.cin = C; g.k = K; g.cout_pad = g.cin_pad = g.M = Cp;
+    g.kt = K; g.ch = std::min(Cp, 64); g.bias_step = true;
+    const size_t stream_bytes = align256(((size_t)Cp * Cp * K + Cp * 16) * 4);
+    void* q1 = base; void* q2 = base + stream_bytes;
+    float* pb1 = (float*)(base + 2 * stream_bytes);
+    float* pb2 = pb1 + align256(Cp * 64 * 4) / 4;
+    HIP_TRY(pack_weights(dtype, g, w1, q1, s));
+    HIP_TRY(pack_weights(dtype, g, w2, q2, s));
+    HIP_TRY(pad_bias(b1, pb1, C, Cp, 1, s));
+    HIP_TRY(pad_bias(b2, pb2, C, Cp, 1, s));
+    HIP_TRY(pack_bias_step(dtype, g, pb1, q1, s));
+    HIP_TRY(pack_bias_step(dtype, g, pb2, q2, s));
+    *p1 = q1; *p2 = q2;
+    return PM_OK;
+}
+
 extern "C" int pm_block_iteration_cl(
     int dtype, const float* x, float* out, const float* w1, const float* b1,
     const float* w2, const float* b2, int B, int L, int C, int K, int d,
@@ -1142,20 +1043,10 @@ extern "C" int pm_block_iteration_cl(
     if (ws_bytes < pm_op_workspace_bytes(C, C, K))
         return fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    ConvGeom g;
-    g.mode = 0; g.cout = g.cin = C; g.k = K; g.cout_pad = g.cin_pad = g.M = Cp;
-    g.kt = K; g.ch = pair_chunk(dtype, Cp); g.bias_step = true;
-    char* base = (char*)ws;
-    const size_t wsz = align256(((size_t)Cp * Cp * K + Cp * 16) * 4);
-    void* p1 = base; void* p2 = base + wsz;
-    float* pb1 = (float*)(base + 2 * wsz);
-    float* pb2 = pb1 + align256(Cp * 64 * 4) / 4;
-    HIP_TRY(pack_weights(dtype, g, w1, p1, s));
-    HIP_TRY(pack_weights(dtype, g, w2, p2, s));
-    HIP_TRY(pad_bias(b1, pb1, C, Cp, 1, s));
-    HIP_TRY(pad_bias(b2, pb2, C, Cp, 1, s));
-    HIP_TRY(pack_bias_step(dtype, g, pb1, p1, s));
-    HIP_TRY(pack_bias_step(dtype, g, pb2, p2, s));
+    const void *p1, *p2;
+    const int rc = pack_iteration(dtype, C, K, w1, b1, w2, b2, (char*)ws, s,
+                                  &p1, &p2);
+    if (rc) return rc;
     PairArgs a = {};
     a.x = x; a.out = out; a.w1 = p1; a.w2 = p2;
     a.B = B; a.L = L; a.dilation = d; a.mode = mode; a.scale = scale;
@@ -1193,43 +1084,29 @@ static int block_cl_impl(
     if (ws_bytes < 3 * pm_op_workspace_bytes(C, C, K))
         return fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    ConvGeom g;
-    g.mode = 0; g.cout = g.cin = C; g.k = K; g.cout_pad = g.cin_pad = g.M = Cp;
-    g.kt = K; g.ch = Cp < 64 ? Cp : 64; g.bias_step = true;
-    Block3Args a = {};
-    a.x = x; a.out = out; a.niter = niter; a.B = B; a.L = L; a.mode = mode;
-    a.scale = scale;
     const size_t per = pm_op_workspace_bytes(C, C, K);
-    const size_t wsz = align256(((size_t)Cp * Cp * K + Cp * 16) * 4);
+    PmStage d = stage_desc(Cp, x, out, B, L, mode, scale, 1, niter);
+    d.blk[0].K = K;
     for (int n = 0; n < niter; ++n) {
-        char* base = (char*)ws + n * per;
-        void* p1 = base; void* p2 = base + wsz;
-        float* pb1 = (float*)(base + 2 * wsz);
-        float* pb2 = pb1 + align256(Cp * 64 * 4) / 4;
-        HIP_TRY(pack_weights(dtype, g, w1[n], p1, s));
-        HIP_TRY(pack_weights(dtype, g, w2[n], p2, s));
-        HIP_TRY(pad_bias(b1[n], pb1, C, Cp, 1, s));
-        HIP_TRY(pad_bias(b2[n], pb2, C, Cp, 1, s));
-        HIP_TRY(pack_bias_step(dtype, g, pb1, p1, s));
-        HIP_TRY(pack_bias_step(dtype, g, pb2, p2, s));
-        a.w1[n] = p1; a.w2[n] = p2;
-        a.dil[n] = dilations[n];
+        const int rc = pack_iteration(dtype, C, K, w1[n], b1[n], w2[n], b2[n],
+                                      (char*)ws + n * per, s, &d.blk[0].w1[n],
+                                      &d.blk[0].w2[n]);
+        if (rc) return rc;
+        d.blk[0].dil[n] = dilations[n];
     }
     // (what the caller hands over beyond the packed weights serves the skewed
     // walk: pm_walk_scratch_bytes)
     if (ws_bytes > 3 * per) {
-        a.scratch = (char*)ws + 3 * per;
-        a.scratch_bytes = ws_bytes - 3 * per;
+        d.scratch = (char*)ws + 3 * per;
+        d.scratch_bytes = ws_bytes - 3 * per;
     }
-    int act16_done = 0;
-    if (act16) {
-        a.act16 = act16; a.act16_type = act_dtype; a.act16_done = &act16_done;
-    }
-    hipError_t e = launch_block3(dtype, Cp, K, a, s);
-    if (e == hipErrorNotSupported)
+    if (act16) { d.act16 = act16; d.act16_type = act_dtype; }
+    PmPlan plan;
+    HIP_TRY(plan_stage(dtype, d, 1, &plan));
+    if (plan.block[0].kernel == PM_PAIRS)
         return fail(PM_EINVAL, "no whole-Block kernel for this shape");
-    HIP_TRY(e);
-    if (act16 && !act16_done)
+    HIP_TRY(launch_block3(dtype, plan.block[0], d, 0, s));
+    if (act16 && !plan.block[0].act16)
         return fail(PM_ESTATE, "the launch did not take the skewed walk: `out` "
                     "holds the fp32 result, the 16-bit operand copy was not "
                     "written");
@@ -1284,43 +1161,32 @@ extern "C" int pm_mrf_cl(
     if (ws_bytes < 3 * (size_t)niter * per)
         return fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    static const int KS[3] = {3, 7, 11};
-    Block3Args blocks[3] = {};
+    PmStage d = stage_desc(Cp, x, out, B, L, 1, 1.f / 3.f, 3, niter);
     for (int j = 0; j < 3; ++j) {
-        ConvGeom g;
-        g.mode = 0; g.cout = g.cin = C; g.k = KS[j];
-        g.cout_pad = g.cin_pad = g.M = Cp; g.kt = KS[j]; g.ch = Cp;
-        g.bias_step = true;
-        Block3Args& a = blocks[j];
-        a.x = x; a.out = out; a.niter = niter; a.B = B; a.L = L;
-        a.mode = j == 0 ? 1 : 2; a.scale = 1.f / 3.f;
-        const size_t wsz = align256(((size_t)Cp * Cp * KS[j] + Cp * 16) * 4);
+        d.blk[j].K = 4 * j + 3;         // 3, 7, 11
         for (int n = 0; n < niter; ++n) {
-            char* base = (char*)ws + (size_t)(j * niter + n) * per;
-            void* p1 = base; void* p2 = base + wsz;
-            float* pb1 = (float*)(base + 2 * wsz);
-            float* pb2 = pb1 + align256(Cp * 64 * 4) / 4;
             const int i = j * niter + n;
-            HIP_TRY(pack_weights(dtype, g, w1[i], p1, s));
-            HIP_TRY(pack_weights(dtype, g, w2[i], p2, s));
-            HIP_TRY(pad_bias(b1[i], pb1, C, Cp, 1, s));
-            HIP_TRY(pad_bias(b2[i], pb2, C, Cp, 1, s));
-            HIP_TRY(pack_bias_step(dtype, g, pb1, p1, s));
-            HIP_TRY(pack_bias_step(dtype, g, pb2, p2, s));
-            a.w1[n] = p1; a.w2[n] = p2; a.dil[n] = dilations[n];
+            const int rc = pack_iteration(
+                dtype, C, d.blk[j].K, w1[i], b1[i], w2[i], b2[i],
+                (char*)ws + (size_t)i * per, s, &d.blk[j].w1[n], &d.blk[j].w2[n]);
+            if (rc) return rc;
+            d.blk[j].dil[n] = dilations[n];
         }
     }
     // (what the caller hands over beyond the packed weights serves the skewed
     // whole-MRF walk of the 4-byte operand layouts: pm_walk_scratch_bytes)
-    if (ws_bytes > 3 * (size_t)niter * per)
-        for (int j = 0; j < 3; ++j) {
-            blocks[j].scratch = (char*)ws + 3 * (size_t)niter * per;
-            blocks[j].scratch_bytes = ws_bytes - 3 * (size_t)niter * per;
-        }
-    hipError_t e = launch_mrf(dtype, Cp, blocks, s);
-    if (e == hipErrorNotSupported)
-        return fail(PM_EINVAL, "no whole-MRF kernel for this shape");
-    HIP_TRY(e);
+    if (ws_bytes > 3 * (size_t)niter * per) {
+        d.scratch = (char*)ws + 3 * (size_t)niter * per;
+        d.scratch_bytes = ws_bytes - 3 * (size_t)niter * per;
+    }
+    PmLaunch l;
+    bool planned = false;
+    HIP_TRY(with_elem(dtype, [&](auto et) {
+        planned = pm_plan_mrf<decltype(et)>(d, false, &l);
+        return hipSuccess;
+    }));
+    if (!planned) return fail(PM_EINVAL, "no whole-MRF kernel for this shape");
+    HIP_TRY(launch_mrf(dtype, l, d, s));
     return PM_OK;
 }
 

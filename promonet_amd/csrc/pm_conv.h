@@ -1085,19 +1085,13 @@ struct Block3Args {
     int ntiles, halo, TL;
     const int* lengths;  // (B) valid frames per utterance or null
     int len_scale;
-    char* scratch;       // device scratch for the skewed walk, or null
-    size_t scratch_bytes;
     // Optional (skewed walk only): instead of the fp32 tensor `out`, store
     // cvt(lrelu(result)) as the 16-bit MFMA operand type `act16_type` (PM_F16 /
     // PM_BF16 numbering) - what the next stage's upsampler, the only reader
-    // of a stage's output, stages anyway. *act16_done (host) is set to 1 by
-    // the launcher when the kernel it took honours the request.
+    // of a stage's output, stages anyway (PmLaunch::act16: whether the
+    // planned launch does).
     void* act16;
     int act16_type;
-    int* act16_done;
-    // pm_launch_mrf: take the skewed whole-MRF walk or nothing
-    // (hipErrorNotSupported) - the caller's fallback is Block by Block
-    int skew_only;
     PM_TIMELINE_FIELD    // debug stamps (tuning builds)
 };
 

@@ -4,4 +4,4 @@
 // (profiles/r03/ab_skew.txt) while it costs the other conv kernels up to 1 %.
 #define PM_INSTANTIATE
 #include "pm_launch.h"
-template hipError_t pm_launch_mrf<ElemF16>(int, const Block3Args (&)[3], hipStream_t);
+template hipError_t pm_launch_mrf<ElemF16>(const PmLaunch&, const PmStage&, hipStream_t);

@@ -1,38 +1,18 @@
-// Host-side launchers: pick the template instantiation (tile geometry) for a
-// layer shape. Explicitly instantiated once per operand type in
-// pm_conv_{f16,bf16,f32}.hip so the three compile in parallel.
+// Host side of the MFMA convolutions: the tile geometry per layer shape, the
+// planner that chooses which kernel runs each MRF stage (pm_plan_*), and the
+// launchers that launch what it chose (pm_launch_*). The launchers are
+// explicitly instantiated once per operand type in pm_conv_*.hip so that the
+// types compile in parallel.
 #pragma once
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <utility>
 
 #include "pm_conv.h"
-
-// Operand types (ElemXX::ID = the PM_* dtype code) whose C = 32 / 64 stages
-// run Block by Block on the skewed walk instead of the fused whole-MRF launch:
-// split f16 (ID 3; three MFMAs per step, so the whole-MRF tiling's 23 % halo
-// recompute shows: profiles/r04/ab_x3_skew.txt) and - measured separately,
-// profiles/r05/ab_x3skew_f32.txt - exact fp32 (ID 0; 16 times the MFMA time per
-// step, the same argument). ONE predicate for the launcher's template choice
-// (pm_launch_block3) and the engine's fusion decision (forward_impl).
-#ifndef PM_X3SKEW_F32
-#define PM_X3SKEW_F32 1
-#endif
-// (A/B builds: -DPM_SKEW16_C32=1 sends the 16-bit C = 32 stage the same way)
-#ifndef PM_SKEW16_C32
-#define PM_SKEW16_C32 0
-#endif
-#ifndef PM_A2_SKEW
-#define PM_A2_SKEW 1
-#endif
-// the skewed whole-MRF walk for those types (-DPM_MRF_SKEW=0: A/B builds)
-#ifndef PM_MRF_SKEW
-#define PM_MRF_SKEW 1
-#endif
-constexpr bool pm_x3skew_id(int id) {
-    return id == 3 || (PM_A2_SKEW && id == 4) || (PM_X3SKEW_F32 && id == 0) ||
-           (PM_SKEW16_C32 && (id == 1 || id == 2));
-}
+#include "promonet_hip.h"
 
 // Opt a kernel into `bytes` of dynamic LDS (> 48 KB needs the attribute).
 // The grant is a property of (kernel, DEVICE): cached per pair, so one process
@@ -56,7 +36,7 @@ inline hipError_t pm_ensure_dynamic_lds(const void* kern, int bytes) {
 }
 
 // Compute units of the current device, queried once per device (the walked
-// launchers size their grids from it on every forward).
+// launches size their grids from it on every forward).
 inline int pm_device_cus() {
     static std::mutex guard;
     static std::map<int, int> cus_of;
@@ -80,10 +60,7 @@ inline int pm_device_cus() {
 // per column tile. 0 = the production heuristics.
 // skew: -1 = never the skewed walk, 0 = where it measured faster, 1 = wherever
 // it fits.
-#ifndef PM_SKEW_DEFAULT
-#define PM_SKEW_DEFAULT 0    // (A/B builds: -DPM_SKEW_DEFAULT=-1)
-#endif
-struct PmForce { int walk_nseg = 0; int upsample_groups = 0; int skew = PM_SKEW_DEFAULT; };
+struct PmForce { int walk_nseg = 0; int upsample_groups = 0; int skew = 0; };
 // scratch the skewed walk takes per workgroup, at most
 #define PM_SKEW_WG_SCRATCH (256 << 10)
 // (per host thread: see pm_debug_force in pm_api.hip)
@@ -100,33 +77,23 @@ inline bool pm_narrow_allowed() {
 #endif
 }
 
-template <class ET> hipError_t pm_launch_pair(
-    int C, int K, const PairArgs& args, hipStream_t stream);
-template <class ET> int pm_pair_tile_len(int C, int K);
-// input-channel chunk size the pair kernel's weight stream is packed with
-template <class ET> int pm_pair_chunk(int C);
-// whether pm_launch_block3 has an instantiation for (C, K)
-template <class ET> bool pm_block3_supported(int C, int K);
+// Fusion level: 2 = whole-MRF launches where they exist, 1 = one kernel per
+// Block, 0 = one kernel per Block iteration. The shipped library always runs
+// level 2; a -DPM_TUNING build reads PM_FUSION=pair|block for A/B runs.
+inline int pm_fusion_level() {
+#ifdef PM_TUNING
+    static const int level = [] {
+        const char* e = getenv("PM_FUSION");
+        return (e && !strcmp(e, "pair")) ? 0 : (e && !strcmp(e, "block")) ? 1 : 2;
+    }();
+    return level;
+#else
+    return 2;
+#endif
+}
 
-// Whole-Block fusion for C <= 64; returns hipErrorNotSupported when the shape
-// has no instantiation (caller falls back to the pair kernel).
-template <class ET> hipError_t pm_launch_block3(
-    int C, int K, const Block3Args& args, hipStream_t stream);
-
-// Whole MRF stage (Blocks k = 3, 7, 11 in that order) in one launch for
-// C <= 64; hipErrorNotSupported otherwise (caller launches Block by Block).
-template <class ET> hipError_t pm_launch_mrf(
-    int C, const Block3Args (&blocks)[3], hipStream_t stream);
-
-// kind 0: plain conv with KT = KSPAN = 7 (input conv); kind 1: polyphase
-// ConvTranspose (KT = 2, KSPAN = 3). cfg: 0 = 256 x 128 tile, 1 = 64 x 128,
-// 3 = 128 x 128 (measured: a 512 x 128 tile is 20 % slower than cfg 0),
-// 2 = 32 x 128.
-template <class ET> hipError_t pm_launch_single(
-    int kind, int ch, int cfg, const SingleArgs& args, hipStream_t stream);
-hipError_t pm_launch_stft(int epi, const SingleArgs& args, hipStream_t stream);
-
-#ifdef PM_INSTANTIATE
+// LDS a walked or skewed workgroup may take
+#define PM_LDS_BYTES (160 * 1024)
 
 // ---- fused pair geometry per (operand type, C) ---------------------------
 template <class ET, int C> struct PairCfg;
@@ -190,80 +157,25 @@ template <> struct PairCfgNarrow<ElemBF16, 256> : PairCfgNarrow<ElemF16, 256> {}
 template <> struct PairCfgNarrow<ElemBF16, 128> : PairCfgNarrow<ElemF16, 128> {};
 #define PM_NARROW_BELOW 150   // 3x the tiles must still fit ~2 rounds of 256 CUs
 
-template <class ET, int C, int K, class G>
-static hipError_t launch_pair_cfg(const PairArgs& a0, hipStream_t stream) {
-    constexpr int WM = G::WM, WN = G::WN, NTW = G::NTW, CH = G::CH;
-    constexpr int ALIAS = G::ALIAS;
-    constexpr int TL = WN * NTW * 32 - (K - 1);
-    PairArgs a = a0;
-    a.ntiles = (a.L + TL - 1) / TL;
-    auto kern = conv_pair_kernel<ET, C, K, WM, WN, NTW, CH, ALIAS>;
-    const int smem =
-        pair_smem_bytes<ET, C, K, WM, WN, NTW, CH, ALIAS>(a.dilation);
-    hipError_t e = pm_ensure_dynamic_lds(
-        reinterpret_cast<const void*>(kern), smem);
-    if (e != hipSuccess) return e;
-    const int grid = a.ntiles * a.B;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem,
-                       stream, a);
-    return hipGetLastError();
+// The MRF conv weights are packed once, in chunks of min(C, 64) input channels
+// (the whole-Block kernels' chunk, block3_body): every pair geometry streams
+// the same packing, so the fusion level never changes it.
+template <class ET, int C> constexpr bool pm_one_packing_c() {
+    return PairCfg<ET, C>::CH == (C < 64 ? C : 64) &&
+           PairCfgNarrow<ET, C>::CH == PairCfg<ET, C>::CH;
 }
-
-template <class ET, int C, int K>
-static hipError_t launch_pair_ck(const PairArgs& a, hipStream_t stream) {
-    typedef PairCfg<ET, C> W;
-    typedef PairCfgNarrow<ET, C> N;
-    if constexpr ((int)N::NTW != (int)W::NTW || (int)N::WN != (int)W::WN) {
-        constexpr int TL = W::WN * W::NTW * 32 - (K - 1);
-        const bool allowed = pm_narrow_allowed();
-        if (allowed && (long long)((a.L + TL - 1) / TL) * a.B < PM_NARROW_BELOW)
-            return launch_pair_cfg<ET, C, K, N>(a, stream);
-    }
-    return launch_pair_cfg<ET, C, K, W>(a, stream);
+template <class ET> constexpr bool pm_one_packing() {
+    return pm_one_packing_c<ET, 32>() &&
+           pm_one_packing_c<ET, 64>() &&
+           pm_one_packing_c<ET, 128>() &&
+           pm_one_packing_c<ET, 256>();
 }
-
-template <class ET, int C>
-static hipError_t launch_pair_c(int K, const PairArgs& a, hipStream_t s) {
-    switch (K) {
-        case 3: return launch_pair_ck<ET, C, 3>(a, s);
-        case 7: return launch_pair_ck<ET, C, 7>(a, s);
-        case 11: return launch_pair_ck<ET, C, 11>(a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <class ET>
-hipError_t pm_launch_pair(int C, int K, const PairArgs& a, hipStream_t s) {
-    switch (C) {
-        case 256: return launch_pair_c<ET, 256>(K, a, s);
-        case 128: return launch_pair_c<ET, 128>(K, a, s);
-        case 64: return launch_pair_c<ET, 64>(K, a, s);
-        case 32: return launch_pair_c<ET, 32>(K, a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <class ET>
-int pm_pair_tile_len(int C, int K) {
-    switch (C) {
-        case 256: return PairCfg<ET, 256>::WN * PairCfg<ET, 256>::NTW * 32 - (K - 1);
-        case 128: return PairCfg<ET, 128>::WN * PairCfg<ET, 128>::NTW * 32 - (K - 1);
-        case 64: return PairCfg<ET, 64>::WN * PairCfg<ET, 64>::NTW * 32 - (K - 1);
-        case 32: return PairCfg<ET, 32>::WN * PairCfg<ET, 32>::NTW * 32 - (K - 1);
-    }
-    return 0;
-}
-
-template <class ET>
-int pm_pair_chunk(int C) {
-    switch (C) {
-        case 256: return PairCfg<ET, 256>::CH;
-        case 128: return PairCfg<ET, 128>::CH;
-        case 64: return PairCfg<ET, 64>::CH;
-        case 32: return PairCfg<ET, 32>::CH;
-    }
-    return 0;
-}
+static_assert(pm_one_packing<ElemF32>() &&
+              pm_one_packing<ElemF16>() &&
+              pm_one_packing<ElemBF16>() &&
+              pm_one_packing<ElemF16X3>() &&
+              pm_one_packing<ElemF16A2>(),
+              "pair and whole-Block kernels read one weight packing");
 
 // ---- whole-Block fusion ---------------------------------------------------
 // Geometry per (operand type, C, K). WM == 0: no whole-Block instantiation
@@ -277,16 +189,15 @@ template <class ET, int C, int K> struct Block3Cfg { enum { WM = 0, WN = 1, NTW 
 // at C = 32 k 3, -5 % at C = 32 k 7, -13 % at C = 64 k 3. With a larger halo
 // (k 11, or k 7 at C = 64) the extra recompute eats the gain; at C = 128 it is
 // 28 % slower.
-template <> struct Block3Cfg<ElemF16, 32, 3>   { enum { WM = 1, WN = PM_SKEW16_C32 ? 8 : 4, NTW = 3 }; };
-template <> struct Block3Cfg<ElemF16, 32, 7>   { enum { WM = 1, WN = PM_SKEW16_C32 ? 8 : 4, NTW = 3 }; };
+template <> struct Block3Cfg<ElemF16, 32, 3>   { enum { WM = 1, WN = 4, NTW = 3 }; };
+template <> struct Block3Cfg<ElemF16, 32, 7>   { enum { WM = 1, WN = 4, NTW = 3 }; };
+// (8 waves at C = 32 k 3 / 7 for the skewed walk: +25 %, profiles/r06/ab_skew16.txt)
 template <> struct Block3Cfg<ElemF16, 32, 11>  { enum { WM = 1, WN = 8, NTW = 3 }; };
 template <> struct Block3Cfg<ElemF16, 64, 3>   { enum { WM = 2, WN = 2, NTW = 4 }; };
 template <> struct Block3Cfg<ElemF16, 64, 7>   { enum { WM = 2, WN = 4, NTW = 4 }; };
 template <> struct Block3Cfg<ElemF16, 64, 11>  { enum { WM = 2, WN = 4, NTW = 4 }; };
-#ifndef PM_K3_NTW
-#define PM_K3_NTW 4     // (A/B builds: 3 tiles per wave at C = 128 k 3)
-#endif
-template <> struct Block3Cfg<ElemF16, 128, 3>  { enum { WM = 4, WN = 2, NTW = PM_K3_NTW }; };
+// (3 tiles per wave at C = 128 k 3: not faster, profiles/r06/ab_k3_tiles.txt)
+template <> struct Block3Cfg<ElemF16, 128, 3>  { enum { WM = 4, WN = 2, NTW = 4 }; };
 // C = 128, k 7: walked only (conv_block3_walk_kernel; stand-alone, the 36-column
 // halo on both sides of a 256-column tile made it 28 % slower than three pair
 // launches - walked it is 10.6 % faster, profiles/r02/ab_block128_k7_walk.txt)
@@ -319,338 +230,509 @@ template <> struct Block3CfgNarrow<ElemF16, 64, 11> { enum { WM = 2, WN = 2, NTW
 template <> struct Block3CfgNarrow<ElemF16, 128, 3> { enum { WM = 4, WN = 1, NTW = 4 }; };
 template <int C, int K> struct Block3CfgNarrow<ElemBF16, C, K> : Block3CfgNarrow<ElemF16, C, K> {};
 
+// ---- which kernels exist per geometry ---------------------------------------
+// The 4-byte operand layouts (exact fp32, split f16, split activations) run
+// their C = 32 / 64 Blocks on the skewed walk where it fits: at 16 times / three
+// times the MFMA time per step, what the skew removes - the two-sided
+// tilings' halo recompute - shows (split f16: three skewed Block launches
+// 6.07 ms against 6.99 ms for the fused whole-MRF tiling,
+// profiles/r04/ab_x3_skew.txt; fp32: profiles/r05/ab_x3skew_f32.txt). The
+// 16-bit types stay on the walked / whole-MRF kernels at C = 32 (skewed: +25 %,
+// profiles/r06/ab_skew16.txt).
+template <class ET, int C>
+constexpr bool pm_skew_4byte() { return ET::ESZ == 4 && (C == 32 || C == 64); }
+
+// Whole-Block kernels instantiated for geometry G (Block3Cfg or its narrow
+// variant): the skewed walk (no recompute at all), the walked tiling (no
+// left-halo recompute: where its carry area fits the LDS) and the two-sided
+// tiling. C = 128 k >= 7 and C = 256 exist walked / skewed only (stand-alone
+// they lose to three pair launches, see Block3Cfg).
+template <class ET, int C, int K, class G> struct Block3Kernels {
+    static constexpr int NW = G::WM * G::WN;
+    static constexpr bool SKEW = G::WM != 0 && NW == 8 && G::NTW >= 2 &&
+                                 (ET::ESZ == 2 || pm_skew_4byte<ET, C>());
+    static constexpr bool WALK = G::WM != 0 && NW == 8 && ET::ESZ == 2 &&
+                                 !(C == 128 && K == 11) && !(C == 256 && K == 7);
+    static constexpr bool TILED = G::WM != 0 && !(C == 128 && K >= 7) && C != 256;
+};
+// Whole-MRF kernels (C = 32, the k 11 geometry G for all three Blocks): the
+// skewed walk for the 4-byte layouts, the walked tiling for the 16-bit ones
+// (split f16 walked: 8.4 ms against 7.0 ms for the two-sided tiling - the
+// carry areas only fit beside one tile per wave, round 4), the two-sided
+// tiling for both.
+template <class ET, class G> struct MrfKernels {
+    static constexpr int NW = G::WM * G::WN;
+    static constexpr bool ANY = G::WM != 0 && Block3Cfg<ET, 32, 3>::WM != 0 &&
+                                Block3Cfg<ET, 32, 7>::WM != 0;
+    static constexpr bool SKEW = ANY && ET::ESZ == 4 && NW == 8 && G::NTW >= 2;
+    static constexpr bool WALK = ANY && ET::ESZ == 2 && NW == 8;
+};
+
+// ---- the planner ------------------------------------------------------------
+// One MRF stage - or, for pm_block_cl, one Block. Everything but the weights
+// and dilations is shared by its Blocks; the first Block stores per `mode`
+// (Block3Args::mode), the ones after it add.
+struct PmBlock {
+    int K;
+    const void* w1[PM_MAX_DILATIONS];   // packed weights + bias step
+    const void* w2[PM_MAX_DILATIONS];
+    int dil[PM_MAX_DILATIONS];
+};
+struct PmStage {
+    int C;                    // padded channels
+    const float* x;
+    float* out;
+    int B, L;
+    const int* lengths;       // (B) valid frames per utterance or null
+    int len_scale;
+    int mode;
+    float scale;
+    char* scratch;            // device scratch for the skewed walks, or null
+    size_t scratch_bytes;
+    void* act16;              // the last Block's result as the next
+    int act16_type;           // upsampler's operand (Block3Args::act16), or null
+    int nblocks, niter;
+    PmBlock blk[PM_MAX_RESBLOCKS];
+    PM_TIMELINE_FIELD         // debug stamps (tuning builds)
+};
+
+enum PmKernel { PM_PAIRS, PM_SKEW, PM_WALK, PM_TILED };
+struct PmLaunch {
+    PmKernel kernel = PM_PAIRS;   // PM_PAIRS: one pair launch per iteration
+    bool narrow = false;          // the latency geometry (Block3CfgNarrow)
+    int halo = 0;                 // the tiling's halo columns
+    int nseg = 0;                 // segments per utterance (walks)
+    bool act16 = false;           // writes PmStage::act16 instead of `out`
+};
+struct PmPlan {
+    bool mrf = false;             // one whole-MRF launch: block[0]
+    PmLaunch block[PM_MAX_RESBLOCKS];
+};
+
+inline int pm_halo(int K, int niter, const int* dil) {
+    int halo = 0;
+    for (int i = 0; i < niter; ++i) halo += (dil[i] + 1) * ((K - 1) / 2);
+    return halo;
+}
+// the skewed walk's carries: dilations <= 5 and H2 (d + 1) <= 30
+inline bool pm_skew_dilations(int K, int niter, const int* dil) {
+    for (int i = 0; i < niter; ++i)
+        if (dil[i] < 1 || dil[i] > 5 || ((K - 1) / 2) * (dil[i] + 1) > 30)
+            return false;
+    return true;
+}
+// Segments per utterance of a walk: one workgroup per (utterance, segment),
+// as many as fill the chip (or the test hook's count); 0: no walk (CU count
+// unknown).
+inline int pm_walk_segments(int B) {
+    if (pm_force().walk_nseg) return pm_force().walk_nseg;
+    const int cus = pm_device_cus();
+    return cus > 0 ? std::max(1, cus / B) : 0;
+}
+// The latency geometry (nc_narrow columns instead of nc_wide) where the wide
+// tiling gives the chip fewer than PM_NARROW_BELOW workgroups. (A forced walk
+// - tests - keeps the 8-wave geometry the walks exist for.)
+inline bool pm_take_narrow(int nc_wide, int nc_narrow, int halo, int B, int L) {
+    const int TL = nc_wide - 2 * halo, TLn = nc_narrow - 2 * halo;
+    return pm_narrow_allowed() && !pm_force().walk_nseg && TL > 0 &&
+           TLn >= 32 && (long long)((L + TL - 1) / TL) * B < PM_NARROW_BELOW;
+}
+
+template <class ET, int C>
+static bool plan_pair_c(int K, int B, int L) {
+    typedef PairCfg<ET, C> W;
+    typedef PairCfgNarrow<ET, C> N;
+    if constexpr ((int)N::NTW != (int)W::NTW || (int)N::WN != (int)W::WN) {
+        const int TL = W::WN * W::NTW * 32 - (K - 1);
+        return pm_narrow_allowed() &&
+               (long long)((L + TL - 1) / TL) * B < PM_NARROW_BELOW;
+    }
+    return false;
+}
+// Pair launch (one Block iteration): whether it takes PairCfgNarrow
+template <class ET> bool pm_plan_pair(int C, int K, int B, int L) {
+    switch (C) {
+        case 256: return plan_pair_c<ET, 256>(K, B, L);
+        case 128: return plan_pair_c<ET, 128>(K, B, L);
+    }
+    return false;
+}
+
 template <class ET, int C, int K, class G>
-static hipError_t launch_block3_cfg(const Block3Args& a0, hipStream_t stream) {
+static bool plan_block_cfg(const PmStage& s, int j, PmLaunch* l) {
+    typedef Block3Kernels<ET, C, K, G> KS;
     if constexpr (G::WM == 0) {
-        return hipErrorNotSupported;
+        return false;
     } else {
-    constexpr int WM = G::WM, WN = G::WN, NTW = G::NTW;
-    constexpr int NC = WN * NTW * 32;
-    Block3Args a = a0;
-    a.halo = 0;
-    for (int i = 0; i < a.niter; ++i) a.halo += (a.dil[i] + 1) * ((K - 1) / 2);
-    a.TL = NC - 2 * a.halo;
-    if (a.TL < 32) return hipErrorNotSupported;
-    a.ntiles = (a.L + a.TL - 1) / a.TL;
-    constexpr int smem = block3_smem_bytes<ET, C, K, WM, WN, NTW>();
-    // Skewed walk (no recompute at all) for grids that fill the chip several
-    // times over: needs scratch, dilations <= 5 and H2 (d + 1) <= 30
-    // (split f16, C = 32: the last stage of the 'checkpoint' operand mode is
-    // MFMA-bound at three MFMAs per step, so what the skew removes - the 23 %
-    // halo of the stand-alone whole-MRF tiling - shows: three skewed Block
-    // launches 6.07 ms against 6.99 ms fused, profiles/r04/ab_x3_skew.txt)
-    constexpr bool X3SKEW = pm_x3skew_id(ET::ID) &&
-                            (C == 32 || (C == 64 && ET::ESZ == 4));
-    if constexpr ((ET::ESZ == 2 || X3SKEW) && WM * WN == 8 && NTW >= 2) {
-        typedef SkewGeom<ET, C, K, WM, WN, NTW> GE;
-        static_assert(GE::SCRATCH <= PM_SKEW_WG_SCRATCH, "scratch bound");
-        const int cus = pm_device_cus();
-        const int forced = pm_force().walk_nseg;
+    constexpr int NC = G::WN * G::NTW * 32;
+    const int* dil = s.blk[j].dil;
+    l->halo = pm_halo(K, s.niter, dil);
+    if (NC - 2 * l->halo < 32) return false;
+    const PmForce& f = pm_force();
+    const int nseg = pm_walk_segments(s.B);
+    if constexpr (KS::SKEW) {
         // Measured at batch 32 x 10 s (profiles/r03/ab_skew.txt): -14 % at C = 128
         // k 11 (against three pair launches), -10 % at C = 128 k 7, -7 % at
         // C = 64 k 11, -1.3 % at C = 64 k 7 (against the walked kernels); where
         // the walked halo is small (k 3: 12 columns) its carries and the
         // hand-over cost 5 % more than the recompute they save, on the
         // 128-column tiles of C = 256 k 7 it is even with three pair launches.
-        constexpr bool WINS = ((C == 128 || C == 64) && K >= 7) || X3SKEW;
-        bool fits = GE::SMEM <= 160 * 1024 && a.niter >= 1 && a.niter <= 3 &&
-                    a.scratch && (cus > 0 || forced) &&
-                    (pm_force().skew > 0 || (pm_force().skew == 0 && WINS));
-        for (int i = 0; i < a.niter; ++i)
-            fits = fits && a.dil[i] >= 1 && a.dil[i] <= 5 &&
-                   ((K - 1) / 2) * (a.dil[i] + 1) <= 30;
-        if (fits) {
-            int nseg = forced ? forced : cus / a.B;
-            if (nseg < 1) nseg = 1;
-            const size_t need = (size_t)a.B * nseg * GE::SCRATCH;
-            if ((forced || (a.L / NC) / nseg >= 4) && need <= a.scratch_bytes) {
-                Block3SkewArgs p;
-                if (a.act16 && a.act16_done) *a.act16_done = 1;
-                a.act16_done = nullptr;     // (a host pointer)
-                p.a = a; p.nseg = nseg; p.wg_scratch = GE::SCRATCH;
-                p.scratch = a.scratch;
-                auto skew = conv_block3_skew_kernel<ET, C, K, WM, WN, NTW>;
-                hipError_t e = pm_ensure_dynamic_lds(
-                    reinterpret_cast<const void*>(skew), GE::SMEM);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(skew, dim3(a.B * nseg), dim3(WM * WN * 64),
-                                   GE::SMEM, stream, p);
-                return hipGetLastError();
-            }
+        typedef SkewGeom<ET, C, K, G::WM, G::WN, G::NTW> GE;
+        static_assert(GE::SCRATCH <= PM_SKEW_WG_SCRATCH, "scratch bound");
+        constexpr bool WINS = ((C == 128 || C == 64) && K >= 7) ||
+                              pm_skew_4byte<ET, C>();
+        // (for grids that fill the chip several times over)
+        if (GE::SMEM <= PM_LDS_BYTES && s.scratch && nseg > 0 &&
+            (f.skew > 0 || (f.skew == 0 && WINS)) &&
+            pm_skew_dilations(K, s.niter, dil) &&
+            (f.walk_nseg || (s.L / NC) / nseg >= 4) &&
+            (size_t)s.B * nseg * GE::SCRATCH <= s.scratch_bytes) {
+            l->kernel = PM_SKEW;
+            l->nseg = nseg;
+            l->act16 = s.act16 && j == s.nblocks - 1;
+            return true;
         }
     }
-    a.act16 = nullptr; a.act16_done = nullptr;   // (the skewed walk only)
-    // Walked variant (no left-halo recompute) for grids that fill the chip
-    // several times over, where its carry area (halo rows) fits the LDS
-    if constexpr (ET::ESZ == 2 && WM * WN == 8 && !(C == 128 && K == 11) &&
-                  !(C == 256 && K == 7)) {
-        const int smem_walk = block3_walk_smem_bytes<ET, C, K, WM, WN, NTW>() +
-                              block3_carry_bytes<ET, C>(a.halo);
-        const int cus = pm_device_cus();
-        const int forced = pm_force().walk_nseg;
-        if (a.niter <= 3 && smem_walk <= 160 * 1024 && (cus > 0 || forced)) {
-            int nseg = forced ? forced : cus / a.B;
-            if (nseg < 1) nseg = 1;
-            if (forced || (a.L / (NC - a.halo)) / nseg >= 6) {
-                Block3WalkArgs p;
-                p.a = a; p.nseg = nseg;
-                auto walk = conv_block3_walk_kernel<ET, C, K, WM, WN, NTW>;
-                hipError_t e = pm_ensure_dynamic_lds(
-                    reinterpret_cast<const void*>(walk), smem_walk);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(walk, dim3(a.B * nseg), dim3(WM * WN * 64),
-                                   smem_walk, stream, p);
-                return hipGetLastError();
-            }
+    if constexpr (KS::WALK) {
+        const int smem = block3_walk_smem_bytes<ET, C, K, G::WM, G::WN, G::NTW>() +
+                         block3_carry_bytes<ET, C>(l->halo);
+        if (smem <= PM_LDS_BYTES && nseg > 0 &&
+            (f.walk_nseg || (s.L / (NC - l->halo)) / nseg >= 6)) {
+            l->kernel = PM_WALK;
+            l->nseg = nseg;
+            return true;
         }
     }
-    if constexpr ((C == 128 && K >= 7) || C == 256)
-        return hipErrorNotSupported;  // walked only
-    auto kern = conv_block3_kernel<ET, C, K, WM, WN, NTW>;
-    hipError_t e = pm_ensure_dynamic_lds(
-        reinterpret_cast<const void*>(kern), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(a.ntiles * a.B), dim3(WM * WN * 64), smem,
-                       stream, a);
-    return hipGetLastError();
+    if constexpr (KS::TILED) {
+        l->kernel = PM_TILED;
+        return true;
+    }
+    return false;
     }
 }
 
 template <class ET, int C, int K>
-static hipError_t launch_block3_ck(const Block3Args& a, hipStream_t stream) {
+static PmLaunch plan_block_ck(const PmStage& s, int j) {
     typedef Block3Cfg<ET, C, K> W;
     typedef Block3CfgNarrow<ET, C, K> N;
+    PmLaunch l;
     if constexpr ((int)W::WM != 0 && (int)N::WN != (int)W::WN) {
-        int halo = 0;
-        for (int i = 0; i < a.niter; ++i) halo += (a.dil[i] + 1) * ((K - 1) / 2);
-        const int TL = W::WN * W::NTW * 32 - 2 * halo;
-        const int TLn = N::WN * N::NTW * 32 - 2 * halo;
-        // (a forced walk - tests - keeps the 8-wave geometry the walks exist for)
-        const bool allowed = pm_narrow_allowed() && !pm_force().walk_nseg;
-        if (allowed && TL > 0 && TLn >= 32 &&
-            (long long)((a.L + TL - 1) / TL) * a.B < PM_NARROW_BELOW)
-            return launch_block3_cfg<ET, C, K, N>(a, stream);
+        if (pm_take_narrow(W::WN * W::NTW * 32, N::WN * N::NTW * 32,
+                           pm_halo(K, s.niter, s.blk[j].dil), s.B, s.L)) {
+            l.narrow = true;
+            return plan_block_cfg<ET, C, K, N>(s, j, &l) ? l : PmLaunch();
+        }
     }
-    return launch_block3_cfg<ET, C, K, W>(a, stream);
+    return plan_block_cfg<ET, C, K, W>(s, j, &l) ? l : PmLaunch();
 }
 
-template <class ET, int C>
-static hipError_t launch_block3_c(int K, const Block3Args& a, hipStream_t s) {
-    switch (K) {
-        case 3: return launch_block3_ck<ET, C, 3>(a, s);
-        case 7: return launch_block3_ck<ET, C, 7>(a, s);
-        case 11: return launch_block3_ck<ET, C, 11>(a, s);
-    }
-    return hipErrorNotSupported;
+// Block j of the stage: a whole-Block launch, or PM_PAIRS where no whole-Block
+// kernel takes the shape
+template <class ET> PmLaunch pm_plan_block(const PmStage& s, int j) {
+    if (s.niter < 1 || s.niter > 3) return PmLaunch();
+    for (int i = 0; i < s.niter; ++i)
+        if (s.blk[j].dil[i] < 1 || s.blk[j].dil[i] > 5) return PmLaunch();
+    const int K = s.blk[j].K;
+#define PM_PLAN_C(C_)                                                        \
+    case C_:                                                                 \
+        if (K == 3) return plan_block_ck<ET, C_, 3>(s, j);                   \
+        if (K == 7) return plan_block_ck<ET, C_, 7>(s, j);                   \
+        if (K == 11) return plan_block_ck<ET, C_, 11>(s, j);                 \
+        break;
+    switch (s.C) { PM_PLAN_C(32) PM_PLAN_C(64) PM_PLAN_C(128) PM_PLAN_C(256) }
+#undef PM_PLAN_C
+    return PmLaunch();
 }
 
-// Whole-MRF launch: kernel sizes (3, 7, 11), the k = 11 tiling for all three.
-template <class ET, int C, class G>
-static hipError_t launch_mrf_cfg(const Block3Args (&blocks)[3], hipStream_t stream) {
-    if constexpr (G::WM == 0 || Block3Cfg<ET, C, 3>::WM == 0 ||
-                  Block3Cfg<ET, C, 7>::WM == 0) {
-        return hipErrorNotSupported;
+template <class ET, class G>
+static bool plan_mrf_cfg(const PmStage& s, bool blocks_ok, PmLaunch* l) {
+    typedef MrfKernels<ET, G> KS;
+    if constexpr (!KS::ANY) {
+        return false;
     } else {
-    constexpr int WM = G::WM, WN = G::WN, NTW = G::NTW;
-    constexpr int NC = WN * NTW * 32;
-    MrfArgs m;
-    int halo = 0;
-    constexpr int KS[3] = {3, 7, 11};
-    for (int j = 0; j < 3; ++j) {
-        m.k[j] = blocks[j];
-        int h = 0;
-        for (int i = 0; i < m.k[j].niter; ++i)
-            h += (m.k[j].dil[i] + 1) * ((KS[j] - 1) / 2);
-        halo = h > halo ? h : halo;
-    }
-    const int TL = NC - 2 * halo;
-    if (TL < 32) return hipErrorNotSupported;
-    // one x tile serves the three Blocks (generator.py MRF: every Block of a
-    // stage reads the stage input)
-    if (blocks[0].x != blocks[1].x || blocks[0].x != blocks[2].x ||
-        blocks[0].L != blocks[1].L || blocks[0].L != blocks[2].L)
-        return hipErrorNotSupported;
-    for (int j = 0; j < 3; ++j) {
-        m.k[j].halo = halo; m.k[j].TL = TL;
-        m.k[j].ntiles = (m.k[j].L + TL - 1) / TL;
-#ifdef PM_TUNING
-        m.k[j].timeline = nullptr;
-#endif
-    }
-    // Skewed whole-MRF walk (conv_mrf_skew_kernel): the operand layouts that
-    // run this stage Block by Block on the skewed walk (pm_x3skew_id), when
-    // the caller hands scratch over and the grid fills the chip several times
-    if constexpr (PM_MRF_SKEW && pm_x3skew_id(ET::ID) && C == 32 &&
-                  WM * WN == 8 && NTW >= 2) {
-        typedef MrfSkewGeom<ET, C, WM, WN, NTW> MG;
+    constexpr int NC = G::WN * G::NTW * 32;
+    constexpr int KS3[3] = {3, 7, 11};
+    l->halo = 0;
+    for (int j = 0; j < 3; ++j)
+        l->halo = std::max(l->halo, pm_halo(KS3[j], s.niter, s.blk[j].dil));
+    if (NC - 2 * l->halo < 32) return false;
+    const PmForce& f = pm_force();
+    const int nseg = pm_walk_segments(s.B);
+    if constexpr (KS::SKEW) {
+        typedef MrfSkewGeom<ET, 32, G::WM, G::WN, G::NTW> MG;
         static_assert(MG::SCRATCH <= PM_SKEW_WG_SCRATCH, "scratch bound");
-        const int cus = pm_device_cus();
-        const int forced = pm_force().walk_nseg;
-        const Block3Args& a = blocks[0];
-        bool fits = MG::SMEM <= 160 * 1024 && a.scratch &&
-                    (cus > 0 || forced) && pm_force().skew >= 0;
-        for (int j = 0; j < 3; ++j) {
-            fits = fits && blocks[j].niter == 3;
-            for (int i = 0; i < 3 && fits; ++i)
-                fits = blocks[j].dil[i] >= 1 && blocks[j].dil[i] <= 5 &&
-                       ((KS[j] - 1) / 2) * (blocks[j].dil[i] + 1) <= 30;
+        bool fits = MG::SMEM <= PM_LDS_BYTES && s.scratch && nseg > 0 &&
+                    f.skew >= 0 && s.niter == 3;
+        for (int j = 0; j < 3; ++j)
+            fits = fits && pm_skew_dilations(KS3[j], 3, s.blk[j].dil);
+        if (fits && (f.walk_nseg || (s.L / NC) / nseg >= 4) &&
+            (size_t)s.B * nseg * MG::SCRATCH <= s.scratch_bytes) {
+            l->kernel = PM_SKEW;
+            l->nseg = nseg;
+            return true;
         }
-        if (fits) {
-            int nseg = forced ? forced : cus / a.B;
-            if (nseg < 1) nseg = 1;
-            const size_t need = (size_t)a.B * nseg * MG::SCRATCH;
-            if ((forced || (a.L / NC) / nseg >= 4) && need <= a.scratch_bytes) {
-                MrfSkewArgs p = {};
-                p.x = a.x; p.out = a.out;
-                for (int j = 0; j < 3; ++j)
-                    for (int n = 0; n < 3; ++n) {
-                        p.w1[j][n] = blocks[j].w1[n];
-                        p.w2[j][n] = blocks[j].w2[n];
-                        p.dil[j][n] = blocks[j].dil[n];
-                    }
-                p.B = a.B; p.L = a.L; p.halo = halo; p.scale = a.scale;
-                p.lengths = a.lengths; p.len_scale = a.len_scale;
-                p.nseg = nseg; p.wg_scratch = MG::SCRATCH;
-                p.scratch = a.scratch;
-#ifdef PM_TUNING
-                p.timeline = blocks[0].timeline;
-#endif
-                auto kern = conv_mrf_skew_kernel<ET, C, WM, WN, NTW>;
-                hipError_t e = pm_ensure_dynamic_lds(
-                    reinterpret_cast<const void*>(kern), MG::SMEM);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kern, dim3(a.B * nseg), dim3(WM * WN * 64),
-                                   MG::SMEM, stream, p);
-                return hipGetLastError();
-            }
+        // A batch long enough for the skewed walk never takes the two-sided
+        // tiling below (pm_skew_4byte): Block by Block instead - unless the
+        // test hook has switched the skewed walk off altogether, which makes
+        // the tiling, whose sum order is the skewed whole-MRF walk's, the
+        // stand-alone counterpart the tests compare bit for bit.
+        const int cus = pm_device_cus();
+        if (blocks_ok && f.skew >= 0 && s.scratch && cus > 0 &&
+            (s.L / NC) / std::max(1, cus / s.B) >= 4)
+            return false;
+    }
+    if constexpr (KS::WALK) {
+        // (enough tiles per segment to amortise its two-sided first tile)
+        if (nseg > 0 && s.niter == 3 &&
+            (f.walk_nseg || (s.L / (NC - l->halo)) / nseg >= 8)) {
+            l->kernel = PM_WALK;
+            l->nseg = nseg;
+            return true;
         }
     }
-    // (skew_only: the caller prefers Block-by-Block skewed launches to the
-    // two-sided tiling below - except when the test hook has switched the
-    // skewed walk off altogether: then this launch, whose sum order is the
-    // skewed whole-MRF walk's, is the stand-alone counterpart the tests compare
-    // bit for bit)
-    if (blocks[0].skew_only && pm_force().skew >= 0)
-        return hipErrorNotSupported;
-    // Walked variant (no left-halo recompute): one workgroup per (utterance,
-    // segment) with enough tiles per segment to amortise its two-sided first
-    // tile; the sum-in-registers geometry (C = 32) only. (Split-f16 operands,
-    // 4 bytes per element in LDS: the carry areas only fit beside 256-column
-    // tiles of one tile per wave, and that walked variant measured 8.4 ms
-    // against 7.0 ms for the stand-alone 512-column tiling - round 4, not kept.)
-    if constexpr (C == 32 && ET::ESZ == 2 && WM * WN == 8) {
-        const int cus = pm_device_cus();
-        const int forced = pm_force().walk_nseg;
-        if ((cus > 0 || forced) &&
-            m.k[0].niter == 3 && m.k[1].niter == 3 && m.k[2].niter == 3) {
-            const int B = m.k[0].B, L = m.k[0].L;
-            const int step = NC - halo;
-            int nseg = forced ? forced : cus / B;
-            if (nseg < 1) nseg = 1;
-            const int tiles_per_seg = (L / step) / nseg;
-            if (forced || tiles_per_seg >= 8) {
-                MrfWalkArgs wa = {};
-                wa.x = m.k[0].x; wa.out = m.k[0].out;
-                for (int j = 0; j < 3; ++j)
-                    for (int n = 0; n < 3; ++n) {
-                        wa.w1[j][n] = m.k[j].w1[n];
-                        wa.w2[j][n] = m.k[j].w2[n];
-                        wa.dil[j][n] = m.k[j].dil[n];
-                    }
-                wa.B = B; wa.L = L; wa.halo = halo; wa.scale = m.k[0].scale;
-                wa.lengths = m.k[0].lengths; wa.len_scale = m.k[0].len_scale;
-                wa.nseg = nseg;
-                auto walk = conv_mrf_walk_kernel<ET, C, WM, WN, NTW>;
-                const int smem_walk =
-                    block3_walk_smem_bytes<ET, C, 11, WM, WN, NTW>() +
-                    3 * block3_carry_bytes<ET, C>(halo);
-                hipError_t e = pm_ensure_dynamic_lds(
-                    reinterpret_cast<const void*>(walk), smem_walk);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(walk, dim3(B * nseg), dim3(WM * WN * 64),
-                                   smem_walk, stream, wa);
-                return hipGetLastError();
-            }
-        }
-    }
-    auto kern = conv_mrf_kernel<ET, C, WM, WN, NTW, C == 32>;
-    constexpr int smem = block3_smem_bytes<ET, C, 11, WM, WN, NTW>();
-    hipError_t e = pm_ensure_dynamic_lds(
-        reinterpret_cast<const void*>(kern), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(m.k[0].ntiles * m.k[0].B),
-                       dim3(WM * WN * 64), smem, stream, m);
-    return hipGetLastError();
+    l->kernel = PM_TILED;
+    return true;
     }
 }
 
-template <class ET, int C>
-static hipError_t launch_mrf_c(const Block3Args (&blocks)[3], hipStream_t stream) {
-    typedef Block3Cfg<ET, C, 11> W;
-    typedef Block3CfgNarrow<ET, C, 11> N;
+// The whole stage (Blocks k = 3, 7, 11) in one launch - C = 32 only: C = 64
+// has no registers left for the sum (trunk + accumulator are 128 VGPRs), its
+// whole-MRF variant read-modify-writes `out` through L2, the lines do not
+// survive there (rocprof: 2.6 GB written per launch instead of 0.9) and it
+// only ties with three Block launches. blocks_ok: the caller can run the
+// stage Block by Block instead. False: no whole-MRF launch.
+template <class ET> bool pm_plan_mrf(const PmStage& s, bool blocks_ok, PmLaunch* l) {
+    *l = PmLaunch();
+    if (s.C != 32 || s.nblocks != 3 || s.niter < 1 || s.niter > 3 ||
+        s.blk[0].K != 3 || s.blk[1].K != 7 || s.blk[2].K != 11)
+        return false;
+    for (int j = 0; j < 3; ++j)
+        for (int i = 0; i < s.niter; ++i)
+            if (s.blk[j].dil[i] < 1 || s.blk[j].dil[i] > 5) return false;
+    typedef Block3Cfg<ET, 32, 11> W;
+    typedef Block3CfgNarrow<ET, 32, 11> N;
     if constexpr ((int)W::WM != 0 && (int)N::WN != (int)W::WN) {
-        int halo = 0;
-        for (int i = 0; i < blocks[2].niter; ++i) halo += (blocks[2].dil[i] + 1) * 5;
-        const int TL = W::WN * W::NTW * 32 - 2 * halo;
-        const int TLn = N::WN * N::NTW * 32 - 2 * halo;
-        const bool allowed = pm_narrow_allowed() && !pm_force().walk_nseg;
-        if (allowed && TL > 0 && TLn >= 32 &&
-            (long long)((blocks[0].L + TL - 1) / TL) * blocks[0].B < PM_NARROW_BELOW)
-            return launch_mrf_cfg<ET, C, N>(blocks, stream);
+        if (pm_take_narrow(W::WN * W::NTW * 32, N::WN * N::NTW * 32,
+                           pm_halo(11, s.niter, s.blk[2].dil), s.B, s.L)) {
+            l->narrow = true;
+            return plan_mrf_cfg<ET, N>(s, blocks_ok, l);
+        }
     }
-    return launch_mrf_cfg<ET, C, W>(blocks, stream);
+    return plan_mrf_cfg<ET, W>(s, blocks_ok, l);
 }
 
-template <class ET>
-hipError_t pm_launch_mrf(int C, const Block3Args (&blocks)[3], hipStream_t s) {
-    for (int j = 0; j < 3; ++j) {
-        if (blocks[j].niter < 1 || blocks[j].niter > 3)
-            return hipErrorNotSupported;
-        for (int i = 0; i < blocks[j].niter; ++i)
-            if (blocks[j].dil[i] < 1 || blocks[j].dil[i] > 5)
-                return hipErrorNotSupported;
+// The stage at fusion level `fusion` (pm_fusion_level)
+template <class ET> PmPlan pm_plan_stage(const PmStage& s, int fusion) {
+    PmPlan p;
+    if (fusion >= 2 && pm_plan_mrf<ET>(s, true, &p.block[0])) {
+        p.mrf = true;
+        return p;
     }
-    // C = 64 has no registers left for the sum (trunk + accumulator are 128
-    // VGPRs): its whole-MRF variant read-modify-writes `out` through L2, the
-    // lines do not survive there (rocprof: 2.6 GB written per launch instead
-    // of 0.9) and it only ties with three Block launches - not used.
-    if (C == 32) return launch_mrf_c<ET, 32>(blocks, s);
-    return hipErrorNotSupported;
+    for (int j = 0; j < s.nblocks; ++j)
+        p.block[j] = fusion >= 1 ? pm_plan_block<ET>(s, j) : PmLaunch();
+    return p;
+}
+
+// ---- launchers --------------------------------------------------------------
+template <class ET> hipError_t pm_launch_pair(
+    int C, int K, bool narrow, const PairArgs& args, hipStream_t stream);
+// Block j of the stage as planned (not PM_PAIRS)
+template <class ET> hipError_t pm_launch_block3(
+    const PmLaunch& plan, const PmStage& s, int j, hipStream_t stream);
+// The stage as one whole-MRF launch, as planned
+template <class ET> hipError_t pm_launch_mrf(
+    const PmLaunch& plan, const PmStage& s, hipStream_t stream);
+
+// kind 0: plain conv with KT = KSPAN = 7 (input conv); kind 1: polyphase
+// ConvTranspose (KT = 2, KSPAN = 3). cfg: 0 = 256 x 128 tile, 1 = 64 x 128,
+// 3 = 128 x 128 (measured: a 512 x 128 tile is 20 % slower than cfg 0),
+// 2 = 32 x 128.
+template <class ET> hipError_t pm_launch_single(
+    int kind, int ch, int cfg, const SingleArgs& args, hipStream_t stream);
+hipError_t pm_launch_stft(int epi, const SingleArgs& args, hipStream_t stream);
+
+#ifdef PM_INSTANTIATE
+
+template <class Kern, class Args>
+static hipError_t launch_with_lds(Kern kern, int grid, int threads, int smem,
+                                  hipStream_t stream, const Args& args) {
+    hipError_t e = pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), smem, stream, args);
+    return hipGetLastError();
+}
+
+template <class ET, int C, int K, class G>
+static hipError_t launch_pair_cfg(const PairArgs& a0, hipStream_t stream) {
+    constexpr int WM = G::WM, WN = G::WN, NTW = G::NTW, CH = G::CH;
+    constexpr int ALIAS = G::ALIAS;
+    constexpr int TL = WN * NTW * 32 - (K - 1);
+    PairArgs a = a0;
+    a.ntiles = (a.L + TL - 1) / TL;
+    return launch_with_lds(
+        conv_pair_kernel<ET, C, K, WM, WN, NTW, CH, ALIAS>, a.ntiles * a.B,
+        WM * WN * 64,
+        pair_smem_bytes<ET, C, K, WM, WN, NTW, CH, ALIAS>(a.dilation), stream, a);
 }
 
 template <class ET, int C>
-static bool block3_supported_c(int K) {
+static hipError_t launch_pair_c(int K, bool narrow, const PairArgs& a, hipStream_t s) {
+    typedef PairCfg<ET, C> W;
+    typedef PairCfgNarrow<ET, C> N;
     switch (K) {
-        case 3: return Block3Cfg<ET, C, 3>::WM != 0;
-        case 7: return Block3Cfg<ET, C, 7>::WM != 0;
-        case 11: return Block3Cfg<ET, C, 11>::WM != 0;
+        case 3: return narrow ? launch_pair_cfg<ET, C, 3, N>(a, s) : launch_pair_cfg<ET, C, 3, W>(a, s);
+        case 7: return narrow ? launch_pair_cfg<ET, C, 7, N>(a, s) : launch_pair_cfg<ET, C, 7, W>(a, s);
+        case 11: return narrow ? launch_pair_cfg<ET, C, 11, N>(a, s) : launch_pair_cfg<ET, C, 11, W>(a, s);
     }
-    return false;
+    return hipErrorInvalidValue;
 }
 
 template <class ET>
-bool pm_block3_supported(int C, int K) {
+hipError_t pm_launch_pair(int C, int K, bool narrow, const PairArgs& a, hipStream_t s) {
     switch (C) {
-        case 256: return block3_supported_c<ET, 256>(K);
-        case 128: return block3_supported_c<ET, 128>(K);
-        case 64: return block3_supported_c<ET, 64>(K);
-        case 32: return block3_supported_c<ET, 32>(K);
+        case 256: return launch_pair_c<ET, 256>(K, narrow, a, s);
+        case 128: return launch_pair_c<ET, 128>(K, narrow, a, s);
+        case 64: return launch_pair_c<ET, 64>(K, narrow, a, s);
+        case 32: return launch_pair_c<ET, 32>(K, narrow, a, s);
     }
-    return false;
+    return hipErrorInvalidValue;
+}
+
+// Block j's arguments, tiled with `halo` columns on NC-column tiles
+static Block3Args block3_args(const PmStage& s, int j, int NC, int halo) {
+    Block3Args a = {};
+    a.x = s.x; a.out = s.out; a.niter = s.niter;
+    for (int n = 0; n < s.niter; ++n) {
+        a.w1[n] = s.blk[j].w1[n];
+        a.w2[n] = s.blk[j].w2[n];
+        a.dil[n] = s.blk[j].dil[n];
+    }
+    a.B = s.B; a.L = s.L; a.mode = j == 0 ? s.mode : 2; a.scale = s.scale;
+    a.halo = halo; a.TL = NC - 2 * halo; a.ntiles = (s.L + a.TL - 1) / a.TL;
+    a.lengths = s.lengths; a.len_scale = s.len_scale;
+#ifdef PM_TUNING
+    a.timeline = s.timeline;
+#endif
+    return a;
+}
+
+template <class ET, int C, int K, class G>
+static hipError_t launch_block3_cfg(const PmLaunch& l, const PmStage& s, int j,
+                                    hipStream_t stream) {
+    typedef Block3Kernels<ET, C, K, G> KS;
+    constexpr int WM = G::WM, WN = G::WN, NTW = G::NTW, NT = WM * WN * 64;
+    Block3Args a = block3_args(s, j, WN * NTW * 32, l.halo);
+    if constexpr (KS::SKEW) if (l.kernel == PM_SKEW) {
+        typedef SkewGeom<ET, C, K, WM, WN, NTW> GE;
+        if (l.act16) { a.act16 = s.act16; a.act16_type = s.act16_type; }
+        Block3SkewArgs p;
+        p.a = a; p.nseg = l.nseg; p.wg_scratch = GE::SCRATCH;
+        p.scratch = s.scratch;
+        return launch_with_lds(conv_block3_skew_kernel<ET, C, K, WM, WN, NTW>,
+                               a.B * l.nseg, NT, GE::SMEM, stream, p);
+    }
+    if constexpr (KS::WALK) if (l.kernel == PM_WALK) {
+        Block3WalkArgs p;
+        p.a = a; p.nseg = l.nseg;
+        return launch_with_lds(
+            conv_block3_walk_kernel<ET, C, K, WM, WN, NTW>, a.B * l.nseg, NT,
+            block3_walk_smem_bytes<ET, C, K, WM, WN, NTW>() +
+                block3_carry_bytes<ET, C>(a.halo),
+            stream, p);
+    }
+    if constexpr (KS::TILED) if (l.kernel == PM_TILED)
+        return launch_with_lds(conv_block3_kernel<ET, C, K, WM, WN, NTW>,
+                               a.ntiles * a.B, NT,
+                               block3_smem_bytes<ET, C, K, WM, WN, NTW>(), stream, a);
+    return hipErrorInvalidValue;
+}
+
+template <class ET, int C, int K>
+static hipError_t launch_block3_ck(const PmLaunch& l, const PmStage& s, int j,
+                                   hipStream_t stream) {
+    return l.narrow
+        ? launch_block3_cfg<ET, C, K, Block3CfgNarrow<ET, C, K>>(l, s, j, stream)
+        : launch_block3_cfg<ET, C, K, Block3Cfg<ET, C, K>>(l, s, j, stream);
 }
 
 template <class ET>
-hipError_t pm_launch_block3(int C, int K, const Block3Args& a, hipStream_t s) {
-    for (int i = 0; i < a.niter; ++i)
-        if (a.dil[i] < 1 || a.dil[i] > 5) return hipErrorNotSupported;
-    if (a.niter < 1 || a.niter > 3) return hipErrorNotSupported;
-    switch (C) {
-        case 256: return launch_block3_c<ET, 256>(K, a, s);
-        case 128: return launch_block3_c<ET, 128>(K, a, s);
-        case 64: return launch_block3_c<ET, 64>(K, a, s);
-        case 32: return launch_block3_c<ET, 32>(K, a, s);
+hipError_t pm_launch_block3(const PmLaunch& l, const PmStage& s, int j,
+                            hipStream_t stream) {
+    const int K = s.blk[j].K;
+#define PM_LAUNCH_C(C_)                                                      \
+    case C_:                                                                 \
+        if (K == 3) return launch_block3_ck<ET, C_, 3>(l, s, j, stream);     \
+        if (K == 7) return launch_block3_ck<ET, C_, 7>(l, s, j, stream);     \
+        if (K == 11) return launch_block3_ck<ET, C_, 11>(l, s, j, stream);   \
+        break;
+    switch (s.C) { PM_LAUNCH_C(32) PM_LAUNCH_C(64) PM_LAUNCH_C(128) PM_LAUNCH_C(256) }
+#undef PM_LAUNCH_C
+    return hipErrorInvalidValue;
+}
+
+// What the skewed and the walked whole-MRF arguments share
+template <class A>
+static void mrf_walk_args(A& p, const PmStage& s, const PmLaunch& l) {
+    p.x = s.x; p.out = s.out;
+    for (int j = 0; j < 3; ++j)
+        for (int n = 0; n < 3; ++n) {
+            p.w1[j][n] = s.blk[j].w1[n];
+            p.w2[j][n] = s.blk[j].w2[n];
+            p.dil[j][n] = s.blk[j].dil[n];
+        }
+    p.B = s.B; p.L = s.L; p.halo = l.halo; p.scale = s.scale;
+    p.lengths = s.lengths; p.len_scale = s.len_scale;
+    p.nseg = l.nseg;
+}
+
+template <class ET, class G>
+static hipError_t launch_mrf_cfg(const PmLaunch& l, const PmStage& s,
+                                 hipStream_t stream) {
+    typedef MrfKernels<ET, G> KS;
+    constexpr int C = 32, WM = G::WM, WN = G::WN, NTW = G::NTW;
+    constexpr int NT = WM * WN * 64;
+    if constexpr (KS::SKEW) if (l.kernel == PM_SKEW) {
+        typedef MrfSkewGeom<ET, C, WM, WN, NTW> MG;
+        MrfSkewArgs p = {};
+        mrf_walk_args(p, s, l);
+        p.wg_scratch = MG::SCRATCH;
+        p.scratch = s.scratch;
+#ifdef PM_TUNING
+        p.timeline = s.timeline;
+#endif
+        return launch_with_lds(conv_mrf_skew_kernel<ET, C, WM, WN, NTW>,
+                               s.B * l.nseg, NT, MG::SMEM, stream, p);
     }
-    return hipErrorNotSupported;
+    if constexpr (KS::WALK) if (l.kernel == PM_WALK) {
+        MrfWalkArgs p = {};
+        mrf_walk_args(p, s, l);
+        return launch_with_lds(
+            conv_mrf_walk_kernel<ET, C, WM, WN, NTW>, s.B * l.nseg, NT,
+            block3_walk_smem_bytes<ET, C, 11, WM, WN, NTW>() +
+                3 * block3_carry_bytes<ET, C>(l.halo),
+            stream, p);
+    }
+    if constexpr (KS::ANY) if (l.kernel == PM_TILED) {
+        MrfArgs m;
+        for (int j = 0; j < 3; ++j) {
+            m.k[j] = block3_args(s, j, WN * NTW * 32, l.halo);
+#ifdef PM_TUNING
+            m.k[j].timeline = nullptr;
+#endif
+        }
+        return launch_with_lds(conv_mrf_kernel<ET, C, WM, WN, NTW, true>,
+                               m.k[0].ntiles * s.B, NT,
+                               block3_smem_bytes<ET, C, 11, WM, WN, NTW>(), stream, m);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <class ET>
+hipError_t pm_launch_mrf(const PmLaunch& l, const PmStage& s, hipStream_t stream) {
+    if (s.C != 32) return hipErrorInvalidValue;
+    return l.narrow
+        ? launch_mrf_cfg<ET, Block3CfgNarrow<ET, 32, 11>>(l, s, stream)
+        : launch_mrf_cfg<ET, Block3Cfg<ET, 32, 11>>(l, s, stream);
 }
 
 // ---- single conv ----------------------------------------------------------
