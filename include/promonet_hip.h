@@ -465,6 +465,57 @@ int pm_loudness(const float* audio, const float* a_weights, float* out,
                 int batch, int samples, int bands, float min_db,
                 void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Vocos mel vocoder engine: replaces promonet.model.Vocos --------------
+ * (promonet/model/vocos.py, config/baselines/vocos.py MODEL = 'vocos').
+ * conv_pre (k7) + cond, backbone embed (k7) + LayerNorm, `layers` fused
+ * ConvNeXt blocks, final LayerNorm, ISTFTHead (Linear C -> n_fft + 2,
+ * exp-clip magnitude, phase) and the inverse STFT with overlap-add.
+ * channels must be 512, hidden a multiple of 64, n_fft 1024, hop 256,
+ * features a multiple of 16. dtype PM_F32, PM_F16 or PM_BF16 is the MFMA
+ * operand type of the contractions; everything else is fp32.               */
+typedef struct pm_vocos_s* pm_vocos_t;
+int pm_vocos_create(int num_features, int global_channels, int channels,
+                    int hidden, int layers, int n_fft, int hop, int dtype,
+                    pm_vocos_t* out);
+int pm_vocos_destroy(pm_vocos_t h);
+/* Vocos.state_dict() keys, e.g. conv_pre.weight (512, 80, 7),
+ * backbone.convnext.3.pwconv1.weight (1536, 512), head.istft.window (1024) */
+int pm_vocos_load_tensor(pm_vocos_t h, const char* name, const float* dev,
+                         const int64_t* shape, int ndim, void* stream);
+int pm_vocos_finalize(pm_vocos_t h, void* stream);
+size_t pm_vocos_workspace_bytes(pm_vocos_t h, int batch, int frames);
+/* Vocos.forward(x, g) (vocos.py:41-54): features (B, F, T), global
+ * (Bg, G) with Bg 1 or B, or NULL (no cond); audio (B, 256 T).              */
+int pm_vocos_forward(pm_vocos_t h, const float* features,
+                     const float* global_features, int global_batch,
+                     float* audio, int batch, int frames, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* One ConvNeXtBlock (vocos.py:113-146), channels-last: x, y (B, T, 512),
+ * y != x; fp32 weights as in the state dict (dwconv (C, 1, 7), pwconv1
+ * (H, C), pwconv2 (C, H)); workspace: pm_convnext_block_workspace_bytes.   */
+size_t pm_convnext_block_workspace_bytes(int dtype, int channels, int hidden);
+int pm_convnext_block_cl(int dtype, const float* x, float* y,
+                         const float* dw_w, const float* dw_b,
+                         const float* ln_w, const float* ln_b,
+                         const float* w1, const float* b1, const float* w2,
+                         const float* b2, const float* gamma, int batch,
+                         int frames, int channels, int hidden,
+                         void* workspace, size_t workspace_bytes,
+                         void* stream);
+/* ISTFTHead (vocos.py:154-172): x (B, T, 512) channels-last, w (1026, 512),
+ * bias (1026), window (1024) -> audio (B, 256 T).                          */
+size_t pm_vocos_head_workspace_bytes(int dtype, int batch, int frames);
+int pm_vocos_head(int dtype, const float* x, const float* w,
+                  const float* bias, const float* window, float* audio,
+                  int batch, int frames, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* ISTFT (vocos.py:175-206): spectrum (B, 513, T) complex as (re, im) pairs
+ * -> audio (B, 256 T); the imaginary parts of bins 0 and 512 are ignored. */
+size_t pm_istft_workspace_bytes(int batch, int frames);
+int pm_istft(const float* spectrum, const float* window, float* audio,
+             int batch, int frames, void* workspace, size_t workspace_bytes,
+             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ from .config import (                                          # noqa: F401
     GLOBAL_CHANNELS, LOG_DYNAMIC_RANGE_COMPRESSION_THRESHOLD, LOG_FMAX,
     LOG_FMIN, NUM_FEATURES, NUM_PREVIOUS_SAMPLES, NUM_SPEAKERS)
 from . import _lib                                             # noqa: F401
+from . import baseline                                         # noqa: F401
 from . import convert                                          # noqa: F401
 from . import edit                                             # noqa: F401
 from . import load                                             # noqa: F401

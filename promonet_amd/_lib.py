@@ -108,6 +108,18 @@ SIGNATURES = {
     'pm_linear_to_mel_backward': (_I, [_P] * 5 + [_I] * 5 + [_F, _P]),
     'pm_loudness_scratch_bytes': (_S, [_I, _I]),
     'pm_loudness': (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _S, _P]),
+    'pm_vocos_create': (_I, [_I] * 8 + [ctypes.POINTER(_P)]),
+    'pm_vocos_destroy': (_I, [_P]),
+    'pm_vocos_load_tensor': (_I, [_P, ctypes.c_char_p, _P, c_int64_p, _I, _P]),
+    'pm_vocos_finalize': (_I, [_P, _P]),
+    'pm_vocos_workspace_bytes': (_S, [_P, _I, _I]),
+    'pm_vocos_forward': (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _S, _P]),
+    'pm_convnext_block_workspace_bytes': (_S, [_I, _I, _I]),
+    'pm_convnext_block_cl': (_I, [_I] + [_P] * 11 + [_I] * 4 + [_P, _S, _P]),
+    'pm_vocos_head_workspace_bytes': (_S, [_I, _I, _I]),
+    'pm_vocos_head': (_I, [_I] + [_P] * 5 + [_I, _I, _P, _S, _P]),
+    'pm_istft_workspace_bytes': (_S, [_I, _I]),
+    'pm_istft': (_I, [_P, _P, _P, _I, _I, _P, _S, _P]),
 }
 
 _lib = None

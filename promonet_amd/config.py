@@ -33,6 +33,7 @@ PPG_CHANNELS = 40
 PPG_INTERP_METHOD = 'linear'
 SPARSE_PPG_METHOD = 'percentile'
 SPARSE_PPG_THRESHOLD = 0.85
+SPARSE_MELS = False
 SPECTROGRAM_ONLY = False
 TRAINING_DATASET = 'vctk'
 VARIABLE_PITCH_BINS = True
@@ -61,6 +62,9 @@ HIFIGAN_UPSAMPLE_INITIAL_SIZE = 512
 HIFIGAN_UPSAMPLE_KERNEL_SIZES = [16, 16, 4, 4]
 HIFIGAN_UPSAMPLE_RATES = [8, 8, 2, 2]
 SPEAKER_CHANNELS = 256
+VOCOS_CHANNELS = 512
+VOCOS_LAYERS = 6
+VOCOS_POINTWISE_CHANNELS = 1536
 WAVLM_EMBEDDING_CHANNELS = 512
 ZERO_SHOT = False
 STEPS = 800000
@@ -100,6 +104,15 @@ FARGAN_SUBFRAMES = 4
 #                     (1.2e-4 at peak 0.5, at bf16's speed)
 # One f16 rounding of the last stage's activations alone is 3e-4 of an output
 # that peaks near 1, so no single-MFMA 16-bit mode holds 1e-4 there.
+# Vocos (MODEL = 'vocos', promonet_amd.model.MelGenerator) honours 'fp32',
+# 'f16' and 'bf16'; 'checkpoint' resolves to 'fp32' there (model/vocos.py
+# VOCOS_DTYPES). Max-abs against the fp32 reference over 4 utterances of the
+# batch-32 x 10 s workload at random-init scale (peak 0.118) | output peak
+# 0.99, and the batch-32 x 10 s step:
+#   'fp32'  2.3e-7 | 1.9e-6   14.6 ms  (= 'checkpoint')
+#   'f16'   7.2e-5 | 6.0e-4    4.2 ms
+#   'bf16'  6.2e-4 | 5.2e-3    4.2 ms
+# HiFi-GAN-only strings ('f16a2', per-stage '+' schedules, ...) raise.
 DEFAULT_COMPUTE_DTYPE = 'checkpoint'
 COMPUTE_DTYPE = DEFAULT_COMPUTE_DTYPE
 

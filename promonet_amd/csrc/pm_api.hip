@@ -36,6 +36,11 @@ static int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// for the other translation units (pm_vocos.hip)
+int pm_fail_message(int code, const char* message) {
+    return fail(code, "%s", message);
+}
+
 #define HIP_TRY(expr)                                                        \
     do {                                                                     \
         hipError_t e_ = (expr);                                              \

@@ -1,4 +1,5 @@
 from .core import get_padding
 from .fargan import FARGAN
-from .generator import Generator
+from .generator import Generator, MelGenerator
 from .hifigan import HiFiGAN
+from .vocos import Vocos

@@ -12,6 +12,7 @@ import promonet_amd
 from promonet_amd import _lib
 from .fargan import FARGAN
 from .hifigan import HiFiGAN
+from .vocos import Vocos
 
 
 class Generator(torch.nn.Module):
@@ -26,6 +27,10 @@ class Generator(torch.nn.Module):
         elif promonet_amd.MODEL == 'hifigan':
             self.model = HiFiGAN(
                 promonet_amd.NUM_FEATURES, promonet_amd.GLOBAL_CHANNELS)
+        elif promonet_amd.MODEL == 'vocos':
+            raise ValueError(
+                "MODEL 'vocos' is a mel vocoder: use "
+                'promonet_amd.model.MelGenerator (config/baselines/vocos.py)')
         else:
             raise ValueError(
                 f'Generator model {promonet_amd.MODEL} is not defined')
@@ -327,3 +332,64 @@ class Generator(torch.nn.Module):
 
     def remove_weight_norm(self):
         self.model.remove_weight_norm()
+
+
+class MelGenerator(torch.nn.Module):
+    """Drop-in for `promonet.model.MelGenerator` (generator.py:430-463):
+    mel spectrogram -> Vocos -> audio. State dict as the reference's:
+    `speaker_embedding.*`, `default_previous_samples` and `model.*`."""
+
+    def __init__(self):
+        super().__init__()
+        if promonet_amd.MODEL != 'vocos':
+            raise ValueError(
+                f'MelGenerator runs the Vocos vocoder (MODEL {promonet_amd.MODEL!r})')
+        self.model = Vocos(
+            promonet_amd.NUM_FEATURES, promonet_amd.GLOBAL_CHANNELS)
+        self.zero_shot = bool(promonet_amd.ZERO_SHOT)
+        self.augment_pitch = bool(promonet_amd.AUGMENT_PITCH)
+        self.augment_loudness = bool(promonet_amd.AUGMENT_LOUDNESS)
+        self.sparse_mels = bool(promonet_amd.SPARSE_MELS)
+        if self.zero_shot:
+            self.speaker_embedding = torch.nn.Linear(
+                promonet_amd.WAVLM_EMBEDDING_CHANNELS,
+                promonet_amd.SPEAKER_CHANNELS)
+        else:
+            self.speaker_embedding = torch.nn.Embedding(
+                promonet_amd.NUM_SPEAKERS, promonet_amd.SPEAKER_CHANNELS)
+        for parameter in self.parameters():
+            parameter.requires_grad_(False)
+        self.register_buffer(
+            'default_previous_samples',
+            torch.zeros(1, 1, promonet_amd.NUM_PREVIOUS_SAMPLES))
+
+    def forward(
+        self,
+        spectrograms,
+        speakers,
+        spectral_balance_ratios,
+        loudness_ratios,
+        previous_samples=None
+    ):
+        """(B, 513, T) linear spectrograms -> (B, 1, 256 T). Vocos ignores
+        `previous_samples`; it is optional here because the reference's own
+        caller (baseline/mels.py:97-102) omits it."""
+        features = self.prepare_features(spectrograms)
+        global_features = self.prepare_global_features(
+            speakers, spectral_balance_ratios, loudness_ratios)
+        return self.model(features, global_features)
+
+    def prepare_features(self, spectrograms):
+        """linear_to_mel (+ the clipping threshold with SPARSE_MELS)."""
+        features = promonet_amd.preprocess.spectrogram.linear_to_mel(
+            spectrograms)
+        if self.sparse_mels:
+            features = features + \
+                promonet_amd.LOG_DYNAMIC_RANGE_COMPRESSION_THRESHOLD
+        return features
+
+    # generator.py:49-70, shared with Generator
+    prepare_global_features = Generator.prepare_global_features
+
+    def remove_weight_norm(self):
+        pass

@@ -1,0 +1,209 @@
+"""Vocos vocoder running on the MI355X HIP engine.
+
+Drop-in for `promonet.model.Vocos` (promonet/model/vocos.py:12-54, selected
+by config/baselines/vocos.py): same constructor arguments, same
+`forward(x, g=None)`, the same `state_dict()` keys, shapes and default
+initialisation, so a reference checkpoint loads unchanged. The forward pass
+is one engine call (`pm_vocos_forward`): input convs, the fused ConvNeXt
+blocks, the spectral head and the inverse STFT; there is no PyTorch compute
+path.
+"""
+import ctypes
+
+import torch
+
+import promonet_amd
+from promonet_amd import _lib
+
+# COMPUTE_DTYPE values Vocos honours; 'checkpoint' is the mode that holds 1e-4
+# at a trained checkpoint's output scale (config.py)
+VOCOS_DTYPES = {'checkpoint': 'fp32', 'fp32': 'fp32', 'f32': 'fp32',
+                'f16': 'f16', 'fp16': 'f16', 'bf16': 'bf16'}
+
+
+def resolve_dtype(name):
+    if name not in VOCOS_DTYPES:
+        raise ValueError(
+            f'COMPUTE_DTYPE {name!r} is not a Vocos mode: one of '
+            f'{sorted(VOCOS_DTYPES)}')
+    return VOCOS_DTYPES[name]
+
+
+class ConvNeXtBlock(torch.nn.Module):
+    """Parameters of vocos.py:113-133 (forward is fused into the engine)."""
+
+    def __init__(self, dim, layer_scale_init_value):
+        super().__init__()
+        self.dwconv = torch.nn.Conv1d(dim, dim, 7, padding=3, groups=dim)
+        self.norm = torch.nn.LayerNorm(dim, eps=1e-6)
+        self.pwconv1 = torch.nn.Linear(
+            dim, promonet_amd.VOCOS_POINTWISE_CHANNELS)
+        self.act = torch.nn.GELU()
+        self.pwconv2 = torch.nn.Linear(
+            promonet_amd.VOCOS_POINTWISE_CHANNELS, dim)
+        self.gamma = torch.nn.Parameter(
+            layer_scale_init_value * torch.ones(dim))
+
+
+class VocosBackbone(torch.nn.Module):
+    """Parameters of vocos.py:62-98, with its truncated-normal init."""
+
+    def __init__(self, input_channels, dim, num_layers):
+        super().__init__()
+        self.input_channels = input_channels
+        self.embed = torch.nn.Conv1d(input_channels, dim, 7, padding=3)
+        self.norm = torch.nn.LayerNorm(dim, eps=1e-6)
+        self.convnext = torch.nn.ModuleList([
+            ConvNeXtBlock(dim, 1 / num_layers) for _ in range(num_layers)])
+        self.final_layer_norm = torch.nn.LayerNorm(dim, eps=1e-6)
+        self.apply(self._init_weights)
+
+    def _init_weights(self, m):
+        if isinstance(m, (torch.nn.Conv1d, torch.nn.Linear)):
+            torch.nn.init.trunc_normal_(m.weight, std=0.02)
+            torch.nn.init.constant_(m.bias, 0)
+
+
+class ISTFT(torch.nn.Module):
+    """vocos.py:175-183: only the periodic Hann `window` buffer."""
+
+    def __init__(self, n_fft, hop_length, win_length):
+        super().__init__()
+        self.n_fft = n_fft
+        self.hop_length = hop_length
+        self.win_length = win_length
+        self.register_buffer('window', torch.hann_window(win_length))
+
+
+class ISTFTHead(torch.nn.Module):
+    """vocos.py:154-161"""
+
+    def __init__(self, dim, n_fft, hop_length):
+        super().__init__()
+        self.out = torch.nn.Linear(dim, n_fft + 2)
+        self.istft = ISTFT(n_fft, hop_length, n_fft)
+
+
+class Vocos(torch.nn.Module):
+
+    def __init__(self, initial_channel, gin_channels):
+        super().__init__()
+        self.initial_channel = initial_channel
+        self.gin_channels = gin_channels
+        self.compute_dtype = promonet_amd.COMPUTE_DTYPE
+        self.conv_pre = torch.nn.Conv1d(
+            initial_channel, promonet_amd.VOCOS_CHANNELS, 7, 1, padding='same')
+        self.backbone = VocosBackbone(
+            promonet_amd.VOCOS_CHANNELS, promonet_amd.VOCOS_CHANNELS,
+            promonet_amd.VOCOS_LAYERS)
+        self.head = ISTFTHead(
+            promonet_amd.VOCOS_CHANNELS, promonet_amd.NUM_FFT,
+            promonet_amd.HOPSIZE)
+        self.cond = torch.nn.Conv1d(
+            gin_channels, promonet_amd.VOCOS_CHANNELS, 1)
+        for parameter in self.parameters():
+            parameter.requires_grad_(False)
+        self._engine = None
+        self._engine_key = None
+        self._workspace = None
+        self.register_load_state_dict_post_hook(
+            lambda module, keys: module._destroy())
+
+    ###########################################################################
+    # Engine lifetime
+    ###########################################################################
+
+    def _destroy(self):
+        if getattr(self, '_engine', None) is not None:
+            _lib.lib().pm_vocos_destroy(self._engine)
+        self._engine = None
+        self._engine_key = None
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:
+            pass
+
+    def _apply(self, fn, *args, **kwargs):
+        result = super()._apply(fn, *args, **kwargs)
+        self._destroy()
+        return result
+
+    def engine(self):
+        first = next(self.parameters())
+        if not first.is_cuda:
+            raise RuntimeError(
+                'promonet_amd.model.Vocos runs on an AMD GPU only; move the '
+                'model with .to("cuda:N") (no CPU fallback)')
+        dtype = resolve_dtype(self.compute_dtype)
+        key = (first.device, dtype)
+        if self._engine is not None and self._engine_key == key:
+            return self._engine
+        self._destroy()
+        lib = _lib.lib()
+        handle = ctypes.c_void_p()
+        with torch.cuda.device(first.device):
+            _lib.check(lib.pm_vocos_create(
+                self.initial_channel, self.gin_channels,
+                promonet_amd.VOCOS_CHANNELS,
+                self.backbone.convnext[0].pwconv1.out_features
+                if len(self.backbone.convnext) else
+                promonet_amd.VOCOS_POINTWISE_CHANNELS,
+                len(self.backbone.convnext), self.head.istft.n_fft,
+                self.head.istft.hop_length, _lib.DTYPES[dtype],
+                ctypes.byref(handle)))
+            try:
+                for name, tensor in self.state_dict().items():
+                    tensor = tensor.detach().to(torch.float32).contiguous()
+                    _lib.check(lib.pm_vocos_load_tensor(
+                        handle, name.encode(), _lib.ptr(tensor),
+                        _lib.shape_array(tensor.shape), tensor.ndim,
+                        _lib.stream()))
+                _lib.check(lib.pm_vocos_finalize(handle, _lib.stream()))
+            except Exception:
+                lib.pm_vocos_destroy(handle)
+                raise
+        self._engine = handle
+        self._engine_key = key
+        return handle
+
+    ###########################################################################
+    # Forward (vocos.py:41-54)
+    ###########################################################################
+
+    def forward(self, x, g=None):
+        """x (B, F, T) features, g (B|1, G, 1) global features or None ->
+        audio (B, 1, 256 T)."""
+        _lib.require_gpu(x)
+        engine = self.engine()
+        lib = _lib.lib()
+        x = x.to(torch.float32).contiguous()
+        batch, channels, frames = x.shape
+        if channels != self.initial_channel:
+            raise ValueError(
+                f'expected {self.initial_channel} feature channels, got '
+                f'{channels}')
+        pointer, gbatch = None, 1
+        if g is not None:
+            g = g.reshape(g.shape[0], -1).to(
+                device=x.device, dtype=torch.float32).contiguous()
+            if g.shape[1] != self.gin_channels or \
+                    g.shape[0] not in (1, batch):
+                raise ValueError(
+                    f'global features must be (B|1, {self.gin_channels}[, 1])')
+            pointer, gbatch = _lib.ptr(g), g.shape[0]
+        out = torch.empty(
+            batch, 1, frames * self.head.istft.hop_length,
+            dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            size = lib.pm_vocos_workspace_bytes(engine, batch, frames)
+            if self._workspace is None or self._workspace.numel() < size or \
+                    self._workspace.device != x.device:
+                self._workspace = torch.empty(
+                    size, dtype=torch.uint8, device=x.device)
+            _lib.check(lib.pm_vocos_forward(
+                engine, _lib.ptr(x), pointer, gbatch, _lib.ptr(out), batch,
+                frames, self._workspace.data_ptr(), self._workspace.numel(),
+                _lib.stream()))
+        return out

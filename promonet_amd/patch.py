@@ -3,7 +3,9 @@ reference package, the literal drop-in.
 
 After patching, `promonet.synthesize.from_features(..., gpu=N)`,
 `promonet.model.Generator()` and `promonet.preprocess.spectrogram.from_audio`
-/ `promonet.preprocess.loudness.from_audio` run on libpromonet_hip.so.
+/ `promonet.preprocess.loudness.from_audio` run on libpromonet_hip.so, and,
+where the target has them, `promonet.model.Vocos` / `MelGenerator` and
+`promonet.baseline.mels.*`.
 """
 import promonet_amd
 
@@ -35,4 +37,16 @@ def patch(promonet):
         promonet_amd.preprocess.spectrogram.linear_to_mel
     promonet.preprocess.loudness.from_audio = \
         promonet_amd.preprocess.loudness.from_audio
+    # the mel vocoder, only where the target has it
+    for name in ('Vocos', 'MelGenerator'):
+        if hasattr(promonet.model, name):
+            setattr(promonet.model, name, getattr(promonet_amd.model, name))
+    mels = getattr(getattr(promonet, 'baseline', None), 'mels', None)
+    if mels is not None:
+        for name in (
+            'from_audio', 'from_features', 'from_file', 'from_file_to_file',
+            'from_files_to_files', 'resample'
+        ):
+            if hasattr(mels, name):
+                setattr(mels, name, getattr(promonet_amd.baseline.mels, name))
     return promonet

@@ -1,0 +1,106 @@
+"""Benchmark the Vocos mel vocoder (MelGenerator at config/baselines/vocos.py)
+on batch 32 x 861 frames (10 s utterances) for each operand type and print one
+JSON line: ms per batch (HIP events, after warmup), M samples/s, TFLOP/s
+against the 0.841 TFLOP of the batch, the fraction of the matching dense MFMA
+peak, and - with --profile - per-kernel times of a `rocprofv3 --kernel-trace
+--stats` run of this script in a child process.
+
+    python scripts/bench_vocos.py [--steps 20] [--warmup 5] [--profile]
+"""
+import argparse
+import csv
+import json
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+BATCH, FRAMES = 32, 861
+FLOP = 0.841e12                      # 30.5 MFLOP a frame x 32 x 861
+PEAK = {'fp32': 157e12, 'f16': 2.5e15, 'bf16': 2.5e15}
+DTYPES = ('fp32', 'f16', 'bf16')
+
+
+def measure(dtype, steps, warmup):
+    import torch
+    import promonet_amd
+    promonet_amd.configure(
+        MODEL='vocos', SPECTROGRAM_ONLY=True, AUGMENT_PITCH=False,
+        AUGMENT_LOUDNESS=False, VOCOS_LAYERS=8, COMPUTE_DTYPE=dtype)
+    torch.manual_seed(0)
+    device = torch.device('cuda:0')
+    model = promonet_amd.model.MelGenerator().to(device).eval()
+    spectrograms = torch.rand(BATCH, 513, FRAMES, device=device) + 1e-3
+    speakers = torch.arange(BATCH, device=device) % promonet_amd.NUM_SPEAKERS
+    ones = torch.ones(BATCH, device=device)
+    with torch.inference_mode():
+        for _ in range(warmup):
+            model(spectrograms, speakers, ones, ones)
+        torch.cuda.synchronize()
+        start = torch.cuda.Event(enable_timing=True)
+        end = torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(steps):
+            model(spectrograms, speakers, ones, ones)
+        end.record()
+        torch.cuda.synchronize()
+    ms = start.elapsed_time(end) / steps
+    return {'ms_per_batch': round(ms, 4),
+            'msamples_per_s': round(BATCH * FRAMES * 256 / ms / 1e3, 2),
+            'tflops': round(FLOP / ms / 1e9, 2),
+            'fraction_of_mfma_peak': round(FLOP / (ms * 1e-3) / PEAK[dtype],
+                                           4)}
+
+
+def profile(steps, warmup):
+    """per-kernel totals (ms a batch) of one rocprofv3 kernel-trace run"""
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        done = subprocess.run(
+            ['rocprofv3', '--kernel-trace', '--stats', '--output-format',
+             'csv', '-d', tmp, '-o', 'vocos', '--', sys.executable,
+             __file__, '--inner', '--steps', str(steps), '--warmup',
+             str(warmup)],
+            capture_output=True, text=True, timeout=900)
+        if done.returncode != 0:
+            return {'error': done.stderr[-500:]}
+        files = list(Path(tmp).rglob('*kernel_stats.csv'))
+        if not files:
+            return {'error': 'no kernel_stats.csv'}
+        # every dtype runs warmup + steps forwards: a kernel templated on the
+        # operand type (Elem*) serves one dtype, the others all three
+        with open(files[0]) as f:
+            for row in csv.DictReader(f):
+                name = row['Name'].split('(')[0]
+                calls = (steps + warmup) * (1 if 'Elem' in name else
+                                            len(DTYPES))
+                out[name[:80]] = round(
+                    float(row['TotalDurationNs']) / 1e6 / calls, 4)
+    return dict(sorted(out.items(), key=lambda kv: -kv[1])[:24])
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--steps', type=int, default=20)
+    parser.add_argument('--warmup', type=int, default=5)
+    parser.add_argument('--profile', action='store_true')
+    parser.add_argument('--dtypes', default=','.join(DTYPES),
+                        help='comma-separated subset of fp32,f16,bf16')
+    parser.add_argument('--inner', action='store_true',
+                        help=argparse.SUPPRESS)
+    args = parser.parse_args()
+    result = {'metric': 'vocos_mel_vocoder', 'batch': BATCH,
+              'frames': FRAMES, 'tflop_per_batch': FLOP / 1e12}
+    for dtype in args.dtypes.split(','):
+        result[dtype] = measure(dtype, args.steps, args.warmup)
+    if args.profile and not args.inner:
+        result['kernels_ms_per_batch'] = profile(
+            args.steps, args.warmup)
+    print(json.dumps(result))
+
+
+if __name__ == '__main__':
+    main()
