@@ -376,6 +376,29 @@ int pm_fargan_forward_ragged(pm_fargan_t h, const float* features,
                              const int* lengths, float* out, int batch,
                              int frames, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* Streaming: the reference's FARGAN.step loop (fargan.py:65-131) over
+ * `frames` >= 1 frames, starting from the given recurrent state. states
+ * (B, PM_FARGAN_STATE_FLOATS) fp32 rows = the reference's `states` tuple
+ * concatenated: [gru1 h 256 | gru2 h 256 | gru3 h 256 | sub-frame input 260]
+ * (fargan.py:406-415), or NULL = zeros; previous (Bp, 512) in time order or
+ * NULL = zeros. Writes the audio (B, 1, 256 T) and the state after the last
+ * frame: previous_out (B, 512), states_out (B, PM_FARGAN_STATE_FLOATS).
+ * Consecutive calls carrying that state equal one pm_fargan_forward over the
+ * concatenated frames bit for bit. Workspace, kernel selection and
+ * pm_fargan_check as for pm_fargan_forward. PM_EINVAL when an output overlaps
+ * an input, the workspace or another output. There is no ragged form: the
+ * lockstep replay of a ragged batch would advance a short utterance's state
+ * past its end.                                                             */
+#define PM_FARGAN_STATE_FLOATS 1028
+int pm_fargan_forward_stateful(pm_fargan_t h, const float* features,
+                               int features_channels_last,
+                               const float* global_features, int global_batch,
+                               const float* previous_samples,
+                               int previous_batch, const float* states,
+                               float* out, float* previous_out,
+                               float* states_out, int batch, int frames,
+                               void* workspace, size_t workspace_bytes,
+                               void* stream);
 
 /* Kernel selection: 0 auto (clusters of 8 workgroups per utterance up to 160
  * utterances per launch, else one persistent workgroup per utterance),

@@ -2169,9 +2169,12 @@ extern "C" size_t pm_fargan_workspace_bytes(pm_fargan_t h, int B, int T) {
            fargan_state_bytes() + fargan_precond_bytes(h, B, T);
 }
 
+// st.states_out != null: the stateful instantiations (pm_fargan_forward_stateful)
 template <class WT>
 static int fargan_launch(
-    pm_fargan_t h, const FarganArgs& a, hipStream_t s, void* cluster_state) {
+    pm_fargan_t h, const FarganArgs& a, hipStream_t s, void* cluster_state,
+    const FarganState& st) {
+    const bool stateful = st.states_out != nullptr;
     FarganWeights<WT> w;
     w.base = (const typename FarganWeights<WT>::S*)h->weights;
     w.base_i = (const typename FarganWeights<WT>::I*)(
@@ -2223,21 +2226,35 @@ static int fargan_launch(
         // (+ the LDS-resident short slices of a one-utterance cluster)
         const size_t smem = (size_t)U * sizeof(FgLds) +
                             (U == 1 ? FgResident<WT, 1>::BYTES : 0);
-        auto launch = [&](auto kern) -> hipError_t {
+        auto launch = [&](auto kern, const auto& args) -> hipError_t {
             hipError_t e = pm_ensure_dynamic_lds(
                 reinterpret_cast<const void*>(kern), (int)smem);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid, block, smem, s, ca, w);
+            hipLaunchKernelGGL(kern, grid, block, smem, s, args, w);
             return hipGetLastError();
         };
-        hipError_t e = U == 1 ? launch(pm_fargan_cluster_kernel<WT, 1>)
-                     : U == 2 ? launch(pm_fargan_cluster_kernel<WT, 2>)
-                              : launch(pm_fargan_cluster_kernel<WT, FG_UMAX>);
-        HIP_TRY(e);
+        auto pick = [&](const auto& args) -> hipError_t {
+            typedef std::decay_t<decltype(args)> CA;
+            return U == 1 ? launch(pm_fargan_cluster_kernel<WT, 1, CA>, args)
+                 : U == 2 ? launch(pm_fargan_cluster_kernel<WT, 2, CA>, args)
+                          : launch(pm_fargan_cluster_kernel<WT, FG_UMAX, CA>, args);
+        };
+        FgStateful<FarganClusterArgs> sca;
+        static_cast<FarganClusterArgs&>(sca) = ca;
+        static_cast<FarganState&>(sca) = st;
+        HIP_TRY(stateful ? pick(sca) : pick(ca));
         return PM_OK;
     }
-    hipLaunchKernelGGL(pm_fargan_kernel<WT>, dim3(a.B), dim3(FG_THREADS), 0, s,
-                       a, w);
+    if (stateful) {
+        FgStateful<FarganArgs> sa;
+        static_cast<FarganArgs&>(sa) = a;
+        static_cast<FarganState&>(sa) = st;
+        auto kern = pm_fargan_kernel<WT, FgStateful<FarganArgs>>;
+        hipLaunchKernelGGL(kern, dim3(a.B), dim3(FG_THREADS), 0, s, sa, w);
+    } else {
+        hipLaunchKernelGGL(pm_fargan_kernel<WT>, dim3(a.B), dim3(FG_THREADS), 0, s,
+                           a, w);
+    }
     HIP_TRY(hipGetLastError());
     return PM_OK;
 }
@@ -2264,7 +2281,8 @@ extern "C" int pm_fargan_check(
 static int fargan_forward_impl(
     pm_fargan_t h, const float* features, int features_cl, const float* g,
     int gbatch, const float* previous, int pbatch, const int* lengths,
-    float* out, int B, int T, void* ws, size_t ws_bytes, void* stream) {
+    float* out, int B, int T, void* ws, size_t ws_bytes, void* stream,
+    const FarganState& st = FarganState()) {
     if (!h || !features || !g || !out) return fail(PM_EINVAL, "null argument");
     if (!h->finalized) return fail(PM_ESTATE, "pm_fargan_finalize not called");
     if (B < 1 || T < 1) return fail(PM_EINVAL, "empty batch or sequence");
@@ -2290,9 +2308,9 @@ static int fargan_forward_impl(
     a.B = B; a.T = T; a.cstride = cpad; a.nfeat = h->nfeat; a.G = h->G;
     a.global_batch = gbatch; a.previous_batch = pbatch;
     a.lengths = lengths;
-    return h->dtype == PM_F32 ? fargan_launch<float>(h, a, s, cluster_state)
-         : h->dtype == PM_F16 ? fargan_launch<_Float16>(h, a, s, cluster_state)
-                              : fargan_launch<FgMixed>(h, a, s, cluster_state);
+    return h->dtype == PM_F32 ? fargan_launch<float>(h, a, s, cluster_state, st)
+         : h->dtype == PM_F16 ? fargan_launch<_Float16>(h, a, s, cluster_state, st)
+                              : fargan_launch<FgMixed>(h, a, s, cluster_state, st);
 }
 
 extern "C" int pm_fargan_forward(
@@ -2313,4 +2331,54 @@ extern "C" int pm_fargan_forward_ragged(
     if (!lengths) return fail(PM_EINVAL, "null lengths");
     return fargan_forward_impl(h, features, features_cl, g, gbatch, previous,
                                pbatch, lengths, out, B, T, ws, ws_bytes, stream);
+}
+
+static_assert(FG_STATE == PM_FARGAN_STATE_FLOATS, "FARGAN state row");
+
+static bool fargan_overlap(const void* a, size_t an, const void* b, size_t bn) {
+    const char* p = (const char*)a;
+    const char* q = (const char*)b;
+    return p && q && an && bn && p < q + bn && q < p + an;
+}
+
+// FARGAN.step (model/fargan.py:65-131) for `frames` consecutive frames, from
+// the recurrent state `states` / `previous` (NULL: zeros) to the state after
+// the last frame. The kernels are the forward's with a state prologue and
+// epilogue, so consecutive calls carrying the state equal one forward over
+// the concatenated frames, bit for bit. The outputs may not overlap an input
+// (nor the workspace, nor each other): a relaunch after a timed-out cluster
+// exchange reads the inputs again.
+extern "C" int pm_fargan_forward_stateful(
+    pm_fargan_t h, const float* features, int features_cl, const float* g,
+    int gbatch, const float* previous, int pbatch, const float* states,
+    float* out, float* previous_out, float* states_out, int B, int T,
+    void* ws, size_t ws_bytes, void* stream) {
+    if (!h || !features || !g || !out || !previous_out || !states_out)
+        return fail(PM_EINVAL, "null argument");
+    if (B < 1 || T < 1) return fail(PM_EINVAL, "empty batch or sequence");
+    if ((gbatch != 1 && gbatch != B) || (previous && pbatch != 1 && pbatch != B))
+        return fail(PM_EINVAL, "broadcast batch must be 1 or batch");
+    const size_t F = sizeof(float);
+    const int channels = features_cl ? pad32(h->nfeat + 1) : h->nfeat + 1;
+    struct Span { const void* p; size_t n; };
+    const Span in[] = {
+        {features, (size_t)B * T * channels * F}, {g, (size_t)gbatch * h->G * F},
+        {previous, (size_t)pbatch * FG_PREV * F}, {states, (size_t)B * FG_STATE * F},
+        {ws, ws_bytes}};
+    const Span outs[] = {
+        {out, (size_t)B * T * FG_HOP * F}, {previous_out, (size_t)B * FG_PREV * F},
+        {states_out, (size_t)B * FG_STATE * F}};
+    for (int o = 0; o < 3; ++o) {
+        for (const Span& i : in)
+            if (fargan_overlap(outs[o].p, outs[o].n, i.p, i.n))
+                return fail(PM_EINVAL, "an output overlaps an input or the workspace");
+        for (int q = o + 1; q < 3; ++q)
+            if (fargan_overlap(outs[o].p, outs[o].n, outs[q].p, outs[q].n))
+                return fail(PM_EINVAL, "outputs overlap");
+    }
+    FarganState st;
+    st.states = states; st.states_out = states_out; st.previous_out = previous_out;
+    return fargan_forward_impl(h, features, features_cl, g, gbatch, previous,
+                               pbatch, nullptr, out, B, T, ws, ws_bytes, stream,
+                               st);
 }

@@ -216,6 +216,24 @@ struct FarganArgs {
                                 // simply stops early; its tail is zero-filled
 };
 
+// Recurrent state of a stateful launch (pm_fargan_forward_stateful): one row of
+// FG_STATE floats per utterance, the reference's `states` tuple concatenated
+// (fargan.py:406-415): [gru1 h 256 | gru2 h 256 | gru3 h 256 | the last
+// sub-frame's input 260] (= hid[0..2] and subin[FG_SUBIN..] of the kernels).
+// The 512-sample history is a separate (B, 512) row in time order.
+#define FG_STATE (3 * FG_HOP + FG_SUBIN)
+struct FarganState {
+    const float* states;    // (B, FG_STATE) or null (zeros)
+    float* states_out;      // (B, FG_STATE), written after the last frame
+    float* previous_out;    // (B, 512)
+};
+// A stateful launch passes the kernel's own arguments followed by the state
+// (a type of its own: the stateless instantiations keep their exact
+// signature and code).
+template <class A> struct FgStateful : A, FarganState {};
+template <class A>
+constexpr bool fg_stateful = std::is_base_of<FarganState, A>::value;
+
 // The activations sit on the dependency chain of every step (12 of them, one
 // after the other): libm's expf + IEEE division are ~40 dependent instructions
 // a sigmoid, tanhf ~80 - 250-500 cycles each at one wave's issue rate. Here the
@@ -239,9 +257,12 @@ __device__ __forceinline__ float fg_sigmoid(float v) {
 __device__ __forceinline__ float fg_tanh(float v) { return tanhf(v); }
 #endif
 
-template <class WT>
+// A = FgStateful<FarganArgs> (pm_fargan_forward_stateful): start from
+// a.states instead of zeros and store the state after the last frame.
+template <class WT, class A = FarganArgs>
 __global__ __launch_bounds__(FG_THREADS) void pm_fargan_kernel(
-    FarganArgs a, FarganWeights<WT> w) {
+    A a, FarganWeights<WT> w) {
+    constexpr bool STATEFUL = fg_stateful<A>;
     constexpr int NT = FG_THREADS;
     constexpr int CPAD = 376;   // 371 conditioning inputs, padded to x8
     typedef typename FgTypes<WT>::S WS;
@@ -278,6 +299,16 @@ __global__ __launch_bounds__(FG_THREADS) void pm_fargan_kernel(
         prev[i] = a.previous
             ? a.previous[(size_t)(a.previous_batch == 1 ? 0 : b) * FG_PREV + i]
             : 0.f;
+    if constexpr (STATEFUL) {
+        // ... or the state a previous launch ended in (each element rewritten
+        // by the thread that zeroed it)
+        if (a.states) {
+            const float* s0 = a.states + (size_t)b * FG_STATE;
+            for (int i = tid; i < 3 * FG_HOP; i += NT) (&hid[0][0])[i] = s0[i];
+            for (int i = tid; i < 2 * FG_SUBIN; i += NT)
+                if (i >= FG_SUBIN) subin[i] = s0[3 * FG_HOP + i - FG_SUBIN];
+        }
+    }
     int base = 0;   // ring offset of `prev`: logical i -> (base + i) % 512
     __syncthreads();
 
@@ -394,6 +425,17 @@ __global__ __launch_bounds__(FG_THREADS) void pm_fargan_kernel(
             base = (base + FG_SUB) & (FG_PREV - 1);
             __syncthreads();
         }
+    }
+    if constexpr (STATEFUL) {
+        // the state after the last frame (the step ended on a barrier); the
+        // history unrolled from its ring into time order
+        float* so = a.states_out + (size_t)b * FG_STATE;
+        for (int i = tid; i < 3 * FG_HOP; i += NT) so[i] = (&hid[0][0])[i];
+        for (int i = tid; i < FG_SUBIN; i += NT)
+            so[3 * FG_HOP + i] = subin[FG_SUBIN + i];
+        for (int i = tid; i < FG_PREV; i += NT)
+            a.previous_out[(size_t)b * FG_PREV + i] =
+                prev[(base + i) & (FG_PREV - 1)];
     }
 }
 
@@ -1083,9 +1125,12 @@ struct FarganClusterArgs {
 // per layer for all of them and one exchange carries U vectors, so the
 // latency of a layer (an L2-and-beyond round trip) is shared U ways. U = 1 is
 // the batch <= 32 case (one utterance per cluster, 32 clusters = 256 CUs).
-template <class WT, int U>
+// CA = FgStateful<FarganClusterArgs>: as pm_fargan_kernel (the state is
+// replicated in every member)
+template <class WT, int U, class CA = FarganClusterArgs>
 __global__ __launch_bounds__(FG_CT) void pm_fargan_cluster_kernel(
-    FarganClusterArgs ca, FarganWeights<WT> w) {
+    CA ca, FarganWeights<WT> w) {
+    constexpr bool STATEFUL = fg_stateful<CA>;
     const FarganArgs& a = ca.f;
     typedef typename FgTypes<WT>::S WS;
     typedef typename FgTypes<WT>::I WI;
@@ -1158,9 +1203,43 @@ __global__ __launch_bounds__(FG_CT) void pm_fargan_cluster_kernel(
                     ? a.previous[(size_t)(a.previous_batch == 1 ? 0 : ut[u]) *
                                      FG_PREV + i]
                     : 0.f;
+            if constexpr (STATEFUL) {
+                if (ca.states) {   // (as pm_fargan_kernel)
+                    const float* s0 = ca.states + (size_t)ut[u] * FG_STATE;
+                    for (int i = tid; i < 3 * FG_HOP; i += NT)
+                        (&L[u].hid[0][0])[i] = s0[i];
+                    for (int i = tid; i < 2 * FG_SUBIN; i += NT)
+                        if (i >= FG_SUBIN)
+                            L[u].subin[i] = s0[3 * FG_HOP + i - FG_SUBIN];
+                }
+            }
         }
         int base = 0;
         __syncthreads();
+        if constexpr (STATEFUL && FG_UNDER(WT) >= 2) {
+            // At level 2, W_hh[0] h and W_hh[1] h are streamed under E5 / E6
+            // of the step BEFORE the one that reads them: step 0 finds the
+            // zeros above, right for a zero state only. From a loaded state
+            // they are computed here by under_hh's slice - same lane map,
+            // same summation order - so that a run resumed from a state has
+            // the bits of the uninterrupted one. (Levels 0 and 1 compute
+            // every W_hh h inside the step that reads it.)
+            constexpr int GLPR = FG_CT >= 768 ? 8 : 4;
+#pragma unroll 1
+            for (int n = 0; n < 2; ++n) {
+                float ghv[U];
+                const int hoff = FG_OFF(hid) + n * FG_HOP;
+                fg_slice_lanes<WI, 96, 768 * FgVec<WI>::VEC, U, 256, GLPR>(
+                    w.gru_hh(n) + g * 96 * FgVec<WI>::VEC, lds, hoff, hoff,
+                    256, tid, ghv);
+                if (FgLanes<GLPR>::lead(tid, 96)) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        L[u].gh[n][FgLanes<GLPR>::row(tid)] = ghv[u];
+                }
+            }
+            __syncthreads();
+        }
 
 #pragma unroll 1
         for (int t = 0; t < frames; ++t) {
@@ -1542,6 +1621,25 @@ __global__ __launch_bounds__(FG_CT) void pm_fargan_cluster_kernel(
                 __syncthreads();
                 FG_STAMP(22);
             }
+        }
+        if constexpr (STATEFUL) {
+            // every member holds the same state: member 0 stores it; slots
+            // past the batch store nothing
+            if (g == 0) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (!live[u]) continue;
+                    float* so = ca.states_out + (size_t)ut[u] * FG_STATE;
+                    for (int i = tid; i < 3 * FG_HOP; i += NT)
+                        so[i] = (&L[u].hid[0][0])[i];
+                    for (int i = tid; i < FG_SUBIN; i += NT)
+                        so[3 * FG_HOP + i] = L[u].subin[FG_SUBIN + i];
+                    for (int i = tid; i < FG_PREV; i += NT)
+                        ca.previous_out[(size_t)ut[u] * FG_PREV + i] =
+                            L[u].prev[(base + i) & (FG_PREV - 1)];
+                }
+            }
+            __syncthreads();   // (the next group's prologue rewrites the state)
         }
     }
 }

@@ -2,11 +2,14 @@
 
 Drop-in for `promonet.model.FARGAN` (promonet/model/fargan.py:13-131,
 selected by `config/fargan.py`): same constructor arguments, same
-`forward(features, global_features, previous_samples)`, same `state_dict()`
-keys (weight-normed Linear layers keep `weight_g` / `weight_v`). The whole
-frame-autoregressive loop - 4 sub-frame steps per frame, the pitch lookback
-gather, three GRU cells, GLUs - runs inside one persistent kernel per
-utterance (`pm_fargan_forward`); there is no PyTorch compute path.
+`forward(features, global_features, previous_samples)` and
+`step(features, global_features, previous_samples, states)`, same
+`state_dict()` keys (weight-normed Linear layers keep `weight_g` /
+`weight_v`). The whole frame-autoregressive loop - 4 sub-frame steps per
+frame, the pitch lookback gather, three GRU cells, GLUs - runs inside one
+persistent kernel per utterance (`pm_fargan_forward`, or
+`pm_fargan_forward_stateful` from a carried recurrent state); there is no
+PyTorch compute path.
 """
 import ctypes
 import math
@@ -16,6 +19,18 @@ import torch
 import promonet_amd
 from promonet_amd import _lib
 from .core import attach
+
+# the recurrent state (fargan.py:406-415): three GRU states and the last
+# sub-frame's input [features 128 | previous subframe 64 | lookback 68]
+STATE_SIZES = (256, 256, 256, 260)
+
+
+def initialize_recurrent_state(batch_size, device):
+    """Zero recurrent state with the reference's shapes (fargan.py:406-415):
+    (B, 256) x 3 and (B, 260), fp32."""
+    return tuple(
+        torch.zeros(batch_size, size, dtype=torch.float32, device=device)
+        for size in STATE_SIZES)
 
 
 class FARGAN(torch.nn.Module):
@@ -151,7 +166,52 @@ class FARGAN(torch.nn.Module):
         return self._run(
             features_cl, global_features, previous_samples, True, lengths)
 
-    def _run(self, x, g, previous, channels_last, lengths=None):
+    ###########################################################################
+    # Streaming (fargan.py:65-131)
+    ###########################################################################
+
+    def step(self, features, global_features, previous_samples, states):
+        """Generate one frame from a recurrent state, as the reference's
+        `FARGAN.step`: features (B, 114) with the pitch period last,
+        global_features (B|1, 258[, 1]), previous_samples (B|1, 1, 512),
+        states the 4-tuple of `initialize_recurrent_state` ->
+        (signal (B, 256), previous_samples (B, 1, 512), states)."""
+        if features.ndim != 2:
+            raise ValueError('step: features must be (B, 114)')
+        signal, previous_samples, states = self.stream(
+            features[:, :, None], global_features, previous_samples, states)
+        return signal[:, 0], previous_samples, states
+
+    def stream(
+        self, features, global_features, previous_samples=None, states=None,
+        channels_last=False
+    ):
+        """Synthesise a chunk of frames from a recurrent state and return the
+        state after it: features (B, 114, T) (or channels-last (B, T, 128)),
+        previous_samples (B|1, 1, 512) or None, states a 4-tuple or None
+        (zeros) -> (signal (B, 1, 256 T), previous_samples (B, 1, 512),
+        states). Consecutive chunks carrying the state equal `forward` over
+        the concatenated frames bit for bit."""
+        batch = features.shape[0]
+        if states is not None:
+            states = tuple(states)
+            if len(states) != len(STATE_SIZES) or any(
+                    tuple(t.shape) != (batch, size)
+                    for t, size in zip(states, STATE_SIZES)):
+                raise ValueError(
+                    'states must be (B, 256) x 3 and (B, 260) with the '
+                    "features' batch")
+            for tensor in states:
+                _lib.require_gpu(tensor)
+            states = torch.cat(states, dim=1).to(torch.float32).contiguous()
+        signal, previous, states = self._run(
+            features, global_features, previous_samples, channels_last,
+            states=states, stateful=True)
+        return (signal, previous[:, None],
+                tuple(states.split(STATE_SIZES, dim=1)))
+
+    def _run(self, x, g, previous, channels_last, lengths=None, states=None,
+             stateful=False):
         _lib.require_gpu(x)
         engine = self.engine()
         lib = _lib.lib()
@@ -176,6 +236,13 @@ class FARGAN(torch.nn.Module):
         out = torch.empty(
             batch, 1, frames * self.hopsize, dtype=torch.float32,
             device=x.device)
+        if stateful:
+            if states is not None and states.device != x.device:
+                raise ValueError('states must be on the features\' device')
+            previous_out = torch.empty(
+                batch, 2 * self.hopsize, dtype=torch.float32, device=x.device)
+            states_out = torch.empty(
+                batch, sum(STATE_SIZES), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             size = lib.pm_fargan_workspace_bytes(engine, batch, frames)
             if self._workspace is None or self._workspace.numel() < size or \
@@ -199,7 +266,15 @@ class FARGAN(torch.nn.Module):
 
             def launch(mode):
                 _lib.check(lib.pm_fargan_set_mode(engine, mode))
-                if lengths is None:
+                if stateful:
+                    _lib.check(lib.pm_fargan_forward_stateful(
+                        engine, _lib.ptr(x), int(channels_last), _lib.ptr(g),
+                        g.shape[0], pointer, pbatch, _lib.ptr(states),
+                        _lib.ptr(out), _lib.ptr(previous_out),
+                        _lib.ptr(states_out), batch, frames,
+                        self._workspace.data_ptr(), self._workspace.numel(),
+                        _lib.stream()))
+                elif lengths is None:
                     _lib.check(lib.pm_fargan_forward(
                         engine, _lib.ptr(x), int(channels_last), _lib.ptr(g),
                         g.shape[0], pointer, pbatch, _lib.ptr(out), batch,
@@ -224,7 +299,7 @@ class FARGAN(torch.nn.Module):
                 # tries the clusters again inside the guarded block below)
                 launch(1)
                 self._fallback_calls -= 1
-                return out
+                return (out, previous_out, states_out) if stateful else out
             try:
                 launch(self.kernel_mode)
             except _lib.LibraryError as error:
@@ -250,7 +325,7 @@ class FARGAN(torch.nn.Module):
                         'calls')
                     self._fallback_calls = self.RETRY_AFTER
                     launch(1)
-        return out
+        return (out, previous_out, states_out) if stateful else out
 
     def remove_weight_norm(self):
         """No-op: weight norm is folded once at load."""
