@@ -167,6 +167,146 @@ struct NoHook { __device__ __forceinline__ void operator()() const {} };
 #ifndef PM_BDEPTH
 #define PM_BDEPTH 2     // B fragments in flight: this many k16 steps' worth
 #endif
+// Issue order of the unsplit 16-bit loop (mma_taps_spread below):
+//   0  the grouped loop (all A loads of a group in front of its first step)
+//   1  one step's share of the next A group behind the first MFMA of a step,
+//      the B reads of a step in one burst in front of it
+//   2  as 1, and the B reads one by one between the MFMAs
+#ifndef PM_MMA_ORDER
+#define PM_MMA_ORDER 2
+#endif
+
+// A packed weight stream as a raw buffer: the wave-uniform base in a
+// descriptor, this lane's fragment (lane * 16 bytes) as the only vector
+// offset, every step / M-tile offset scalar. `exists` false gives zero
+// records: every load returns zero without a fetch.
+template <class frag_t>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t a_stream_rsrc(
+    const frag_t* lane_ptr, const unsigned lane_bytes, const bool exists) {
+    const unsigned long long at =
+        reinterpret_cast<unsigned long long>(lane_ptr) - lane_bytes;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)at);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(at >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(
+        reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
+        exists ? 0x7fffffff : 0, 0x00020000);
+}
+
+// mma_taps for the unsplit 16-bit operand types: the same pipeline (A one
+// group ahead, B BD - 1 steps ahead, the same MFMAs in the same order into
+// every accumulator), issued so that no point of a wave's in-order stream
+// holds more non-MFMA issue than one MFMA hides:
+//   * the next group's A fragments are requested one step's share (MTW
+//     loads) at a time, behind the first MFMA of each step, instead of
+//     G * MTW loads in front of the group - a group head the SIMD's other
+//     wave, in step with this one from the same barrier, met at the same time;
+//   * they go through a buffer descriptor (a_stream_rsrc): a fragment is
+//     descriptor + lane offset + immediate, the advance is scalar. The
+//     per-lane 64-bit pointers of the grouped loop cost two
+//     v_add_co / v_addc pairs per group and a v_cndmask select for `wnext`;
+//   * a null `wnext` is a descriptor of zero records: the same loads, no
+//     fetch, no branch in the stream (`first` then returns zeros).
+// `wptr` / `wnext` are this lane's fragment of a stream (stream + lane), as
+// in load_a_group.
+template <class ET, int KT, int KC, int MTW, int NTW, int G, int S, int BD,
+          class Hook>
+__device__ __forceinline__ void mma_taps_spread(
+    floatx16 (&acc)[MTW][NTW], const char* bptr, const int tap_bytes,
+    const typename ET::afrag_t* __restrict__ wptr, const int w_mt_stride,
+    typename ET::afrag_t (&first)[G][MTW],
+    const typename ET::afrag_t* __restrict__ wnext, Hook mid) {
+    typedef typename ET::afrag_t frag_t;
+    typedef typename ET::bfrag_t bfrag_t;
+    static_assert(sizeof(frag_t) == 16, "one b128 load per fragment");
+    constexpr int NS = KT * KC, NG = NS / G;
+    const unsigned lane_bytes = (threadIdx.x & 63) * 16;
+    const bool chained =
+        __builtin_amdgcn_readfirstlane(wnext != nullptr ? 1 : 0) != 0;
+    const __amdgpu_buffer_rsrc_t here = a_stream_rsrc(wptr, lane_bytes, true);
+    const __amdgpu_buffer_rsrc_t next =
+        a_stream_rsrc(chained ? wnext : wptr, lane_bytes, chained);
+    const unsigned mt_bytes = (unsigned)w_mt_stride * 16;
+    frag_t abuf[2][G][MTW];
+    bfrag_t bbuf[BD][NTW];
+    auto load_b = [&](bfrag_t (&dst)[NTW], const int step) {
+        const int j = step / KC, kc = step % KC;
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt)
+            dst[nt] = *reinterpret_cast<const bfrag_t*>(
+                bptr + nt * 32 * S + j * tap_bytes + kc * 16 * ET::ESZ);
+    };
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int mt = 0; mt < MTW; ++mt) abuf[0][g][mt] = first[g][mt];
+#pragma unroll
+    for (int s = 0; s < BD - 1; ++s) load_b(bbuf[s], s);
+#pragma unroll
+    for (int g0 = 0; g0 < NS; g0 += G) {
+        const int cur = (g0 / G) & 1;
+        const bool last = g0 + G >= NS;
+        if (g0 == (NG / 2) * G) mid();
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int step = g0 + g;
+            const int cb = step % BD;
+            const bool more_b = step + BD - 1 < NS;
+            if (more_b) {
+#if defined(PM_TUNING) && defined(PM_ABLATE_B)   // timing experiment only: no LDS operand stream
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt)
+                    bbuf[(step + BD - 1) % BD][nt] = bbuf[cb][nt];
+#else
+                load_b(bbuf[(step + BD - 1) % BD], step + BD - 1);
+#endif
+            }
+            // fragment g of the next group (last group: of the next stream)
+#pragma unroll
+            for (int mt = 0; mt < MTW; ++mt) {
+#if defined(PM_TUNING) && defined(PM_ABLATE_A)   // timing experiment only: no weight stream
+                abuf[cur ^ 1][g][mt] = abuf[cur][g][mt];
+#else
+                const pm_u4 v = __builtin_amdgcn_raw_buffer_load_b128(
+                    last ? next : here, lane_bytes + g * 1024,
+                    mt * mt_bytes + (last ? 0 : (g0 + G) * 1024), 0);
+                abuf[cur ^ 1][g][mt] = __builtin_bit_cast(frag_t, v);
+#endif
+            }
+#pragma unroll
+            for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt)
+                    ET::mma(abuf[cur][g][mt], bbuf[cb][nt], acc[mt][nt]);
+            // The order asked for (masks: 0x008 MFMA, 0x020 VMEM read,
+            // 0x100 DS read). Left alone, the scheduler sinks every load to
+            // just before its MFMA into ONE register set: s_waitcnt vmcnt(0)
+            // (an L2 round trip) per A fragment and ds_read -> lgkmcnt(0) ->
+            // MFMA (an LDS round trip) per MFMA.
+#if PM_MMA_ORDER == 2
+#pragma unroll
+            for (int i = 0; i < MTW * NTW; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                if (i == 0) __builtin_amdgcn_sched_group_barrier(0x020, MTW, 0);
+                if (more_b && i < NTW)
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
+#else
+            if (more_b) __builtin_amdgcn_sched_group_barrier(0x100, NTW, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, MTW, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, MTW * NTW - 1, 0);
+#endif
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    constexpr int LAST = (NG - 1) & 1;
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int mt = 0; mt < MTW; ++mt) first[g][mt] = abuf[LAST ^ 1][g][mt];
+}
+
 template <class ET, int KT, int KC, int MTW, int NTW, int G, int S,
           class Hook = NoHook, int BDO = 0>
 __device__ __forceinline__ void mma_taps(
@@ -185,6 +325,15 @@ __device__ __forceinline__ void mma_taps(
     constexpr int BD = BDO ? BDO : (ET::SPLIT && NTW >= 2 ? 1 : PM_BDEPTH);
     static_assert(NS % G == 0, "group size must divide the step count");
     static_assert(NS >= BD, "fewer steps than B buffers");
+#if PM_MMA_ORDER
+    // (the split types and exact fp32 - two or eight MFMAs and wider
+    // fragments per step - keep the grouped loop below)
+    if constexpr (!ET::SPLIT && ET::ESZ == 2) {
+        mma_taps_spread<ET, KT, KC, MTW, NTW, G, S, BD, Hook>(
+            acc, bptr, tap_bytes, wptr, w_mt_stride, first, wnext, mid);
+        return;
+    }
+#endif
     typedef typename ET::bfrag_t bfrag_t;
     frag_t abuf[2][G][MTW];   // A (weights): one GROUP ahead, from L2
     bfrag_t bbuf[BD][NTW];    // B (activations): BD - 1 STEPS ahead, from LDS

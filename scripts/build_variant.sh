@@ -12,5 +12,7 @@ done
 for f in pm_conv_f16_mrf pm_conv_bf16_mrf; do   # (Makefile: MRF_FLAGS)
   /opt/rocm/bin/hipcc $F ${MRF_FLAGS--mllvm -amdgpu-sched-strategy=max-ilp} -c promonet_amd/csrc/$f.hip -o build/obj_$SUF/$f.o &
 done
+# (Makefile: the spectral head keeps torch.clip's NaN)
+/opt/rocm/bin/hipcc $F -fhonor-nans -c promonet_amd/csrc/pm_vocos.hip -o build/obj_$SUF/pm_vocos.o &
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC build/obj_$SUF/*.o -o promonet_amd/lib/libpromonet_hip_$SUF.so
