@@ -513,6 +513,18 @@ int pm_vocos_forward(pm_vocos_t h, const float* features,
                      const float* global_features, int global_batch,
                      float* audio, int batch, int frames, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* Ragged batch (no reference counterpart: the reference reconstructs one
+ * file per call, promonet/baseline/mels.py:146-166): lengths (B) int32 device
+ * array of valid frames, 1 <= lengths[b] <= frames; frames past an
+ * utterance's end are never read, so each utterance equals its stand-alone
+ * synthesis; audio is (B, 256 frames) and its tail is zero. lengths is read
+ * on the device only: the call stays asynchronous and capturable.          */
+size_t pm_vocos_ragged_workspace_bytes(pm_vocos_t h, int batch, int frames);
+int pm_vocos_forward_ragged(pm_vocos_t h, const float* features,
+                            const float* global_features, int global_batch,
+                            const int* lengths, float* audio, int batch,
+                            int frames, void* workspace,
+                            size_t workspace_bytes, void* stream);
 /* One ConvNeXtBlock (vocos.py:113-146), channels-last: x, y (B, T, 512),
  * y != x; fp32 weights as in the state dict (dwconv (C, 1, 7), pwconv1
  * (H, C), pwconv2 (C, H)); workspace: pm_convnext_block_workspace_bytes.   */

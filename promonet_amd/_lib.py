@@ -115,6 +115,9 @@ SIGNATURES = {
     'pm_vocos_finalize': (_I, [_P, _P]),
     'pm_vocos_workspace_bytes': (_S, [_P, _I, _I]),
     'pm_vocos_forward': (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _S, _P]),
+    'pm_vocos_ragged_workspace_bytes': (_S, [_P, _I, _I]),
+    'pm_vocos_forward_ragged': (
+        _I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _S, _P]),
     'pm_convnext_block_workspace_bytes': (_S, [_I, _I, _I]),
     'pm_convnext_block_cl': (_I, [_I] + [_P] * 11 + [_I] * 4 + [_P, _S, _P]),
     'pm_vocos_head_workspace_bytes': (_S, [_I, _I, _I]),

@@ -19,6 +19,15 @@
 //                     (1024 points as a 512-point complex FFT in LDS)
 // vocos_ola_kernel    overlap-add of the 4 frames covering a sample, crop 384,
 //                     divide by the overlap-added window^2 (vocos.py:175-206)
+//
+// RAGGED (a compile-time switch of every kernel that derives (b, t) from
+// row / T): the rows are PACKED. Utterance b of lengths[b] frames owns rows
+// [off[b], off[b + 1]) of R = off[B] rows; vocos_rowmap_kernel writes off and
+// the per-row lookup VocosRow from the device array lengths. Grids are sized
+// on the host from the bound B T and workgroups past R exit, so nothing reads
+// lengths on the host. A row's arithmetic is that of the uniform kernels, in
+// the same order: a ragged utterance equals its stand-alone synthesis bit
+// for bit.
 #pragma once
 #include "pm_common.h"
 
@@ -31,6 +40,18 @@
 #define PM_VOCOS_HC 64                 // hidden channels per chunk
 #define PM_VOCOS_GEMM_ROWS 64          // vocos_gemm_kernel tile: rows x cols
 #define PM_VOCOS_GEMM_COLS 128
+
+// One packed row of a ragged batch: utterance, frame within it, the
+// utterance's length and its first row. 16 bytes, one load from global / L2.
+struct __attribute__((aligned(16))) VocosRow {
+    int b, t, len, off;
+};
+
+// Packed-row lookup of the RAGGED instantiations (both null when uniform)
+struct VocosRagged {
+    const VocosRow* map;  // (R) valid rows only
+    const int* off;       // (B + 1) first row of every utterance; off[B] = R
+};
 
 // MT rows of the ConvNeXt tile: 128 for the 16-bit types (xn tile 130 KiB),
 // 64 for fp32 (the same bytes)
@@ -103,6 +124,28 @@ __global__ __launch_bounds__(256) void vocos_dw_pack_kernel(
     out[i] = w[(i % C) * 7 + i / C];
 }
 
+// ragged prologue: lengths (B) -> off (B + 1) and the row map. Workgroup
+// (x, b) sums the lengths before b itself (B is small, the loads are scalar)
+// and fills 256 rows of utterance b. A length is clamped to [0, T]: R never
+// exceeds the B T rows the workspace holds, whatever lengths contains.
+__global__ __launch_bounds__(256) void vocos_rowmap_kernel(
+    const int* lengths, int* off, VocosRow* map, int B, int T) {
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    int first = 0;
+    for (int i = 0; i < b; ++i) first += min(max(lengths[i], 0), T);
+    const int len = min(max(lengths[b], 0), T);
+    if (t == 0) {
+        off[b] = first;
+        if (b == B - 1) off[B] = first + len;
+    }
+    if (t < len) {
+        VocosRow r;
+        r.b = b; r.t = t; r.len = len; r.off = first;
+        map[first + t] = r;
+    }
+}
+
 // cond: gb (Bg, N) = W (N, G) g (Bg, G) + b          vocos.py:47-49
 __global__ __launch_bounds__(256) void vocos_cond_kernel(
     const float* g, const float* w, const float* b, float* out, int G, int N) {
@@ -127,21 +170,31 @@ struct VocosGemmArgs {
     int gbatch;
     float* out;           // (B T, ldo)
     int B, T, K, N, ldo;
+    VocosRagged rg;       // RAGGED: x (CF: padded (B, K, T)) and out packed
 };
 
-template <class ET, int TAPS, bool CF>
+template <class ET, int TAPS, bool CF, bool RAGGED>
 __global__ __launch_bounds__(256) void vocos_gemm_kernel(VocosGemmArgs a) {
     typedef typename ET::lds_t et;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ln = lane & 31, lh = lane >> 5;
-    const int rows = a.B * a.T;
+    const int rows = RAGGED ? a.rg.off[a.B] : a.B * a.T;
     const int r0 = blockIdx.x * PM_VOCOS_GEMM_ROWS + (wave >> 1) * 32;
     const int n0 = blockIdx.y * PM_VOCOS_GEMM_COLS + (wave & 1) * 64;
     if (r0 >= rows) return;                 // (no barrier in this kernel)
     const int row = r0 + ln;
     const bool live = row < rows;
-    const int b = live ? row / a.T : 0;
-    const int t = live ? row - b * a.T : 0;
+    int b, t, len, first;                   // first: row of the utterance's t = 0
+    if constexpr (RAGGED) {
+        VocosRow m = {0, 0, 0, 0};
+        if (live) m = a.rg.map[row];
+        b = m.b; t = m.t; len = m.len; first = m.off;
+    } else {
+        b = live ? row / a.T : 0;
+        t = live ? row - b * a.T : 0;
+        len = a.T;
+        first = b * a.T;
+    }
 
     floatx16 acc[2];
 #pragma unroll
@@ -156,10 +209,10 @@ __global__ __launch_bounds__(256) void vocos_gemm_kernel(VocosGemmArgs a) {
 #pragma unroll 1
     for (int tap = 0; tap < TAPS; ++tap) {
         const int ts = t + tap - TAPS / 2;
-        const bool ok = live && ts >= 0 && ts < a.T;
+        const bool ok = live && ts >= 0 && ts < len;
         const float* xr = CF
             ? a.x + (size_t)b * a.K * a.T + (ok ? ts : 0) + (size_t)lh * 8 * a.T
-            : a.x + ((size_t)b * a.T + (ok ? ts : 0)) * a.K + lh * 8;
+            : a.x + ((size_t)first + (ok ? ts : 0)) * a.K + lh * 8;
         const et* wt0 = w0 + (size_t)tap * a.K;
         const et* wt1 = w1 + (size_t)tap * a.K;
 #pragma unroll 1
@@ -192,8 +245,14 @@ __global__ __launch_bounds__(256) void vocos_gemm_kernel(VocosGemmArgs a) {
             const int rr = r0 + vc_acc_row(r, lh);
             if (rr >= rows) continue;
             float v = acc[nt][r] + bias;
-            if (a.gbias)
-                v += a.gbias[(size_t)(a.gbatch == 1 ? 0 : rr / a.T) * a.N + n];
+            if (a.gbias) {
+                int gb = 0;
+                if (a.gbatch != 1) {
+                    if constexpr (RAGGED) gb = a.rg.map[rr].b;
+                    else gb = rr / a.T;
+                }
+                v += a.gbias[(size_t)gb * a.N + n];
+            }
             a.out[(size_t)rr * a.ldo + n] = v;
         }
     }
@@ -226,10 +285,13 @@ __device__ __forceinline__ void vc_layer_norm8(
     for (int e = 0; e < 8; ++e) v[e] = v[e] * rstd * gg[e] + bb[e];
 }
 
+// (rows: the host's bound B T; RAGGED reads the packed row count off[B])
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void vocos_ln_kernel(
-    float* x, const float* g, const float* beta, int rows) {
+    float* x, const float* g, const float* beta, int rows, const int* total) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if constexpr (RAGGED) rows = *total;
     if (row >= rows) return;
     float* p = x + (size_t)row * PM_VOCOS_C + lane * 8;
     const float4 lo = *reinterpret_cast<const float4*>(p);
@@ -257,9 +319,10 @@ struct VocosBlockArgs {
     const float* b2;
     const float* gamma;
     int B, T, H;
+    VocosRagged rg;       // RAGGED: x and y packed
 };
 
-template <class ET>
+template <class ET, bool RAGGED>
 __global__ __launch_bounds__(VocosTile<ET>::THREADS) void vocos_block_kernel(
     VocosBlockArgs a) {
     typedef VocosTile<ET> Tile;
@@ -278,8 +341,10 @@ __global__ __launch_bounds__(VocosTile<ET>::THREADS) void vocos_block_kernel(
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ln = lane & 31, lh = lane >> 5;
-    const int rows = a.B * a.T;
+    const int rows = RAGGED ? a.rg.off[a.B] : a.B * a.T;
     const int m0 = blockIdx.x * MT;
+    if constexpr (RAGGED)
+        if (m0 >= rows) return;           // the whole workgroup, before a barrier
 
     // depthwise k7 conv (zero padding at each utterance's ends) + LayerNorm
     for (int i = wave; i < MT; i += NW) {
@@ -287,7 +352,15 @@ __global__ __launch_bounds__(VocosTile<ET>::THREADS) void vocos_block_kernel(
         char* dst = xs + i * SX + lane * 8 * ESZ;
         float v[8];
         if (row < rows) {
-            const int t = row % a.T;
+            int t, len;                   // (a tile may hold several ends)
+            if constexpr (RAGGED) {
+                const VocosRow m = a.rg.map[row];
+                t = m.t;
+                len = m.len;
+            } else {
+                t = row % a.T;
+                len = a.T;
+            }
             const float4 d0 = *reinterpret_cast<const float4*>(a.dw_b + lane * 8);
             const float4 d1 =
                 *reinterpret_cast<const float4*>(a.dw_b + lane * 8 + 4);
@@ -295,7 +368,7 @@ __global__ __launch_bounds__(VocosTile<ET>::THREADS) void vocos_block_kernel(
 #pragma unroll
             for (int tap = 0; tap < 7; ++tap) {
                 const int ts = t + tap - 3;
-                if (ts < 0 || ts >= a.T) continue;
+                if (ts < 0 || ts >= len) continue;
                 const float* src = a.x + (size_t)(row + tap - 3) * C + lane * 8;
                 const float* wt = a.dw_w + tap * C + lane * 8;
                 const float4 x0 = *reinterpret_cast<const float4*>(src);
@@ -401,6 +474,7 @@ struct VocosIstftArgs {
     const float* window;  // (1024) the loaded head.istft.window
     float* frames;        // (B T, 1024) windowed irfft of every frame
     int B, T;
+    const int* total;     // RAGGED: the packed row count off[B]
 };
 
 __device__ __forceinline__ unsigned vc_bitrev9(unsigned v) {
@@ -413,13 +487,16 @@ __device__ __forceinline__ unsigned vc_bitrev9(unsigned v) {
 // inverse DFT z[n] is x[2n] + i x[2n + 1] (the mirror of pm_fft.h's forward
 // packing). The imaginary parts of bins 0 and 512 are dropped, as the C2R
 // irfft does.
-template <int MODE>
+template <int MODE, bool RAGGED>
 __global__ __launch_bounds__(256) void vocos_istft_frame_kernel(
     VocosIstftArgs a) {
+    static_assert(MODE == 0 || !RAGGED, "the (B, 513, T) spectrum is uniform");
     __shared__ float2 z[512];
     __shared__ float2 tw[512];          // e^{+2 pi i j / 512}
     const int tid = threadIdx.x;
     const int row = blockIdx.x;
+    if constexpr (RAGGED)
+        if (row >= *a.total) return;    // the whole workgroup, before a barrier
     const int b = row / a.T, t = row - b * a.T;
 
     auto bin = [&](int k) -> float2 {
@@ -484,18 +561,32 @@ __global__ __launch_bounds__(256) void vocos_istft_frame_kernel(
 // audio (B, 256 T): sample n sits at n + 384 of the uncropped overlap-add;
 // frames are summed in increasing order (as torch fold does), then divided by
 // the window^2 envelope summed the same way. No atomics.
+// RAGGED: the frames of utterance b are its len packed rows from off[b]; its
+// last frame is len - 1, so the envelope is that of the frames that exist,
+// and the samples from 256 len up to the padded 256 T are exact zeros.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void vocos_ola_kernel(
-    const float* frames, const float* window, float* audio, int T) {
+    const float* frames, const float* window, float* audio, int T,
+    const int* off) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
     if (n >= T * PM_VOCOS_HOP) return;
+    int first = b * T, len = T;
+    if constexpr (RAGGED) {
+        first = off[b];
+        len = off[b + 1] - first;
+        if (n >= len * PM_VOCOS_HOP) {
+            audio[(size_t)b * T * PM_VOCOS_HOP + n] = 0.f;
+            return;
+        }
+    }
     const int p = n + PM_VOCOS_PAD;
-    const int hi = min(p / PM_VOCOS_HOP, T - 1);
+    const int hi = min(p / PM_VOCOS_HOP, len - 1);
     const int lo = max(0, (p - PM_VOCOS_NFFT + PM_VOCOS_HOP) / PM_VOCOS_HOP);
     float y = 0.f, env = 0.f;
     for (int f = lo; f <= hi; ++f) {
         const int i = p - f * PM_VOCOS_HOP;
-        y += frames[((size_t)b * T + f) * PM_VOCOS_NFFT + i];
+        y += frames[((size_t)first + f) * PM_VOCOS_NFFT + i];
         const float w = window[i];
         env += w * w;
     }

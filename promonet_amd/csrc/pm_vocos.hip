@@ -7,6 +7,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "promonet_hip.h"
@@ -92,23 +93,33 @@ hipError_t gemm(int dtype, int taps, bool cf, const VocosGemmArgs& a,
                     round_up(a.N, PM_VOCOS_GEMM_COLS) / PM_VOCOS_GEMM_COLS);
     return with_elem(dtype, [&](auto et) {
         typedef decltype(et) ET;
-        if (taps == 7 && cf)
-            hipLaunchKernelGGL((vocos_gemm_kernel<ET, 7, true>), grid,
-                               dim3(256), 0, s, a);
-        else if (taps == 7)
-            hipLaunchKernelGGL((vocos_gemm_kernel<ET, 7, false>), grid,
-                               dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL((vocos_gemm_kernel<ET, 1, false>), grid,
-                               dim3(256), 0, s, a);
+        auto launch = [&](auto ragged) {
+            constexpr bool RG = decltype(ragged)::value;
+            if (taps == 7 && cf)
+                hipLaunchKernelGGL((vocos_gemm_kernel<ET, 7, true, RG>), grid,
+                                   dim3(256), 0, s, a);
+            else if (taps == 7)
+                hipLaunchKernelGGL((vocos_gemm_kernel<ET, 7, false, RG>), grid,
+                                   dim3(256), 0, s, a);
+            else
+                hipLaunchKernelGGL((vocos_gemm_kernel<ET, 1, false, RG>), grid,
+                                   dim3(256), 0, s, a);
+        };
+        if (a.rg.map) launch(std::true_type());
+        else launch(std::false_type());
         return hipGetLastError();
     });
 }
 
+// rows: B T; total: the packed row count on the device (ragged) or null
 hipError_t layer_norm(float* x, const float* g, const float* b, int rows,
-                      hipStream_t s) {
-    hipLaunchKernelGGL(vocos_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, s,
-                       x, g, b, rows);
+                      const int* total, hipStream_t s) {
+    if (total)
+        hipLaunchKernelGGL(vocos_ln_kernel<true>, dim3((rows + 3) / 4),
+                           dim3(256), 0, s, x, g, b, rows, total);
+    else
+        hipLaunchKernelGGL(vocos_ln_kernel<false>, dim3((rows + 3) / 4),
+                           dim3(256), 0, s, x, g, b, rows, total);
     return hipGetLastError();
 }
 
@@ -116,7 +127,8 @@ hipError_t block(int dtype, const VocosBlockArgs& a, hipStream_t s) {
     return with_elem(dtype, [&](auto et) {
         typedef decltype(et) ET;
         typedef VocosTile<ET> Tile;
-        auto kern = vocos_block_kernel<ET>;
+        auto kern = a.rg.map ? vocos_block_kernel<ET, true>
+                             : vocos_block_kernel<ET, false>;
         hipError_t e = ensure_lds(reinterpret_cast<const void*>(kern),
                                   Tile::SMEM);
         if (e != hipSuccess) return e;
@@ -127,35 +139,45 @@ hipError_t block(int dtype, const VocosBlockArgs& a, hipStream_t s) {
     });
 }
 
-// frames (B T, 1024) -> audio (B, 256 T)
+// frames (B T, 1024) -> audio (B, 256 T); off: the ragged batch's (B + 1)
+// first rows (mode 0 only) or null
 hipError_t istft(int mode, const float* spec, const float* window,
-                 float* frames, float* audio, int B, int T, hipStream_t s) {
-    VocosIstftArgs a = {spec, window, frames, B, T};
-    if (mode == 0)
-        hipLaunchKernelGGL(vocos_istft_frame_kernel<0>, dim3(B * T), dim3(256),
-                           0, s, a);
+                 float* frames, float* audio, int B, int T, const int* off,
+                 hipStream_t s) {
+    VocosIstftArgs a = {spec, window, frames, B, T, off ? off + B : nullptr};
+    if (mode == 0 && off)
+        hipLaunchKernelGGL((vocos_istft_frame_kernel<0, true>), dim3(B * T),
+                           dim3(256), 0, s, a);
+    else if (mode == 0)
+        hipLaunchKernelGGL((vocos_istft_frame_kernel<0, false>), dim3(B * T),
+                           dim3(256), 0, s, a);
     else
-        hipLaunchKernelGGL(vocos_istft_frame_kernel<1>, dim3(B * T), dim3(256),
-                           0, s, a);
+        hipLaunchKernelGGL((vocos_istft_frame_kernel<1, false>), dim3(B * T),
+                           dim3(256), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(vocos_ola_kernel,
-                       dim3((T * PM_VOCOS_HOP + 255) / 256, B), dim3(256), 0,
-                       s, frames, window, audio, T);
+    const dim3 grid((T * PM_VOCOS_HOP + 255) / 256, B);
+    if (off)
+        hipLaunchKernelGGL(vocos_ola_kernel<true>, grid, dim3(256), 0, s,
+                           frames, window, audio, T, off);
+    else
+        hipLaunchKernelGGL(vocos_ola_kernel<false>, grid, dim3(256), 0, s,
+                           frames, window, audio, T, off);
     return hipGetLastError();
 }
 
 // the head's logits (B T, 1026) -> audio; frames aliases nothing it reads
 hipError_t head(int dtype, const float* x, const void* w, const float* bias,
                 const float* window, float* logits, float* frames,
-                float* audio, int B, int T, hipStream_t s) {
+                float* audio, int B, int T, const VocosRagged& rg,
+                hipStream_t s) {
     VocosGemmArgs g = {};
     g.x = x; g.w = w; g.bias = bias; g.out = logits;
     g.B = B; g.T = T; g.K = PM_VOCOS_C; g.N = PM_VOCOS_HEAD_OUT;
-    g.ldo = PM_VOCOS_HEAD_OUT;
+    g.ldo = PM_VOCOS_HEAD_OUT; g.rg = rg;
     hipError_t e = gemm(dtype, 1, false, g, s);
     if (e != hipSuccess) return e;
-    return istft(0, logits, window, frames, audio, B, T, s);
+    return istft(0, logits, window, frames, audio, B, T, rg.off, s);
 }
 
 size_t block_weight_bytes(int dtype, int C, int H) {
@@ -339,20 +361,33 @@ extern "C" size_t pm_vocos_workspace_bytes(pm_vocos_t h, int batch,
            align256((size_t)batch * h->C * 4);
 }
 
-extern "C" int pm_vocos_forward(pm_vocos_t h, const float* features,
-                                const float* global_features, int global_batch,
-                                float* audio, int batch, int frames,
-                                void* workspace, size_t workspace_bytes,
-                                void* stream) {
-    if (!h || !features || !audio) return vfail(PM_EINVAL, "null argument");
+// the uniform workspace | row map (rows x 16 bytes) | offsets (B + 1)
+extern "C" size_t pm_vocos_ragged_workspace_bytes(pm_vocos_t h, int batch,
+                                                  int frames) {
+    const size_t uniform = pm_vocos_workspace_bytes(h, batch, frames);
+    if (!uniform) return 0;
+    return uniform + align256((size_t)batch * frames * sizeof(VocosRow)) +
+           align256(((size_t)batch + 1) * 4);
+}
+
+// lengths null: the uniform batch; else the ragged one, rows packed
+static int vocos_forward(pm_vocos_t h, const float* features,
+                         const float* global_features, int global_batch,
+                         const int* lengths, bool ragged, float* audio,
+                         int batch, int frames, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (!h || !features || !audio || (ragged && !lengths))
+        return vfail(PM_EINVAL, "null argument");
     if (!h->finalized)
         return vfail(PM_ESTATE, "pm_vocos_finalize not called");
     if (batch < 1 || frames < 1)
         return vfail(PM_EINVAL, "batch and frames must be positive");
     if (global_features && global_batch != 1 && global_batch != batch)
         return vfail(PM_EINVAL, "global batch must be 1 or batch");
-    if (!workspace ||
-        workspace_bytes < pm_vocos_workspace_bytes(h, batch, frames))
+    const size_t uniform = pm_vocos_workspace_bytes(h, batch, frames);
+    if (!workspace || workspace_bytes <
+            (ragged ? pm_vocos_ragged_workspace_bytes(h, batch, frames)
+                    : uniform))
         return vfail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t rows = (size_t)batch * frames;
@@ -364,6 +399,18 @@ extern "C" int pm_vocos_forward(pm_vocos_t h, const float* features,
     float* cond = (float*)((char*)logits +
                            align256(rows * PM_VOCOS_HEAD_OUT * 4));
     float* frames_buf = x0;         // 2 x rows x 512 == rows x 1024 floats
+    VocosRagged rg = {nullptr, nullptr};
+    if (ragged) {
+        VocosRow* map = (VocosRow*)(ws + uniform);
+        int* off = (int*)(ws + uniform + align256(rows * sizeof(VocosRow)));
+        hipLaunchKernelGGL(vocos_rowmap_kernel,
+                           dim3((frames + 255) / 256, batch), dim3(256), 0, s,
+                           lengths, off, map, batch, frames);
+        VC_TRY(hipGetLastError());
+        rg.map = map;
+        rg.off = off;
+    }
+    const int* total = ragged ? rg.off + batch : nullptr;
 
     // conv_pre(x) + cond(g)                                vocos.py:41-49
     if (global_features) {
@@ -378,14 +425,16 @@ extern "C" int pm_vocos_forward(pm_vocos_t h, const float* features,
     g.x = features; g.w = h->conv_pre; g.bias = h->at("conv_pre.bias");
     g.gbias = global_features ? cond : nullptr; g.gbatch = global_batch;
     g.out = x1; g.B = batch; g.T = frames; g.K = h->F; g.N = C; g.ldo = C;
+    g.rg = rg;
     VC_TRY(gemm(d, 7, true, g, s));
     // backbone embed + norm                                vocos.py:96-98
     g = {};
     g.x = x1; g.w = h->embed; g.bias = h->at("backbone.embed.bias");
     g.out = x0; g.B = batch; g.T = frames; g.K = C; g.N = C; g.ldo = C;
+    g.rg = rg;
     VC_TRY(gemm(d, 7, false, g, s));
     VC_TRY(layer_norm(x0, h->at("backbone.norm.weight"),
-                      h->at("backbone.norm.bias"), (int)rows, s));
+                      h->at("backbone.norm.bias"), (int)rows, total, s));
     float* cur = x0;
     float* nxt = x1;
     for (int i = 0; i < h->layers; ++i) {
@@ -397,17 +446,39 @@ extern "C" int pm_vocos_forward(pm_vocos_t h, const float* features,
         a.w1 = h->w1[i]; a.b1 = h->at(layer_key(i, "pwconv1.bias"));
         a.w2 = h->w2[i]; a.b2 = h->at(layer_key(i, "pwconv2.bias"));
         a.gamma = h->at(layer_key(i, "gamma"));
-        a.B = batch; a.T = frames; a.H = h->H;
+        a.B = batch; a.T = frames; a.H = h->H; a.rg = rg;
         VC_TRY(block(d, a, s));
         std::swap(cur, nxt);
     }
     VC_TRY(layer_norm(cur, h->at("backbone.final_layer_norm.weight"),
-                      h->at("backbone.final_layer_norm.bias"), (int)rows, s));
+                      h->at("backbone.final_layer_norm.bias"), (int)rows, total,
+                      s));
     // head: cur -> logits, then the frames overwrite the residual buffers
     VC_TRY(head(d, cur, h->head, h->at("head.out.bias"),
                 h->at("head.istft.window"), logits, frames_buf, audio, batch,
-                frames, s));
+                frames, rg, s));
     return PM_OK;
+}
+
+extern "C" int pm_vocos_forward(pm_vocos_t h, const float* features,
+                                const float* global_features, int global_batch,
+                                float* audio, int batch, int frames,
+                                void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    return vocos_forward(h, features, global_features, global_batch, nullptr,
+                         false, audio, batch, frames, workspace,
+                         workspace_bytes, stream);
+}
+
+extern "C" int pm_vocos_forward_ragged(pm_vocos_t h, const float* features,
+                                       const float* global_features,
+                                       int global_batch, const int* lengths,
+                                       float* audio, int batch, int frames,
+                                       void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    return vocos_forward(h, features, global_features, global_batch, lengths,
+                         true, audio, batch, frames, workspace,
+                         workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -486,7 +557,8 @@ extern "C" int pm_vocos_head(int dtype, const float* x, const float* w,
     char* frames_buf = logits + align256(rows * PM_VOCOS_HEAD_OUT * 4);
     VC_TRY(pack(dtype, w, base, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1, s));
     VC_TRY(head(dtype, x, base, bias, window, (float*)logits,
-                (float*)frames_buf, audio, batch, frames, s));
+                (float*)frames_buf, audio, batch, frames,
+                VocosRagged{nullptr, nullptr}, s));
     return PM_OK;
 }
 
@@ -505,6 +577,6 @@ extern "C" int pm_istft(const float* spectrum, const float* window,
         workspace_bytes < pm_istft_workspace_bytes(batch, frames))
         return vfail(PM_ENOMEM, "workspace too small");
     VC_TRY(istft(1, spectrum, window, (float*)workspace, audio, batch, frames,
-                 (hipStream_t)stream));
+                 nullptr, (hipStream_t)stream));
     return PM_OK;
 }

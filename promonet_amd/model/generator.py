@@ -369,15 +369,18 @@ class MelGenerator(torch.nn.Module):
         speakers,
         spectral_balance_ratios,
         loudness_ratios,
-        previous_samples=None
+        previous_samples=None,
+        lengths=None
     ):
         """(B, 513, T) linear spectrograms -> (B, 1, 256 T). Vocos ignores
         `previous_samples`; it is optional here because the reference's own
-        caller (baseline/mels.py:97-102) omits it."""
+        caller (baseline/mels.py:97-102) omits it. `lengths` (B,) frames (not
+        in the reference): ragged batch of zero-padded spectrograms, see
+        `Vocos.forward`."""
         features = self.prepare_features(spectrograms)
         global_features = self.prepare_global_features(
             speakers, spectral_balance_ratios, loudness_ratios)
-        return self.model(features, global_features)
+        return self.model(features, global_features, lengths)
 
     def prepare_features(self, spectrograms):
         """linear_to_mel (+ the clipping threshold with SPARSE_MELS)."""

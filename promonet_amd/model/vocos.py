@@ -6,7 +6,9 @@ by config/baselines/vocos.py): same constructor arguments, same
 initialisation, so a reference checkpoint loads unchanged. The forward pass
 is one engine call (`pm_vocos_forward`): input convs, the fused ConvNeXt
 blocks, the spectral head and the inverse STFT; there is no PyTorch compute
-path.
+path. Not in the reference: `forward(..., lengths=)` runs a ragged batch of
+zero-padded utterances (`pm_vocos_forward_ragged`), each equal to its
+stand-alone synthesis bit for bit.
 """
 import ctypes
 
@@ -27,6 +29,22 @@ def resolve_dtype(name):
             f'COMPUTE_DTYPE {name!r} is not a Vocos mode: one of '
             f'{sorted(VOCOS_DTYPES)}')
     return VOCOS_DTYPES[name]
+
+
+def check_lengths(lengths, batch, frames):
+    """`lengths` of a ragged (batch, ..., frames) input as a tensor. Values
+    that arrive on the host (a list or a CPU tensor) must lie in [1, frames];
+    a device tensor is trusted: reading it back would stall the stream."""
+    lengths = torch.as_tensor(lengths)
+    if lengths.shape != (batch,):
+        raise ValueError('lengths must have shape (B,)')
+    if lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+        raise ValueError('lengths must be integers')
+    if not lengths.is_cuda and (
+            int(lengths.min()) < 1 or int(lengths.max()) > frames):
+        raise ValueError(
+            f'lengths must be in [1, {frames}] (the frames of the input)')
+    return lengths
 
 
 class ConvNeXtBlock(torch.nn.Module):
@@ -172,9 +190,13 @@ class Vocos(torch.nn.Module):
     # Forward (vocos.py:41-54)
     ###########################################################################
 
-    def forward(self, x, g=None):
+    def forward(self, x, g=None, lengths=None):
         """x (B, F, T) features, g (B|1, G, 1) global features or None ->
-        audio (B, 1, 256 T)."""
+        audio (B, 1, 256 T). `lengths` (B,) frames (not in the reference):
+        ragged batch of zero-padded utterances, each synthesised as if alone;
+        the audio past 256 * lengths[b] is zero. Values on the host (a list
+        or a CPU tensor) are range-checked; a device tensor is trusted and
+        never read back."""
         _lib.require_gpu(x)
         engine = self.engine()
         lib = _lib.lib()
@@ -193,17 +215,31 @@ class Vocos(torch.nn.Module):
                 raise ValueError(
                     f'global features must be (B|1, {self.gin_channels}[, 1])')
             pointer, gbatch = _lib.ptr(g), g.shape[0]
+        if lengths is not None:
+            lengths = check_lengths(lengths, batch, frames).to(
+                device=x.device, dtype=torch.int32).contiguous()
         out = torch.empty(
             batch, 1, frames * self.head.istft.hop_length,
             dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            size = lib.pm_vocos_workspace_bytes(engine, batch, frames)
+            if lengths is None:
+                size = lib.pm_vocos_workspace_bytes(engine, batch, frames)
+            else:
+                size = lib.pm_vocos_ragged_workspace_bytes(
+                    engine, batch, frames)
             if self._workspace is None or self._workspace.numel() < size or \
                     self._workspace.device != x.device:
                 self._workspace = torch.empty(
                     size, dtype=torch.uint8, device=x.device)
-            _lib.check(lib.pm_vocos_forward(
-                engine, _lib.ptr(x), pointer, gbatch, _lib.ptr(out), batch,
-                frames, self._workspace.data_ptr(), self._workspace.numel(),
-                _lib.stream()))
+            if lengths is None:
+                _lib.check(lib.pm_vocos_forward(
+                    engine, _lib.ptr(x), pointer, gbatch, _lib.ptr(out),
+                    batch, frames, self._workspace.data_ptr(),
+                    self._workspace.numel(), _lib.stream()))
+            else:
+                _lib.check(lib.pm_vocos_forward_ragged(
+                    engine, _lib.ptr(x), pointer, gbatch,
+                    _lib.ptr(lengths, torch.int32), _lib.ptr(out), batch,
+                    frames, self._workspace.data_ptr(),
+                    self._workspace.numel(), _lib.stream()))
         return out
