@@ -235,13 +235,11 @@ def broadcast_model(model, src=0):
 
 def invalidate_engines(model):
     """In-place parameter updates bypass `_apply` and the load_state_dict
-    hooks: drop every packed engine (HiFiGAN / FARGAN, bare or inside a
-    Generator) and every host-side copy of a buffer."""
+    hooks: drop every packed engine (model.engine.EngineModule, bare or
+    inside a Generator) and every host-side copy of a buffer."""
     for module in model.modules():
         if hasattr(module, '_invalidate'):
             module._invalidate()
-        elif hasattr(module, '_destroy'):
-            module._destroy()
         if hasattr(module, '_threshold'):
             module._threshold = None
 

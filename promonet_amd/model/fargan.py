@@ -11,7 +11,6 @@ persistent kernel per utterance (`pm_fargan_forward`, or
 `pm_fargan_forward_stateful` from a carried recurrent state); there is no
 PyTorch compute path.
 """
-import ctypes
 import math
 
 import torch
@@ -19,6 +18,7 @@ import torch
 import promonet_amd
 from promonet_amd import _lib
 from .core import attach
+from .engine import EngineModule, device_lengths, global_features
 
 # the recurrent state (fargan.py:406-415): three GRU states and the last
 # sub-frame's input [features 128 | previous subframe 64 | lookback 68]
@@ -33,7 +33,9 @@ def initialize_recurrent_state(batch_size, device):
         for size in STATE_SIZES)
 
 
-class FARGAN(torch.nn.Module):
+class FARGAN(EngineModule):
+
+    ABI = 'fargan'
 
     # auto mode: calls served by the one-workgroup-per-utterance kernel after
     # the cluster exchange has timed out twice in a row, before the clusters
@@ -51,11 +53,6 @@ class FARGAN(torch.nn.Module):
         self._fallback_calls = 0    # auto mode: calls left on the slow kernel
         for key, tensor in self._initial_state().items():
             attach(self, key, tensor)
-        self._engine = None
-        self._engine_key = None
-        self._workspace = None
-        self.register_load_state_dict_post_hook(
-            lambda module, keys: module._destroy())
 
     def _initial_state(self):
         """Reference init: orthogonal Linear weights (fargan.py:418-424),
@@ -92,59 +89,16 @@ class FARGAN(torch.nn.Module):
         return state
 
     ###########################################################################
-    # Engine lifetime
+    # Engine (handle lifetime, workspace and stream guard: engine.py)
     ###########################################################################
 
-    def _invalidate(self):
-        self._destroy()
+    def _key(self):
+        return self.weight_dtype
 
-    def _destroy(self):
-        if getattr(self, '_engine', None) is not None:
-            _lib.lib().pm_fargan_destroy(self._engine)
-        self._engine = None
-        self._engine_key = None
-
-    def __del__(self):
-        try:
-            self._destroy()
-        except Exception:
-            pass
-
-    def _apply(self, fn, *args, **kwargs):
-        result = super()._apply(fn, *args, **kwargs)
-        self._destroy()
-        return result
-
-    def engine(self):
-        first = next(self.parameters())
-        if not first.is_cuda:
-            raise RuntimeError(
-                'promonet_amd.model.FARGAN runs on an AMD GPU only; move the '
-                'model with .to("cuda:N") (no CPU fallback)')
-        key = (first.device, self.weight_dtype)
-        if self._engine is not None and self._engine_key == key:
-            return self._engine
-        self._destroy()
-        lib = _lib.lib()
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(first.device):
-            _lib.check(lib.pm_fargan_create(
-                self.num_features, self.global_channels,
-                _lib.DTYPES[self.weight_dtype], ctypes.byref(handle)))
-            try:
-                for name, tensor in self.state_dict().items():
-                    tensor = tensor.detach().to(torch.float32).contiguous()
-                    _lib.check(lib.pm_fargan_load_tensor(
-                        handle, name.encode(), _lib.ptr(tensor),
-                        _lib.shape_array(tensor.shape), tensor.ndim,
-                        _lib.stream()))
-                _lib.check(lib.pm_fargan_finalize(handle, _lib.stream()))
-            except Exception:
-                lib.pm_fargan_destroy(handle)
-                raise
-        self._engine = handle
-        self._engine_key = key
-        return handle
+    def _create(self, lib, handle):
+        return lib.pm_fargan_create(
+            self.num_features, self.global_channels,
+            _lib.DTYPES[self.weight_dtype], handle)
 
     ###########################################################################
     # Forward (fargan.py:21-59)
@@ -222,9 +176,7 @@ class FARGAN(torch.nn.Module):
             raise ValueError(
                 f'expected {self.num_features + 1} feature channels (the last '
                 f'one is the pitch period), got {x.shape[1]}')
-        g = g.reshape(g.shape[0], -1).to(torch.float32).contiguous()
-        if g.shape[1] != self.global_channels or g.shape[0] not in (1, batch):
-            raise ValueError('global features must be (B|1, 258[, 1])')
+        g = global_features(g, batch, self.global_channels, x.device)
         pointer, pbatch = None, 1
         if previous is not None:
             previous = previous.reshape(previous.shape[0], -1).to(
@@ -243,55 +195,39 @@ class FARGAN(torch.nn.Module):
                 batch, 2 * self.hopsize, dtype=torch.float32, device=x.device)
             states_out = torch.empty(
                 batch, sum(STATE_SIZES), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            size = lib.pm_fargan_workspace_bytes(engine, batch, frames)
-            if self._workspace is None or self._workspace.numel() < size or \
-                    self._workspace.device != x.device:
-                self._workspace = torch.empty(
-                    size, dtype=torch.uint8, device=x.device)
-
-            if lengths is not None:
-                lengths = torch.as_tensor(lengths).to(
-                    device=x.device, dtype=torch.int32).contiguous()
-                if lengths.shape != (batch,):
-                    raise ValueError('lengths must have shape (B,)')
-
-            if self.kernel_mode == 0 and not self.check_exchange:
-                # the clusters' bounded waits are the only safety net of auto
-                # mode: without the check a timed-out exchange would pass as
-                # audio
-                raise RuntimeError(
-                    'FARGAN: check_exchange=False needs an explicit '
-                    'kernel_mode (1 or 2)')
+        if lengths is not None:
+            lengths = device_lengths(lengths, batch, x.device)
+        if self.kernel_mode == 0 and not self.check_exchange:
+            # the clusters' bounded waits are the only safety net of auto
+            # mode: without the check a timed-out exchange would pass as
+            # audio
+            raise RuntimeError(
+                'FARGAN: check_exchange=False needs an explicit '
+                'kernel_mode (1 or 2)')
+        if stateful:
+            forward = 'pm_fargan_forward_stateful'
+            tail = (_lib.ptr(states), _lib.ptr(out), _lib.ptr(previous_out),
+                    _lib.ptr(states_out))
+        elif lengths is None:
+            forward, tail = 'pm_fargan_forward', (_lib.ptr(out),)
+        else:
+            forward = 'pm_fargan_forward_ragged'
+            tail = (_lib.ptr(lengths, torch.int32), _lib.ptr(out))
+        # (one claim of the workspace over every launch of the retry sequence)
+        with self._claimed_workspace(
+                engine, batch, frames, x.device) as workspace:
 
             def launch(mode):
                 _lib.check(lib.pm_fargan_set_mode(engine, mode))
-                if stateful:
-                    _lib.check(lib.pm_fargan_forward_stateful(
-                        engine, _lib.ptr(x), int(channels_last), _lib.ptr(g),
-                        g.shape[0], pointer, pbatch, _lib.ptr(states),
-                        _lib.ptr(out), _lib.ptr(previous_out),
-                        _lib.ptr(states_out), batch, frames,
-                        self._workspace.data_ptr(), self._workspace.numel(),
-                        _lib.stream()))
-                elif lengths is None:
-                    _lib.check(lib.pm_fargan_forward(
-                        engine, _lib.ptr(x), int(channels_last), _lib.ptr(g),
-                        g.shape[0], pointer, pbatch, _lib.ptr(out), batch,
-                        frames, self._workspace.data_ptr(),
-                        self._workspace.numel(), _lib.stream()))
-                else:
-                    _lib.check(lib.pm_fargan_forward_ragged(
-                        engine, _lib.ptr(x), int(channels_last), _lib.ptr(g),
-                        g.shape[0], pointer, pbatch,
-                        _lib.ptr(lengths, torch.int32), _lib.ptr(out), batch,
-                        frames, self._workspace.data_ptr(),
-                        self._workspace.numel(), _lib.stream()))
+                _lib.check(getattr(lib, forward)(
+                    engine, _lib.ptr(x), int(channels_last), _lib.ptr(g),
+                    g.shape[0], pointer, pbatch, *tail, batch, frames,
+                    workspace.data_ptr(), workspace.numel(), _lib.stream()))
                 if self.check_exchange:
                     # the cluster kernel's inter-workgroup waits are bounded;
                     # a tripped bound must not pass as audio (one stream sync)
                     _lib.check(lib.pm_fargan_check(
-                        engine, batch, frames, self._workspace.data_ptr(),
+                        engine, batch, frames, workspace.data_ptr(),
                         _lib.stream()))
             if self.kernel_mode == 0 and self._fallback_calls > 0:
                 # the mode is chosen BEFORE the counter moves (the call that

@@ -306,7 +306,6 @@ class Generator(torch.nn.Module):
         capture. The graph gets a workspace of its OWN: the module's shared
         one may be re-allocated by a later, larger forward, and a captured
         kernel keeps the pointer it was recorded with."""
-        vocoder = self.model
         # (inference mode OFF for the capture: the static input is written in
         # place on every replay, by callers inside AND outside
         # torch.inference_mode() - an inference tensor would refuse the second
@@ -316,19 +315,14 @@ class Generator(torch.nn.Module):
             static = torch.empty(x.shape, dtype=x.dtype, device=x.device)
             static.copy_(x)
             self.packed_inference(static)
-            shared = vocoder._workspace
-            vocoder._workspace = None
-            try:
+            with self.model.private_workspace() as private:
                 graph = torch.cuda.CUDAGraph()
                 torch.cuda.synchronize(x.device)
                 with torch.cuda.graph(graph):
                     output = self.packed_inference(static)
-                private = vocoder._workspace
-            finally:
-                vocoder._workspace = shared
             torch.cuda.synchronize(x.device)
         return {'graph': graph, 'input': static, 'output': output,
-                'workspace': private}
+                'workspace': private.tensor}
 
     def remove_weight_norm(self):
         self.model.remove_weight_norm()

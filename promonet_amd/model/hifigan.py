@@ -15,6 +15,7 @@ import torch
 import promonet_amd
 from promonet_amd import _lib
 from .core import attach
+from .engine import EngineModule, device_lengths, global_features
 
 
 def checkpoint_schedule(stages):
@@ -27,7 +28,10 @@ def checkpoint_schedule(stages):
         return ['f16a2']
     return ['f16'] * (stages - 2) + ['f16ux', 'f16a2']
 
-class HiFiGAN(torch.nn.Module):
+
+class HiFiGAN(EngineModule):
+
+    ABI = 'hifigan'
 
     def __init__(self, initial_channel, gin_channels):
         super().__init__()
@@ -44,14 +48,6 @@ class HiFiGAN(torch.nn.Module):
 
         for key, tensor in self._initial_state().items():
             attach(self, key, tensor)
-
-        self._engine = None
-        self._engine_key = None
-        self._generation = 0     # bumped whenever the engine is dropped
-        self._workspace = None
-        self._busy = None        # (stream, event) of the last forward
-        self.register_load_state_dict_post_hook(
-            lambda module, keys: module._invalidate())
 
     ###########################################################################
     # Parameters (reference init: hifigan.py:19-61, 220-223)
@@ -95,45 +91,13 @@ class HiFiGAN(torch.nn.Module):
         return state
 
     ###########################################################################
-    # Engine lifetime
+    # Engine (handle lifetime, workspace and stream guard: engine.py)
     ###########################################################################
 
-    def _invalidate(self):
-        self._destroy()
+    def _key(self):
+        return self.compute_dtype
 
-    def _destroy(self):
-        if getattr(self, '_engine', None) is not None:
-            _lib.lib().pm_hifigan_destroy(self._engine)
-            # (captured graphs hold the old engine's weight pointers:
-            # Generator.packed_inference(graph=True) keys its cache on this)
-            self._generation = getattr(self, '_generation', 0) + 1
-        self._engine = None
-        self._engine_key = None
-
-    def __del__(self):
-        try:
-            self._destroy()
-        except Exception:
-            pass
-
-    def _apply(self, fn, *args, **kwargs):
-        # .to() / .cuda() / .half() move the parameters: repack lazily
-        result = super()._apply(fn, *args, **kwargs)
-        self._invalidate()
-        return result
-
-    def engine(self):
-        """Create the HIP engine and (re)load every tensor when needed."""
-        first = next(self.parameters())
-        if not first.is_cuda:
-            raise RuntimeError(
-                'promonet_amd.model.HiFiGAN runs on an AMD GPU only; move the '
-                'model with .to("cuda:N") (no CPU fallback)')
-        key = (first.device, self.compute_dtype)
-        if self._engine is not None and self._engine_key == key:
-            return self._engine
-        self._destroy()
-        lib = _lib.lib()
+    def _create(self, lib, handle):
         config = _lib.HifiganConfig()
         config.num_features = self.initial_channel
         config.global_channels = self.gin_channels
@@ -164,64 +128,7 @@ class HiFiGAN(torch.nn.Module):
         if len(per_stage) > 1:
             for i, name in enumerate(per_stage):
                 config.stage_compute_dtype[i] = 1 + _lib.DTYPES[name]
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(first.device):
-            _lib.check(lib.pm_hifigan_create(
-                ctypes.byref(config), ctypes.byref(handle)))
-            try:
-                for name, tensor in self.state_dict().items():
-                    tensor = tensor.detach().to(torch.float32).contiguous()
-                    _lib.check(lib.pm_hifigan_load_tensor(
-                        handle, name.encode(), _lib.ptr(tensor),
-                        _lib.shape_array(tensor.shape), tensor.ndim,
-                        _lib.stream()))
-                _lib.check(lib.pm_hifigan_finalize(handle, _lib.stream()))
-            except Exception:
-                lib.pm_hifigan_destroy(handle)
-                raise
-        self._engine = handle
-        self._engine_key = key
-        return handle
-
-    def workspace(self, batch, frames, device):
-        size = _lib.lib().pm_hifigan_workspace_bytes(
-            self.engine(), batch, frames)
-        if (
-            self._workspace is None or self._workspace.numel() < size or
-            self._workspace.device != device
-        ):
-            self._workspace = None
-            self._workspace = torch.empty(
-                size, dtype=torch.uint8, device=device)
-        return self._workspace
-
-    def _claim_workspace(self, device):
-        """One workspace per module: a forward on stream B while the previous
-        one is still running on stream A would overwrite the activations under
-        it. Raise instead (same-stream calls are ordered by the stream; a
-        different stream is fine once the previous forward has finished)."""
-        stream = torch.cuda.current_stream(device)
-        if torch.cuda.is_current_stream_capturing():
-            return None
-        if self._busy is not None:
-            previous, event = self._busy
-            if previous != stream and not event.query():
-                raise RuntimeError(
-                    'promonet_amd.model.HiFiGAN: forward on '
-                    f'{stream} while the previous forward is still running on '
-                    f'{previous} - the module owns ONE workspace; wait for it '
-                    '(stream.wait_stream / synchronize) or use one model per '
-                    'stream')
-            event = event if previous.device == stream.device \
-                else torch.cuda.Event()
-        else:
-            event = torch.cuda.Event()
-        return stream, event
-
-    def _release_workspace(self, claim):
-        if claim is not None:
-            claim[1].record(claim[0])
-            self._busy = claim
+        return lib.pm_hifigan_create(ctypes.byref(config), handle)
 
     ###########################################################################
     # Forward
@@ -243,17 +150,10 @@ class HiFiGAN(torch.nn.Module):
     def _run(self, x, g, channels_last, lengths=None):
         _lib.require_gpu(x)
         engine = self.engine()
-        lib = _lib.lib()
         x = x.to(torch.float32).contiguous()
         batch = x.shape[0]
         frames = x.shape[1] if channels_last else x.shape[2]
-        g = g.reshape(g.shape[0], -1).to(torch.float32).contiguous()
-        if g.shape[1] != self.gin_channels:
-            raise ValueError(
-                f'expected {self.gin_channels} global channels, '
-                f'got {g.shape[1]}')
-        if g.shape[0] not in (1, batch):
-            raise ValueError('global features must have batch 1 or B')
+        g = global_features(g, batch, self.gin_channels, x.device)
         if not channels_last and x.shape[1] != self.initial_channel:
             raise ValueError(
                 f'expected {self.initial_channel} feature channels, '
@@ -262,29 +162,18 @@ class HiFiGAN(torch.nn.Module):
             batch, 1, frames * self.hopsize, dtype=torch.float32,
             device=x.device)
         if lengths is not None:
-            lengths = torch.as_tensor(lengths).to(
-                device=x.device, dtype=torch.int32).contiguous()
-            if lengths.shape != (batch,):
-                raise ValueError('lengths must have shape (B,)')
-        with torch.cuda.device(x.device):
-            claim = self._claim_workspace(x.device)
-            workspace = self.workspace(batch, frames, x.device)
-            try:
-                if lengths is not None:
-                    _lib.check(lib.pm_hifigan_forward_ragged(
-                        engine, _lib.ptr(x), int(channels_last), _lib.ptr(g),
-                        g.shape[0], _lib.ptr(lengths, torch.int32),
-                        _lib.ptr(out), batch, frames, workspace.data_ptr(),
-                        workspace.numel(), _lib.stream()))
-                else:
-                    fn = lib.pm_hifigan_forward_cl if channels_last \
-                        else lib.pm_hifigan_forward
-                    _lib.check(fn(
-                        engine, _lib.ptr(x), _lib.ptr(g), g.shape[0],
-                        _lib.ptr(out), batch, frames, workspace.data_ptr(),
-                        workspace.numel(), _lib.stream()))
-            finally:
-                self._release_workspace(claim)
+            lengths = device_lengths(lengths, batch, x.device)
+            self._call(
+                'pm_hifigan_forward_ragged', engine, _lib.ptr(x),
+                int(channels_last), _lib.ptr(g), g.shape[0],
+                _lib.ptr(lengths, torch.int32), _lib.ptr(out), batch=batch,
+                frames=frames, device=x.device)
+        else:
+            self._call(
+                'pm_hifigan_forward_cl' if channels_last
+                else 'pm_hifigan_forward', engine, _lib.ptr(x), _lib.ptr(g),
+                g.shape[0], _lib.ptr(out), batch=batch, frames=frames,
+                device=x.device)
         return out
 
     def remove_weight_norm(self):

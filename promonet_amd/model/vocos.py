@@ -10,12 +10,11 @@ path. Not in the reference: `forward(..., lengths=)` runs a ragged batch of
 zero-padded utterances (`pm_vocos_forward_ragged`), each equal to its
 stand-alone synthesis bit for bit.
 """
-import ctypes
-
 import torch
 
 import promonet_amd
 from promonet_amd import _lib
+from .engine import EngineModule, device_lengths, global_features
 
 # COMPUTE_DTYPE values Vocos honours; 'checkpoint' is the mode that holds 1e-4
 # at a trained checkpoint's output scale (config.py, DESIGN.md section 10)
@@ -31,17 +30,18 @@ def resolve_dtype(name):
     return VOCOS_DTYPES[name]
 
 
-def check_lengths(lengths, batch, frames):
-    """`lengths` of a ragged (batch, ..., frames) input as a tensor. Values
-    that arrive on the host (a list or a CPU tensor) must lie in [1, frames];
-    a device tensor is trusted: reading it back would stall the stream."""
-    lengths = torch.as_tensor(lengths)
-    if lengths.shape != (batch,):
-        raise ValueError('lengths must have shape (B,)')
-    if lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+def check_lengths(lengths, batch, frames, device=None):
+    """`lengths` of a ragged (batch, ..., frames) input as an int32 tensor, on
+    `device` if one is given. Values that arrive on the host (a list or a CPU
+    tensor) must lie in [1, frames]; a device tensor is trusted: reading it
+    back would stall the stream."""
+    given = torch.as_tensor(lengths)
+    if given.dtype.is_floating_point or given.dtype == torch.bool:
         raise ValueError('lengths must be integers')
-    if not lengths.is_cuda and (
-            int(lengths.min()) < 1 or int(lengths.max()) > frames):
+    lengths = device_lengths(
+        given, batch, given.device if device is None else device)
+    if not given.is_cuda and (
+            int(given.min()) < 1 or int(given.max()) > frames):
         raise ValueError(
             f'lengths must be in [1, {frames}] (the frames of the input)')
     return lengths
@@ -102,7 +102,9 @@ class ISTFTHead(torch.nn.Module):
         self.istft = ISTFT(n_fft, hop_length, n_fft)
 
 
-class Vocos(torch.nn.Module):
+class Vocos(EngineModule):
+
+    ABI = 'vocos'
 
     def __init__(self, initial_channel, gin_channels):
         super().__init__()
@@ -121,70 +123,23 @@ class Vocos(torch.nn.Module):
             gin_channels, promonet_amd.VOCOS_CHANNELS, 1)
         for parameter in self.parameters():
             parameter.requires_grad_(False)
-        self._engine = None
-        self._engine_key = None
-        self._workspace = None
-        self.register_load_state_dict_post_hook(
-            lambda module, keys: module._destroy())
 
     ###########################################################################
-    # Engine lifetime
+    # Engine (handle lifetime, workspace and stream guard: engine.py)
     ###########################################################################
 
-    def _destroy(self):
-        if getattr(self, '_engine', None) is not None:
-            _lib.lib().pm_vocos_destroy(self._engine)
-        self._engine = None
-        self._engine_key = None
+    def _key(self):
+        return resolve_dtype(self.compute_dtype)
 
-    def __del__(self):
-        try:
-            self._destroy()
-        except Exception:
-            pass
-
-    def _apply(self, fn, *args, **kwargs):
-        result = super()._apply(fn, *args, **kwargs)
-        self._destroy()
-        return result
-
-    def engine(self):
-        first = next(self.parameters())
-        if not first.is_cuda:
-            raise RuntimeError(
-                'promonet_amd.model.Vocos runs on an AMD GPU only; move the '
-                'model with .to("cuda:N") (no CPU fallback)')
-        dtype = resolve_dtype(self.compute_dtype)
-        key = (first.device, dtype)
-        if self._engine is not None and self._engine_key == key:
-            return self._engine
-        self._destroy()
-        lib = _lib.lib()
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(first.device):
-            _lib.check(lib.pm_vocos_create(
-                self.initial_channel, self.gin_channels,
-                promonet_amd.VOCOS_CHANNELS,
-                self.backbone.convnext[0].pwconv1.out_features
-                if len(self.backbone.convnext) else
-                promonet_amd.VOCOS_POINTWISE_CHANNELS,
-                len(self.backbone.convnext), self.head.istft.n_fft,
-                self.head.istft.hop_length, _lib.DTYPES[dtype],
-                ctypes.byref(handle)))
-            try:
-                for name, tensor in self.state_dict().items():
-                    tensor = tensor.detach().to(torch.float32).contiguous()
-                    _lib.check(lib.pm_vocos_load_tensor(
-                        handle, name.encode(), _lib.ptr(tensor),
-                        _lib.shape_array(tensor.shape), tensor.ndim,
-                        _lib.stream()))
-                _lib.check(lib.pm_vocos_finalize(handle, _lib.stream()))
-            except Exception:
-                lib.pm_vocos_destroy(handle)
-                raise
-        self._engine = handle
-        self._engine_key = key
-        return handle
+    def _create(self, lib, handle):
+        return lib.pm_vocos_create(
+            self.initial_channel, self.gin_channels,
+            promonet_amd.VOCOS_CHANNELS,
+            self.backbone.convnext[0].pwconv1.out_features
+            if len(self.backbone.convnext) else
+            promonet_amd.VOCOS_POINTWISE_CHANNELS,
+            len(self.backbone.convnext), self.head.istft.n_fft,
+            self.head.istft.hop_length, _lib.DTYPES[self._key()], handle)
 
     ###########################################################################
     # Forward (vocos.py:41-54)
@@ -199,7 +154,6 @@ class Vocos(torch.nn.Module):
         never read back."""
         _lib.require_gpu(x)
         engine = self.engine()
-        lib = _lib.lib()
         x = x.to(torch.float32).contiguous()
         batch, channels, frames = x.shape
         if channels != self.initial_channel:
@@ -208,38 +162,20 @@ class Vocos(torch.nn.Module):
                 f'{channels}')
         pointer, gbatch = None, 1
         if g is not None:
-            g = g.reshape(g.shape[0], -1).to(
-                device=x.device, dtype=torch.float32).contiguous()
-            if g.shape[1] != self.gin_channels or \
-                    g.shape[0] not in (1, batch):
-                raise ValueError(
-                    f'global features must be (B|1, {self.gin_channels}[, 1])')
+            g = global_features(g, batch, self.gin_channels, x.device)
             pointer, gbatch = _lib.ptr(g), g.shape[0]
-        if lengths is not None:
-            lengths = check_lengths(lengths, batch, frames).to(
-                device=x.device, dtype=torch.int32).contiguous()
         out = torch.empty(
             batch, 1, frames * self.head.istft.hop_length,
             dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            if lengths is None:
-                size = lib.pm_vocos_workspace_bytes(engine, batch, frames)
-            else:
-                size = lib.pm_vocos_ragged_workspace_bytes(
-                    engine, batch, frames)
-            if self._workspace is None or self._workspace.numel() < size or \
-                    self._workspace.device != x.device:
-                self._workspace = torch.empty(
-                    size, dtype=torch.uint8, device=x.device)
-            if lengths is None:
-                _lib.check(lib.pm_vocos_forward(
-                    engine, _lib.ptr(x), pointer, gbatch, _lib.ptr(out),
-                    batch, frames, self._workspace.data_ptr(),
-                    self._workspace.numel(), _lib.stream()))
-            else:
-                _lib.check(lib.pm_vocos_forward_ragged(
-                    engine, _lib.ptr(x), pointer, gbatch,
-                    _lib.ptr(lengths, torch.int32), _lib.ptr(out), batch,
-                    frames, self._workspace.data_ptr(),
-                    self._workspace.numel(), _lib.stream()))
+        if lengths is None:
+            self._call(
+                'pm_vocos_forward', engine, _lib.ptr(x), pointer, gbatch,
+                _lib.ptr(out), batch=batch, frames=frames, device=x.device)
+        else:
+            lengths = check_lengths(lengths, batch, frames, x.device)
+            self._call(
+                'pm_vocos_forward_ragged', engine, _lib.ptr(x), pointer,
+                gbatch, _lib.ptr(lengths, torch.int32), _lib.ptr(out),
+                batch=batch, frames=frames, device=x.device,
+                workspace_bytes='pm_vocos_ragged_workspace_bytes')
         return out

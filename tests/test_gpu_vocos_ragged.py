@@ -182,15 +182,13 @@ def test_lengths_are_read_on_the_device(device, baseline, small):
         eager = model(static_mels, static_g, lengths=static_lengths).clone()
         # a workspace of the graph's own, allocated inside the capture
         shared = model._workspace
-        model._workspace = None
-        try:
+        with model.private_workspace() as holder:
             graph = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
             with torch.cuda.graph(graph):
                 output = model(static_mels, static_g, lengths=static_lengths)
-            private = model._workspace
-        finally:
-            model._workspace = shared
+        private = holder.tensor
+        assert model._workspace is shared
         graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(output, eager)
