@@ -488,6 +488,31 @@ int pm_loudness(const float* audio, const float* a_weights, float* out,
                 int batch, int samples, int bands, float min_db,
                 void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- resampling: torchaudio.functional.resample on the device -------------
+ * Replaces the host resampler of promonet/load.py:16-28 (load.audio) and
+ * promonet/baseline/mels.py:174- (mels.resample): torchaudio's
+ * 'sinc_interp_hann' algorithm, a polyphase bank of `new` Hann-windowed sinc
+ * filters of taps = 2 width + orig each, applied with stride `orig`.
+ * x: `rows` rows of up to n_in samples, x_stride floats apart; lengths: device
+ * int32 per row, clamped to [0, n_in] on the device and never read on the
+ * host (NULL: every row has n_in); bank: the filters TRANSPOSED, (taps, new).
+ * For a row of length len, out[q new + p] = sum_k bank[k][p]
+ * x[q orig + k - width] (x = 0 outside [0, len)) up to ceil(new len / orig),
+ * and exact zeros from there to n_out >= ceil(new n_in / orig). One fp32
+ * accumulator and an fma chain in ascending k per output: its bits depend on
+ * its row and index only, not on the tiling, the batch or `lengths`.
+ * Asynchronous, no allocation, no workspace; argument errors are reported
+ * before any GPU call. pm_resample_tile: the strides q one workgroup takes
+ * for this ratio (tile = that many x new outputs); negative on bad arguments
+ * and for a filter too long for the kernel's LDS segment (no standard rate
+ * pair: 8192 floats hold 4 strides of any of them), which pm_resample refuses
+ * in the same way.                                                          */
+int pm_resample_tile(int orig, int new_rate, int width);
+int pm_resample(const float* x, const int* lengths, const float* bank,
+                float* out, int rows, int n_in, long long x_stride, int orig,
+                int new_rate, int width, int n_out, long long out_stride,
+                void* stream);
+
 /* ---- Vocos mel vocoder engine: replaces promonet.model.Vocos --------------
  * (promonet/model/vocos.py, config/baselines/vocos.py MODEL = 'vocos').
  * conv_pre (k7) + cond, backbone embed (k7) + LayerNorm, `layers` fused

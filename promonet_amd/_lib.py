@@ -109,6 +109,9 @@ SIGNATURES = {
     'pm_linear_to_mel_backward': (_I, [_P] * 5 + [_I] * 5 + [_F, _P]),
     'pm_loudness_scratch_bytes': (_S, [_I, _I]),
     'pm_loudness': (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _S, _P]),
+    'pm_resample_tile': (_I, [_I, _I, _I]),
+    'pm_resample': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_int64, _I, _I, _I, _I,
+                         ctypes.c_int64, _P]),
     'pm_vocos_create': (_I, [_I] * 8 + [ctypes.POINTER(_P)]),
     'pm_vocos_destroy': (_I, [_P]),
     'pm_vocos_load_tensor': (_I, [_P, ctypes.c_char_p, _P, c_int64_p, _I, _P]),

@@ -15,6 +15,8 @@ Vocos) -> audio, all on the GPU. Differences from the reference:
 - `from_files_to_files_batched` (no reference counterpart) reconstructs
   `batch_size` files per ragged Vocos forward; same files, same bytes as
   `from_files_to_files`.
+- Audio at another rate is resampled on the device (pm_resample); the
+  reference resamples on the host (mels.py:174-).
 """
 from pathlib import Path
 
@@ -39,7 +41,7 @@ def from_audio(
 ):
     """Perform Mel spectrogram reconstruction: (1, N) audio -> (1, 256 T)"""
     device = _device(gpu, audio)
-    audio = resample(audio, sample_rate).to(device)
+    audio = resample(audio.to(device), sample_rate)
     spectrogram = promonet_amd.preprocess.spectrogram.from_audio(audio)
     return from_features(
         spectrogram,
@@ -86,7 +88,7 @@ def from_file(
 ):
     """Perform Mel reconstruction from audio file"""
     return from_audio(
-        promonet_amd.load.audio(audio_file),
+        promonet_amd.load.audio(audio_file, gpu=gpu),
         speaker=speaker,
         spectral_balance_ratio=spectral_balance_ratio,
         loudness_ratio=loudness_ratio,
@@ -149,8 +151,10 @@ def from_files_to_files_batched(
     the reference's one-file loop (mels.py:146-166); same files, same audio.
     Each utterance's spectrogram is taken on its own (`from_audio` reflect-pads
     its ends), the (513, T_b) spectrograms are zero-padded into one batch and
-    run as one ragged forward, and 256 T_b samples are written per file. Runs
-    in this process."""
+    run as one ragged forward, and 256 T_b samples are written per file. The
+    files of a batch are decoded on the host, grouped by native rate and
+    resampled one group per ragged launch, one row per channel (`_load_batch`).
+    Runs in this process."""
     count = len(audio_files)
     if count == 0:
         return
@@ -165,19 +169,20 @@ def from_files_to_files_batched(
         speakers = [0] * count
     model = _model(checkpoint, device)
     hop = promonet_amd.HOPSIZE
-    audio = [promonet_amd.load.audio(file) for file in audio_files]
-    frames = [item.shape[-1] // hop for item in audio]
+    decoded = [promonet_amd.load.decode(file) for file in audio_files]
+    frames = [_resampled_length(rate, data.shape[-1]) // hop
+              for rate, data in decoded]
     # (longest first: the engine's workspace is sized once, not per batch)
     order = sorted(range(count), key=lambda index: (-frames[index], index))
     for start in range(0, count, batch_size):
         group = order[start:start + batch_size]
+        audio = _load_batch([decoded[index] for index in group], device)
         spectrograms = torch.zeros(
             len(group), promonet_amd.NUM_FFT // 2 + 1, frames[group[0]],
             device=device)
         for row, index in enumerate(group):
             spectrograms[row, :, :frames[index]] = \
-                promonet_amd.preprocess.spectrogram.from_audio(
-                    audio[index].to(device))
+                promonet_amd.preprocess.spectrogram.from_audio(audio[row])
         size = (len(group),)
         with torch.inference_mode():
             reconstructed = model(
@@ -227,13 +232,55 @@ def _model(checkpoint, device):
 
 
 def resample(audio, sample_rate):
-    """Resample audio to the ProMoNet sample rate (promonet_amd.load.resample,
-    on the host)"""
+    """Resample audio to the ProMoNet sample rate (promonet_amd.load.resample:
+    a device tensor stays on the device, mels.py:174-)"""
     if int(sample_rate) == promonet_amd.SAMPLE_RATE:
         return audio
-    device = audio.device
     return promonet_amd.load.resample(
-        audio.cpu(), sample_rate, promonet_amd.SAMPLE_RATE).to(device)
+        audio, sample_rate, promonet_amd.SAMPLE_RATE)
+
+
+def _resampled_length(rate, samples):
+    """Samples of `samples` at `rate` once at the ProMoNet sample rate"""
+    if int(rate) == promonet_amd.SAMPLE_RATE:
+        return samples
+    orig, new, _, _ = promonet_amd.load.resample_geometry(
+        rate, promonet_amd.SAMPLE_RATE)
+    return (new * samples + orig - 1) // orig
+
+
+def _load_batch(decoded, device):
+    """`promonet_amd.load.audio(file, gpu)` of every (rate, (channels,
+    samples)) item of promonet_amd.load.decode, bit for bit: the items of one
+    native rate are zero-padded into one (rows, longest) upload, one row per
+    channel, and resampled in one ragged launch; an item at the ProMoNet rate
+    never reaches the resampler."""
+    result = [None] * len(decoded)
+    rates = {}
+    for index, (rate, data) in enumerate(decoded):
+        if int(rate) == promonet_amd.SAMPLE_RATE:
+            result[index] = data.mean(dim=0, keepdim=True).to(device)
+        else:
+            rates.setdefault(int(rate), []).append(index)
+    for rate, members in rates.items():
+        longest = max(decoded[index][1].shape[-1] for index in members)
+        rows = sum(decoded[index][1].shape[0] for index in members)
+        batch = torch.zeros(rows, longest)
+        lengths, row = [], 0
+        for index in members:
+            data = decoded[index][1]
+            batch[row:row + data.shape[0], :data.shape[-1]] = data
+            lengths += [data.shape[-1]] * data.shape[0]
+            row += data.shape[0]
+        resampled, out_lengths = promonet_amd.load.resample(
+            batch.to(device), rate, promonet_amd.SAMPLE_RATE, lengths=lengths)
+        row = 0
+        for index in members:
+            channels = decoded[index][1].shape[0]
+            result[index] = promonet_amd.load.mono(
+                resampled[row:row + channels, :out_lengths[row]])
+            row += channels
+    return result
 
 
 def _device(gpu, audio):

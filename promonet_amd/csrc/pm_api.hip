@@ -1,7 +1,8 @@
 // C ABI of libpromonet_hip.so (see include/promonet_hip.h) and the HiFi-GAN
 // engine behind it: weight folding / packing at load, workspace planning and
 // the per-forward launch sequence. Host C++; every kernel it launches is
-// hand-written HIP for gfx950 (pm_conv.h, pm_misc.h, pm_stft.h, pm_fft.h).
+// hand-written HIP for gfx950 (pm_conv.h, pm_misc.h, pm_stft.h, pm_fft.h,
+// pm_resample.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +21,7 @@
 #include "pm_stft.h"
 #include "pm_fft.h"
 #include "pm_fargan.h"
+#include "pm_resample.h"
 
 #define PM_VERSION 100
 
@@ -1887,6 +1889,66 @@ extern "C" int pm_stretch_grid(
         HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern),
                                       (int)smem));
     hipLaunchKernelGGL(kern, dim3(1), dim3(256), smem, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return PM_OK;
+}
+
+// Polyphase sinc resampling (pm_resample.h). Every argument is checked before
+// the first HIP call, so the checks answer on a machine without a GPU.
+extern "C" int pm_resample_tile(int orig, int new_, int width) {
+    if (orig < 1 || new_ < 1 || width < 1)
+        return fail(PM_EINVAL, "orig, new and width must be at least 1");
+    const int groups = pm_resample_groups(orig, new_, width);
+    if (groups < 1)
+        return fail(PM_EINVAL, "resampling ratio %d / %d: %d strides of a "
+                    "%lld-tap filter do not fit %d floats of LDS", orig, new_,
+                    RS_CHAINS, 2ll * width + orig, RS_LDS_FLOATS);
+    return RS_CHAINS * groups;
+}
+
+extern "C" int pm_resample(
+    const float* x, const int* lengths, const float* bank, float* out,
+    int rows, int n_in, long long x_stride, int orig, int new_, int width,
+    int n_out, long long out_stride, void* stream) {
+    if (rows < 0 || n_in < 0 || n_out < 0)
+        return fail(PM_EINVAL, "negative size");
+    if (orig < 1 || new_ < 1 || width < 1)
+        return fail(PM_EINVAL, "orig, new and width must be at least 1");
+    if (!x || !bank || !out) return fail(PM_EINVAL, "null argument");
+    if (n_out < ((long long)new_ * n_in + orig - 1) / orig)
+        return fail(PM_EINVAL, "n_out %d is below ceil(new n_in / orig) = %lld",
+                    n_out, ((long long)new_ * n_in + orig - 1) / orig);
+    if (x_stride < n_in || out_stride < n_out)
+        return fail(PM_EINVAL, "a row stride is below its row's length");
+    const int strides = pm_resample_tile(orig, new_, width);
+    if (strides < 0) return strides;
+    if (rows == 0 || n_out == 0) return PM_OK;
+    ResampleArgs a;
+    a.x = x; a.lengths = lengths; a.bank = bank; a.out = out;
+    a.x_stride = x_stride; a.out_stride = out_stride;
+    a.n_in = n_in; a.n_out = n_out; a.orig = orig; a.new_ = new_;
+    a.width = width; a.taps = 2 * width + orig;
+    a.groups = strides / RS_CHAINS;
+    const long long tile_out = (long long)strides * new_;
+    a.tiles = (int)((n_out + tile_out - 1) / tile_out);
+    if ((long long)a.tiles * rows > 0x7fffffffll)
+        return fail(PM_EINVAL, "too many workgroups (%d per row x %d rows)",
+                    a.tiles, rows);
+    const int phases = pm_resample_phases(new_);
+    a.half = (new_ + phases - 1) / phases;
+    const int V = orig % 4 == 0 ? 4 : orig % 2 == 0 ? 2 : 1;
+    void (*kern)(ResampleArgs);
+    if (phases == 1)
+        kern = V == 4 ? pm_resample_kernel<4, 1> : V == 2 ? pm_resample_kernel<2, 1>
+                                                          : pm_resample_kernel<1, 1>;
+    else
+        kern = V == 4 ? pm_resample_kernel<4, RS_PHASES>
+             : V == 2 ? pm_resample_kernel<2, RS_PHASES>
+                      : pm_resample_kernel<1, RS_PHASES>;
+    // at most RS_LDS_FLOATS floats (pm_resample.h): under the default limit
+    const size_t smem = ((size_t)(strides - 1) * orig + a.taps) * sizeof(float);
+    hipLaunchKernelGGL(kern, dim3(a.tiles * rows), dim3(RS_THREADS), smem,
+                       (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return PM_OK;
 }

@@ -20,7 +20,14 @@ def from_audio(
     loudness_bands=None,
     max_harmonics=3
 ):
-    """Preprocess audio (preprocess/core.py:17-126)."""
+    """Preprocess audio (preprocess/core.py:17-126). Audio at another
+    `sample_rate` is resampled to SAMPLE_RATE on the device first
+    (promonet_amd.load.resample) and every feature is taken from the
+    resampled audio, a device tensor (at SAMPLE_RATE penn and ppgs get the
+    caller's tensor as before). The reference hands `sample_rate` to penn and ppgs,
+    which resample for themselves, but feeds the audio at its ORIGINAL rate
+    to its loudness (core.py:55-61), whose frames then do not line up with
+    the other features: a quirk of the reference that is not mirrored here."""
     sample_rate = sample_rate or promonet_amd.SAMPLE_RATE
     features = list(features or promonet_amd.INPUT_FEATURES)
     if loudness_bands is None:
@@ -30,9 +37,9 @@ def from_audio(
             'promonet_amd preprocessing runs on an AMD GPU: pass gpu=<index>')
     device = torch.device(f'cuda:{gpu}')
     if sample_rate != promonet_amd.SAMPLE_RATE:
-        raise ValueError(
-            f'resample to {promonet_amd.SAMPLE_RATE} Hz first '
-            '(promonet_amd.load.audio does)')
+        audio = promonet_amd.load.resample(
+            audio.to(device), sample_rate, promonet_amd.SAMPLE_RATE)
+        sample_rate = promonet_amd.SAMPLE_RATE
     result = []
     if 'loudness' in features:
         result.append(promonet_amd.preprocess.loudness.from_audio(
@@ -77,9 +84,10 @@ def from_audio(
 
 
 def from_file(file, gpu=None, features=None, loudness_bands=None):
-    """preprocess/core.py:129-166"""
+    """preprocess/core.py:129-166; the file is resampled on the device
+    (load.audio(file, gpu)), so every feature gets a device tensor"""
     return from_audio(
-        promonet_amd.load.audio(file), gpu=gpu, features=features,
+        promonet_amd.load.audio(file, gpu=gpu), gpu=gpu, features=features,
         loudness_bands=loudness_bands)
 
 
