@@ -1,7 +1,13 @@
 """GPU parity, per kernel: HIP path (through the C ABI) vs the CPU oracle on
 the same seeded inputs. fp32 operand mode is exact-fp32 MFMA (only the
 summation order differs from ATen); 16-bit operands accumulate in fp32. The
-gates are set from measurement (TOL* below)."""
+gates are set from measurement (TOL* below).
+
+These tolerance tests guard conditioning on realistic values, three fused
+iterations and the ledger; indexing, rounding and saturation are guarded bit
+for bit by test_gpu_exact.py (integer inputs, sums exact in fp32). Three
+iterations are not in the exact set: 24.8 - 25.1 bits in bf16, over fp32's 24,
+and the f16 operands saturate; one (21.6 bits) and two (19 bits) are."""
 import ctypes
 
 import pytest
