@@ -513,6 +513,67 @@ int pm_resample(const float* x, const int* lengths, const float* bank,
                 int new_rate, int width, int n_out, long long out_stride,
                 void* stream);
 
+/* ---- Viterbi decoding: torbi.from_probabilities on the device -------------
+ * (the decoder of promonet/preprocess/harmonics.py:270-276 and of penn's
+ * pitch contour). With A = log transition, B = log observation (batch,
+ * frames, states), p = log initial, all fp32:
+ *   d_0[j] = B[0][j] + p[j];  m_t[j] = argmax_i d_{t-1}[i] + A[j][i];
+ *   d_t[j] = B[t][j] + (d_{t-1}[m] + A[j][m])
+ * each sum one fp32 add in that association; the last state is the argmax of
+ * d_{len-1}, earlier states follow the back-pointers; every tie goes to the
+ * lowest index, the tie of all -inf included. A[j][i] is the step from i to
+ * j. The transition is passed banded: table (3, states) int32 = lo, count and
+ * offset of every row j; band[offset_j + k] = A[j][lo_j + k], k < count_j,
+ * padded with -inf to a multiple of 4 floats (offset_j a multiple of 4);
+ * outside [lo_j, lo_j + count_j) A is -inf. A table entry that points outside
+ * the band or the states makes its row empty, never an access out of bounds.
+ * lengths: device int32 per row, clamped to [0, frames], read on the device
+ * only (NULL: every row has `frames`); out (batch, frames) int32 is zero from
+ * a row's length on. states <= 32767 (int16 back-pointers in the workspace,
+ * pm_viterbi_workspace bytes: 0 for invalid sizes) and two rows of scores
+ * must fit 64 KiB of LDS (states <= 8188). One workgroup per row;
+ * asynchronous, no allocation, capturable.                                  */
+size_t pm_viterbi_workspace(int batch, int frames, int states);
+int pm_viterbi(const float* observation, const int* lengths,
+               const float* band, long long band_floats, const int* table,
+               const float* initial, int* out, int batch, int frames,
+               int states, void* workspace, size_t workspace_bytes,
+               void* stream);
+
+/* ---- harmonic analysis: promonet/preprocess/harmonics.py ------------------
+ * pm_harmonics_highpass (:378-381): y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2]
+ * - a1 y[n-1] - a2 y[n-2] over each row's length (device int32 or NULL), zero
+ * state, clamped to [-1, 1] once at the end as torchaudio's lfilter does;
+ * zeros past the length.
+ * pm_harmonics_stft (:390-428): geometry (rows, 3) int32 = samples, frames
+ * and reflect padding of each row; Hann `window` (4096); twiddle (2048, 2) =
+ * (cos, -sin)(2 pi k / 4096); out (rows, frames, states) = sqrt(re^2 + im^2 +
+ * 1e-6) of bins [bin0, bin0 + states), frames-major, zeros past a row's
+ * frames.
+ * pm_harmonics_observation (:228-229, :252-264, :285-295): one decode round's
+ * log softmax per frame. f0 NULL: round 0, the bias 0.5 (states - s) added.
+ * Else masked to [searchsorted(frequencies, f0 low), searchsorted(
+ * frequencies, f0 high)), -inf outside; a frame with an empty mask, a NaN f0
+ * or past row_frames (device int32 or NULL) is all zeros and valid = 0.
+ * pm_harmonics_peaks (:199-212): the first `peaks` local maxima of each
+ * frame (scipy.signal.find_peaks without conditions) as frequencies, NaN
+ * beyond them; out (rows, peaks, frames).                                   */
+int pm_harmonics_highpass(const float* x, const int* lengths, float* y,
+                          int rows, int samples, long long x_stride,
+                          long long y_stride, float b0, float b1, float b2,
+                          float a1, float a2, void* stream);
+int pm_harmonics_stft(const float* x, const int* geometry,
+                      const float* window, const float* twiddle, float* out,
+                      int rows, long long x_stride, int frames, int states,
+                      int bin0, int hop, void* stream);
+int pm_harmonics_observation(const float* x, const float* f0,
+                             const float* frequencies, const int* row_frames,
+                             float* out, int* valid, int rows, int frames,
+                             int states, float low, float high, void* stream);
+int pm_harmonics_peaks(const float* x, const float* frequencies,
+                       const int* row_frames, float* out, int rows, int frames,
+                       int states, int peaks, void* stream);
+
 /* ---- Vocos mel vocoder engine: replaces promonet.model.Vocos --------------
  * (promonet/model/vocos.py, config/baselines/vocos.py MODEL = 'vocos').
  * conv_pre (k7) + cond, backbone embed (k7) + LayerNorm, `layers` fused

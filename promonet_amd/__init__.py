@@ -19,5 +19,6 @@ from . import load                                             # noqa: F401
 from . import model                                            # noqa: F401
 from . import preprocess                                       # noqa: F401
 from . import synthesize                                       # noqa: F401
+from . import viterbi                                          # noqa: F401
 from . import distributed                                      # noqa: F401
 from .patch import patch                                       # noqa: F401

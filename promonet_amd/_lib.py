@@ -112,6 +112,15 @@ SIGNATURES = {
     'pm_resample_tile': (_I, [_I, _I, _I]),
     'pm_resample': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_int64, _I, _I, _I, _I,
                          ctypes.c_int64, _P]),
+    'pm_viterbi_workspace': (_S, [_I, _I, _I]),
+    'pm_viterbi': (_I, [_P, _P, _P, ctypes.c_int64, _P, _P, _P, _I, _I, _I, _P,
+                        _S, _P]),
+    'pm_harmonics_highpass': (_I, [_P, _P, _P, _I, _I, ctypes.c_int64,
+                                   ctypes.c_int64] + [_F] * 5 + [_P]),
+    'pm_harmonics_stft': (_I, [_P] * 5 + [_I, ctypes.c_int64, _I, _I, _I, _I,
+                                          _P]),
+    'pm_harmonics_observation': (_I, [_P] * 6 + [_I, _I, _I, _F, _F, _P]),
+    'pm_harmonics_peaks': (_I, [_P] * 4 + [_I, _I, _I, _I, _P]),
     'pm_vocos_create': (_I, [_I] * 8 + [ctypes.POINTER(_P)]),
     'pm_vocos_destroy': (_I, [_P]),
     'pm_vocos_load_tensor': (_I, [_P, ctypes.c_char_p, _P, c_int64_p, _I, _P]),

@@ -26,6 +26,7 @@ WINDOW_SIZE = 1024
 AUGMENT_LOUDNESS = True
 AUGMENT_PITCH = True
 LOUDNESS_BANDS = 8
+MAX_HARMONICS = 3       # speech harmonics of preprocess.harmonics
 PITCH_EMBEDDING = True
 PITCH_BINS = 256
 PITCH_EMBEDDING_SIZE = 64

@@ -1,0 +1,315 @@
+// Stages of promonet_amd.preprocess.harmonics around the Viterbi decode
+// (promonet/preprocess/harmonics.py): the high-pass biquad (:378-381), the
+// 4096-point STFT magnitude (:390-428), the observation of a decode round
+// (:228-229, :252-264, :285-295) and peak picking (:199-212). NaN is a value
+// here (an unvoiced prior, a harmonic that does not exist): this translation
+// unit is built with -fhonor-nans.
+#pragma once
+#include <hip/hip_runtime.h>
+
+// ---------------------------------------------------------------------------
+// High-pass biquad, torchaudio.functional.highpass_biquad + lfilter's clamp:
+//   y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2]
+// with zero state before the row, clamped to [-1, 1] once at the end. One
+// workgroup a row, chunk by chunk: every thread computes the feed-forward part
+// v[n] of the chunk into LDS, thread 0 runs the two-term recursion over it
+// SERIALLY (one dependent fma a sample: the a2 term is folded in first, from
+// a value two samples old), and every thread stores the clamped chunk. The
+// poles sit at radius 0.987: the recursion cannot be cut to a short FIR, and
+// the serial form keeps fp32 rounding where the plain recursion has it.
+// ---------------------------------------------------------------------------
+#define HM_HP_THREADS 256
+#define HM_HP_CHUNK 2048
+
+struct HighpassArgs {
+    const float* x;
+    const int* lengths;     // NULL: every row has n samples
+    float* y;
+    long long x_stride, y_stride;
+    int n;
+    float b0, b1, b2, a1, a2;
+};
+
+__global__ __launch_bounds__(HM_HP_THREADS) void hm_highpass_kernel(
+    HighpassArgs a) {
+    __shared__ __attribute__((aligned(16))) float v[HM_HP_CHUNK];
+    __shared__ __attribute__((aligned(16))) float y[HM_HP_CHUNK];
+    const int t = threadIdx.x;
+    const int row = blockIdx.x;
+    int len = a.lengths ? a.lengths[row] : a.n;
+    len = len < 0 ? 0 : (len > a.n ? a.n : len);
+    const float* __restrict__ x = a.x + (long long)row * a.x_stride;
+    float* __restrict__ out = a.y + (long long)row * a.y_stride;
+    float y1 = 0.f, y2 = 0.f;       // thread 0 only: y[n-1], y[n-2]
+    for (int base = 0; base < len; base += HM_HP_CHUNK) {
+        const int count = len - base < HM_HP_CHUNK ? len - base : HM_HP_CHUNK;
+        for (int l = t; l < HM_HP_CHUNK; l += HM_HP_THREADS) {
+            const int n = base + l;
+            float s = 0.f;
+            if (l < count) {
+                const float x0 = x[n];
+                const float x1 = n >= 1 ? x[n - 1] : 0.f;
+                const float x2 = n >= 2 ? x[n - 2] : 0.f;
+                s = fmaf(a.b2, x2, fmaf(a.b1, x1, a.b0 * x0));
+            }
+            v[l] = s;
+        }
+        __syncthreads();
+        if (t == 0) {
+            const float na1 = -a.a1, na2 = -a.a2;
+            float4 in = *(const float4*)&v[0];
+            for (int l = 0; l < count; l += 4) {
+                const float4 now = in;
+                if (l + 4 < HM_HP_CHUNK) in = *(const float4*)&v[l + 4];
+                float4 o;
+                o.x = fmaf(na1, y1, fmaf(na2, y2, now.x));
+                o.y = fmaf(na1, o.x, fmaf(na2, y1, now.y));
+                o.z = fmaf(na1, o.y, fmaf(na2, o.x, now.z));
+                o.w = fmaf(na1, o.z, fmaf(na2, o.y, now.w));
+                *(float4*)&y[l] = o;
+                // (a chunk that ends inside this quad is the row's last: the
+                // state is not used again)
+                y2 = o.z; y1 = o.w;
+            }
+        }
+        __syncthreads();
+        for (int l = t; l < count; l += HM_HP_THREADS) {
+            const float s = y[l];
+            out[base + l] = s < -1.f ? -1.f : (s > 1.f ? 1.f : s);
+        }
+        // (v and y of the next chunk are written after the barrier above and
+        // the one inside it; y is read before the next recursion's barrier)
+    }
+    for (int n = len + t; n < a.n; n += HM_HP_THREADS) out[n] = 0.f;
+}
+
+// ---------------------------------------------------------------------------
+// STFT magnitude: reflect padding, Hann window over 4096, center = False,
+// sqrt(re^2 + im^2 + 1e-6), bins [bin0, 2049) of frame f of a row to
+// out[row][f][bin - bin0] (frames-major). One workgroup a frame. The real
+// 4096-point transform is a complex 2048-point radix-2 FFT of z[m] = x[2m] +
+// i x[2m+1] in LDS (16 KiB) and the split
+//   X[k] = (Z[k] + conj Z[2048-k]) / 2 - i W^k (Z[k] - conj Z[2048-k]) / 2,
+// W = exp(-2 pi i / 4096); `twiddle` holds W^k, k < 2048, rounded from
+// float64 on the host. Frames past a row's count are zeros.
+// ---------------------------------------------------------------------------
+#define HM_FFT 4096
+#define HM_HALF 2048
+#define HM_STFT_THREADS 256
+
+struct HarmonicStftArgs {
+    const float* x;         // (B, x_stride) high-passed audio
+    const int* geometry;    // (B, 3): samples, frames, reflect padding
+    const float* window;    // (4096)
+    const float* twiddle;   // (2048, 2): cos, -sin of 2 pi k / 4096
+    float* out;             // (B, T, S)
+    long long x_stride;
+    int T, S, bin0, hop;
+};
+
+__global__ __launch_bounds__(HM_STFT_THREADS) void hm_stft_kernel(
+    HarmonicStftArgs a) {
+    __shared__ float2 z[HM_HALF];
+    const int t = threadIdx.x;
+    const int f = blockIdx.x % a.T;
+    const int row = blockIdx.x / a.T;
+    const int len = a.geometry[3 * row];
+    const int frames = a.geometry[3 * row + 1];
+    const int pad = a.geometry[3 * row + 2];
+    float* __restrict__ out = a.out + ((long long)row * a.T + f) * a.S;
+    // (the host checks 0 <= pad < len; a row that fails it is left zero)
+    if (f >= frames || len < 1 || pad < 0 || pad >= len) {
+        for (int s = t; s < a.S; s += HM_STFT_THREADS) out[s] = 0.f;
+        return;
+    }
+    const float* __restrict__ x = a.x + (long long)row * a.x_stride;
+    const long long start = (long long)f * a.hop - pad;
+    for (int m = t; m < HM_HALF; m += HM_STFT_THREADS) {
+        float pair[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            long long i = start + 2 * m + h;
+            if (i < 0) i = -i;
+            if (i >= len) i = 2ll * (len - 1) - i;
+            // (one reflection reaches every frame the host admits)
+            i = i < 0 ? 0 : (i >= len ? len - 1 : i);
+            pair[h] = x[i] * a.window[2 * m + h];
+        }
+        z[__brev((unsigned)m) >> 21] = make_float2(pair[0], pair[1]);
+    }
+    __syncthreads();
+    const float2* __restrict__ w = (const float2*)a.twiddle;
+    for (int s = 0; s < 11; ++s) {
+        const int half = 1 << s;
+        for (int q = t; q < HM_HALF / 2; q += HM_STFT_THREADS) {
+            const int pos = q & (half - 1);
+            const int i0 = ((q >> s) << (s + 1)) + pos;
+            const int i1 = i0 + half;
+            const float2 tw = w[2 * (pos << (10 - s))];
+            const float2 u = z[i0], b = z[i1];
+            const float re = b.x * tw.x - b.y * tw.y;
+            const float im = b.x * tw.y + b.y * tw.x;
+            z[i0] = make_float2(u.x + re, u.y + im);
+            z[i1] = make_float2(u.x - re, u.y - im);
+        }
+        __syncthreads();
+    }
+    for (int s = t; s < a.S; s += HM_STFT_THREADS) {
+        const int k = s + a.bin0;                      // bin0 <= k <= 2048
+        const float2 zk = z[k & (HM_HALF - 1)];
+        const float2 zc = z[(HM_HALF - k) & (HM_HALF - 1)];
+        const float er = .5f * (zk.x + zc.x), ei = .5f * (zk.y - zc.y);
+        const float orr = .5f * (zk.y + zc.y), oi = -.5f * (zk.x - zc.x);
+        float2 tw = make_float2(-1.f, 0.f);            // W^2048
+        if (k < HM_HALF) tw = w[k];
+        const float re = er + (orr * tw.x - oi * tw.y);
+        const float im = ei + (orr * tw.y + oi * tw.x);
+        out[s] = sqrtf(re * re + im * im + 1e-6f);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Observation of one decode round, as log-probabilities: per frame
+//   round 0:   log softmax(x[s] + 0.5 (S - s))
+//   masked:    log softmax(x[s]) over lo <= s < hi, -inf elsewhere, with
+//              lo = searchsorted(frequencies, f0 * low), hi = ...(f0 * high)
+// softmax = exp(x - max) / sum in fp32, then logf: what underflows is -inf,
+// as in the reference. A frame whose mask is empty or whose f0 is NaN gets a
+// row of zeros (it contributes nothing to any path) and valid = 0; so does a
+// frame past the row's count. One workgroup a frame.
+// ---------------------------------------------------------------------------
+#define HM_OBS_THREADS 256
+
+struct ObservationArgs {
+    const float* x;             // (B, T, S) features
+    const float* f0;            // (B, T) or NULL: round 0
+    const float* frequencies;   // (S) ascending
+    const int* frames;          // (B) frames of each row, or NULL: T
+    float* out;                 // (B, T, S)
+    int* valid;                 // (B, T)
+    int T, S;
+    float low, high;
+};
+
+// torch.searchsorted(frequencies, v) (right = False): the first index whose
+// frequency is not below v; S for NaN, as every comparison fails
+__device__ __forceinline__ int hm_searchsorted(const float* __restrict__ f,
+                                               int S, float v) {
+    int lo = 0, hi = S;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (f[mid] >= v) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ float hm_block_reduce(float v, float* scratch,
+                                                 bool is_max) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float o = __shfl_xor(v, m, 64);
+        v = is_max ? fmaxf(v, o) : v + o;
+    }
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) scratch[wave] = v;
+    __syncthreads();
+    v = scratch[0];
+    for (int w = 1; w < HM_OBS_THREADS / 64; ++w)
+        v = is_max ? fmaxf(v, scratch[w]) : v + scratch[w];
+    return v;
+}
+
+__global__ __launch_bounds__(HM_OBS_THREADS) void hm_observation_kernel(
+    ObservationArgs a) {
+    __shared__ float scratch[HM_OBS_THREADS / 64];
+    const int t = threadIdx.x;
+    const int f = blockIdx.x % a.T;
+    const int row = blockIdx.x / a.T;
+    const long long frame = (long long)row * a.T + f;
+    const float* __restrict__ x = a.x + frame * a.S;
+    float* __restrict__ out = a.out + frame * a.S;
+    const int S = a.S;
+    int lo = 0, hi = S;
+    bool live = !a.frames || f < a.frames[row];
+    if (live && a.f0) {
+        const float f0 = a.f0[frame];
+        lo = hm_searchsorted(a.frequencies, S, f0 * a.low);
+        hi = hm_searchsorted(a.frequencies, S, f0 * a.high);
+        live = f0 == f0 && lo < hi;
+    }
+    if (!live) {
+        for (int s = t; s < S; s += HM_OBS_THREADS) out[s] = 0.f;
+        if (t == 0) a.valid[frame] = 0;
+        return;
+    }
+    const float ninf = -__builtin_inff();
+    const bool bias = !a.f0;
+    float top = ninf;
+    for (int s = lo + t; s < hi; s += HM_OBS_THREADS) {
+        const float v = bias ? x[s] + .5f * (float)(S - s) : x[s];
+        top = fmaxf(top, v);
+    }
+    top = hm_block_reduce(top, scratch, true);
+    float sum = 0.f;
+    for (int s = lo + t; s < hi; s += HM_OBS_THREADS) {
+        const float v = bias ? x[s] + .5f * (float)(S - s) : x[s];
+        sum += expf(v - top);
+    }
+    sum = hm_block_reduce(sum, scratch, false);
+    for (int s = t; s < S; s += HM_OBS_THREADS) {
+        float o = ninf;
+        if (s >= lo && s < hi) {
+            const float v = bias ? x[s] + .5f * (float)(S - s) : x[s];
+            o = logf(expf(v - top) / sum);
+        }
+        out[s] = o;
+    }
+    if (t == 0) a.valid[frame] = 1;
+}
+
+// ---------------------------------------------------------------------------
+// Peak picking: scipy.signal.find_peaks(frame) with no conditions (a sample
+// strictly above both neighbours; a plateau counts once, at (left + right) /
+// 2), the first `peaks` of them in ascending order as frequencies, NaN beyond
+// that. One thread a frame walks its S values; out is (B, peaks, T).
+// ---------------------------------------------------------------------------
+#define HM_PEAK_THREADS 64
+
+struct PeakArgs {
+    const float* x;             // (B, T, S)
+    const float* frequencies;   // (S)
+    const int* frames;          // (B) or NULL
+    float* out;                 // (B, peaks, T)
+    int B, T, S, peaks;
+};
+
+__global__ __launch_bounds__(HM_PEAK_THREADS) void hm_peak_kernel(PeakArgs a) {
+    const long long frame = (long long)blockIdx.x * HM_PEAK_THREADS + threadIdx.x;
+    if (frame >= (long long)a.B * a.T) return;
+    const int row = (int)(frame / a.T), f = (int)(frame % a.T);
+    const float* __restrict__ x = a.x + frame * a.S;
+    float* __restrict__ out = a.out + (long long)row * a.peaks * a.T + f;
+    const bool live = !a.frames || f < a.frames[row];
+    int found = 0;
+    if (live) {
+        const int last = a.S - 1;
+        int i = 1;
+        while (i < last && found < a.peaks) {
+            if (x[i - 1] < x[i]) {
+                int ahead = i + 1;
+                while (ahead < last && x[ahead] == x[i]) ++ahead;
+                if (x[ahead] < x[i]) {
+                    out[(long long)found * a.T] =
+                        a.frequencies[(i + ahead - 1) / 2];
+                    ++found;
+                    i = ahead;
+                }
+            }
+            ++i;
+        }
+    }
+    // (a frame past its row's count has no peaks either)
+    for (; found < a.peaks; ++found)
+        out[(long long)found * a.T] = __builtin_nanf("");
+}

@@ -1,3 +1,4 @@
 from .core import *
+from . import harmonics
 from . import loudness
 from . import spectrogram
