@@ -13,7 +13,8 @@ OBJ = build/obj
 LIB = promonet_amd/lib/libpromonet_hip.so
 OBJS = $(OBJ)/pm_api.o $(OBJ)/pm_conv_f16.o $(OBJ)/pm_conv_bf16.o $(OBJ)/pm_conv_f32.o \
        $(OBJ)/pm_conv_f16x3.o $(OBJ)/pm_conv_f16a2.o \
-       $(OBJ)/pm_conv_f16_mrf.o $(OBJ)/pm_conv_bf16_mrf.o $(OBJ)/pm_vocos.o $(OBJ)/pm_harmonics.o
+       $(OBJ)/pm_conv_f16_mrf.o $(OBJ)/pm_conv_bf16_mrf.o $(OBJ)/pm_vocos.o $(OBJ)/pm_harmonics.o \
+       $(OBJ)/pm_loss.o
 # the spectral head keeps torch.clip's NaN (a NaN magnitude stays NaN)
 $(OBJ)/pm_vocos.o: CXXFLAGS += -fhonor-nans
 # the harmonic contours carry NaN (an unvoiced prior, a harmonic that is absent)

@@ -574,6 +574,59 @@ int pm_harmonics_peaks(const float* x, const float* frequencies,
                        const int* row_frames, float* out, int rows, int frames,
                        int states, int peaks, void* stream);
 
+/* ---- training losses of the FARGAN configurations: promonet/train/loss.py --
+ * Spectral convergence (:61-150): s = sqrt(max(|STFT(x)|, 1e-7)) with
+ * torch.stft's center = True reflect padding (samples > fft_size / 2), the
+ * loss is sum |s_y - s_x| / sum s_y over the whole batch. fft_size is 2^a or
+ * 5 2^a in [64, 2560], 1 <= hop_size <= fft_size; frames = 1 + samples /
+ * hop_size, bins = fft_size / 2 + 1. window (fft_size) is the window already
+ * zero-padded to fft_size; twiddle (fft_size, 2) = (cos, -sin)(2 pi m /
+ * fft_size); both fp32, rounded from float64 by the caller.
+ * Stage 1, the transform: s (batch, bins, frames), or NULL. With `gradient`
+ * (batch, bins, frames, 2) it also writes upstream * X / (2 s |X|) where |X| >
+ * 1e-7 and 0 elsewhere, the gradient of a loss whose derivative by s is
+ * `upstream` (batch, bins, frames).
+ * Stage 2, the loss: sums (3) = S1 = sum |s_y - s_x|, S2 = sum s_y and S1 / S2,
+ * reduced in a fixed order (per-workgroup partials, one final pass). With
+ * with_gradient the workspace begins with G (batch, bins, frames, 2) =
+ * -sign(s_y - s_x) X / (2 s_x |X|) where |X| > 1e-7, 0 elsewhere: d S1 / d X.
+ * Stage 3, the adjoint: grad_x (batch, samples) = (or, with accumulate, +=)
+ * scale[0] * A(G), A the adjoint of x -> STFT(x): the inverse real transform
+ * of each frame with every bin counted once (the imaginary parts of bins 0
+ * and fft_size / 2 are ignored), the window, overlap-add in gather form and
+ * the fold of the two reflected margins. scale is a device scalar.
+ * No float atomics: every output is bit-identical from run to run. All
+ * asynchronous, no allocation, capturable; the workspace queries return 0 for
+ * sizes outside the limits.                                                 */
+size_t pm_sc_forward_workspace_bytes(int batch, int samples, int fft_size,
+                                     int hop_size, int with_gradient);
+size_t pm_sc_adjoint_workspace_bytes(int batch, int samples, int fft_size,
+                                     int hop_size);
+int pm_sc_stft(const float* x, const float* window, const float* twiddle,
+               const float* upstream, float* s, float* gradient, int batch,
+               int samples, int fft_size, int hop_size, void* stream);
+int pm_sc_forward(const float* x, const float* y, const float* window,
+                  const float* twiddle, float* sums, int batch, int samples,
+                  int fft_size, int hop_size, int with_gradient,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int pm_sc_adjoint(const float* gradient, const float* window,
+                  const float* twiddle, const float* scale, float* grad_x,
+                  int batch, int samples, int fft_size, int hop_size,
+                  int accumulate, void* workspace, size_t workspace_bytes,
+                  void* stream);
+/* signal (:158-162): out (1) = mean over rows of 1 - <p, t> with p, t the
+ * rows of y_pred, y_true over (1e-15 + their L2 norm). The forward leaves the
+ * rows' sums in the workspace; the backward reads them there and writes
+ * grad (rows, samples) = grad_out[0] * d out / d y_pred.                    */
+size_t pm_signal_loss_workspace_bytes(int rows);
+int pm_signal_loss(const float* y_true, const float* y_pred, float* out,
+                   int rows, int samples, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int pm_signal_loss_backward(const float* y_true, const float* y_pred,
+                            const float* grad_out, float* grad, int rows,
+                            int samples, const void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* ---- Vocos mel vocoder engine: replaces promonet.model.Vocos --------------
  * (promonet/model/vocos.py, config/baselines/vocos.py MODEL = 'vocos').
  * conv_pre (k7) + cond, backbone embed (k7) + LayerNorm, `layers` fused

@@ -16,6 +16,7 @@ from . import baseline                                         # noqa: F401
 from . import convert                                          # noqa: F401
 from . import edit                                             # noqa: F401
 from . import load                                             # noqa: F401
+from . import loss                                             # noqa: F401
 from . import model                                            # noqa: F401
 from . import preprocess                                       # noqa: F401
 from . import synthesize                                       # noqa: F401

@@ -121,6 +121,14 @@ SIGNATURES = {
                                           _P]),
     'pm_harmonics_observation': (_I, [_P] * 6 + [_I, _I, _I, _F, _F, _P]),
     'pm_harmonics_peaks': (_I, [_P] * 4 + [_I, _I, _I, _I, _P]),
+    'pm_sc_forward_workspace_bytes': (_S, [_I] * 5),
+    'pm_sc_adjoint_workspace_bytes': (_S, [_I] * 4),
+    'pm_sc_stft': (_I, [_P] * 6 + [_I] * 4 + [_P]),
+    'pm_sc_forward': (_I, [_P] * 5 + [_I] * 5 + [_P, _S, _P]),
+    'pm_sc_adjoint': (_I, [_P] * 5 + [_I] * 5 + [_P, _S, _P]),
+    'pm_signal_loss_workspace_bytes': (_S, [_I]),
+    'pm_signal_loss': (_I, [_P] * 3 + [_I, _I, _P, _S, _P]),
+    'pm_signal_loss_backward': (_I, [_P] * 4 + [_I, _I, _P, _S, _P]),
     'pm_vocos_create': (_I, [_I] * 8 + [ctypes.POINTER(_P)]),
     'pm_vocos_destroy': (_I, [_P]),
     'pm_vocos_load_tensor': (_I, [_P, ctypes.c_char_p, _P, c_int64_p, _I, _P]),
