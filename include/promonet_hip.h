@@ -488,6 +488,47 @@ int pm_loudness(const float* audio, const float* a_weights, float* out,
                 int batch, int samples, int bands, float min_db,
                 void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- loudness editing: promonet/preprocess/loudness.py:114-141, :179-193 ---
+ * pm_limit, the look-ahead limiter (:114-141), all fp32, every operation one
+ * rounding of its own (no fma), for n = 0 .. len + delay - 2 with x[n] = 0
+ * from len on, e[-1] = 0, g[-1] = 1:
+ *   e[n] = max(|x[n]|, e[n-1] release)
+ *   t[n] = e[n] > threshold ? (1 / e[n]) threshold : 1
+ *   g[n] = g[n-1] attack + t[n] attack_complement
+ *   out[j] = x[j] g[j + delay - 1]
+ * attack_complement is the fp32 rounding of 1 - attack_coef taken in double,
+ * as the reference's Python arithmetic has it. x: `rows` rows of `samples`,
+ * x_stride floats apart; FINITE input is a precondition. lengths: device int32
+ * per row, clamped to [0, samples], read on the device only (NULL: full rows);
+ * out is exact zero from a row's length on and must not overlap x. gain: NULL,
+ * or rows of samples + delay - 1 floats that receive g[0 .. len + delay - 2]
+ * (zero beyond). One workgroup per row, in tiles of pm_limit_tile's `tile`
+ * steps, a lane taking `chunk` of them: exact whatever the tiling, see
+ * pm_limit.h. The workspace (pm_limit_workspace_bytes; 0 for rows < 1)
+ * receives 4 int32 per row: envelope steps and gain steps walked serially,
+ * chunks walked, tiles skipped as a whole. 1 <= delay, the coefficients inside
+ * (0, 1), threshold > 0. Asynchronous, no allocation, capturable; argument
+ * errors are reported before any GPU call.
+ * pm_loudness_shift (:179-193): out = x gain, gain = 2^(db / 10) per frame,
+ * interpolated linearly to the row's samples as torch's interpolate(mode =
+ * 'linear', align_corners = False): src = max(0, (n + .5) F / N - .5), split
+ * into index and weight in integers. Per row N = lengths[row] (clamped to
+ * [0, samples]) and F = frame_lengths[row] (clamped to [1, frames]), device
+ * int32 or NULL for `samples` and `frames`; frames == 1 is the scalar shift.
+ * db: rows of `frames`, db_stride apart (0: one contour for every row).
+ * Zeros from a row's length on; out may be x.                                */
+int pm_limit_tile(int* chunk, int* tile);
+size_t pm_limit_workspace_bytes(int rows);
+int pm_limit(const float* x, const int* lengths, float* out, float* gain,
+             int rows, int samples, long long x_stride, long long out_stride,
+             int delay, float attack, float attack_complement, float release,
+             float threshold, void* workspace, size_t workspace_bytes,
+             void* stream);
+int pm_loudness_shift(const float* x, const float* db, const int* lengths,
+                      const int* frame_lengths, float* out, int rows,
+                      int samples, long long x_stride, int frames,
+                      long long db_stride, long long out_stride, void* stream);
+
 /* ---- resampling: torchaudio.functional.resample on the device -------------
  * Replaces the host resampler of promonet/load.py:16-28 (load.audio) and
  * promonet/baseline/mels.py:174- (mels.resample): torchaudio's

@@ -109,6 +109,12 @@ SIGNATURES = {
     'pm_linear_to_mel_backward': (_I, [_P] * 5 + [_I] * 5 + [_F, _P]),
     'pm_loudness_scratch_bytes': (_S, [_I, _I]),
     'pm_loudness': (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _S, _P]),
+    'pm_limit_tile': (_I, [ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    'pm_limit_workspace_bytes': (_S, [_I]),
+    'pm_limit': (_I, [_P] * 4 + [_I, _I, ctypes.c_int64, ctypes.c_int64, _I] +
+                 [_F] * 4 + [_P, _S, _P]),
+    'pm_loudness_shift': (_I, [_P] * 5 + [_I, _I, ctypes.c_int64, _I,
+                                          ctypes.c_int64, ctypes.c_int64, _P]),
     'pm_resample_tile': (_I, [_I, _I, _I]),
     'pm_resample': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_int64, _I, _I, _I, _I,
                          ctypes.c_int64, _P]),

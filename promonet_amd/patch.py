@@ -3,7 +3,8 @@ reference package, the literal drop-in.
 
 After patching, `promonet.synthesize.from_features(..., gpu=N)`,
 `promonet.model.Generator()` and `promonet.preprocess.spectrogram.from_audio`
-/ `promonet.preprocess.loudness.from_audio` run on libpromonet_hip.so, and,
+/ `promonet.preprocess.loudness.from_audio` / `limit` / `scale` / `shift` run on
+libpromonet_hip.so, and,
 where the target has them, `promonet.model.Vocos` / `MelGenerator` and
 `promonet.baseline.mels.*`.
 """
@@ -37,6 +38,12 @@ def patch(promonet):
         promonet_amd.preprocess.spectrogram.linear_to_mel
     promonet.preprocess.loudness.from_audio = \
         promonet_amd.preprocess.loudness.from_audio
+    # the editing utilities, where the target has them (every release of the
+    # reference does; a stand-in of its layout may not)
+    for name in ('limit', 'scale', 'shift'):
+        if hasattr(promonet.preprocess.loudness, name):
+            setattr(promonet.preprocess.loudness, name,
+                    getattr(promonet_amd.preprocess.loudness, name))
     # the mel vocoder, only where the target has it
     for name in ('Vocos', 'MelGenerator'):
         if hasattr(promonet.model, name):
