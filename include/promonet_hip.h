@@ -717,6 +717,19 @@ int pm_convnext_block_cl(int dtype, const float* x, float* y,
                          int frames, int channels, int hidden,
                          void* workspace, size_t workspace_bytes,
                          void* stream);
+/* The contraction of conv_pre, embed and head.out on its own (a test entry):
+ * out (B, T, N) = conv1d(x, w, padding = taps / 2) + bias (+ gbias[b], or
+ * gbias[0] when gbatch is 1; NULL: none), out channels-last. x (B, T, K)
+ * channels-last or, channels_first (taps 7 only), (B, K, T); w (N, K, taps)
+ * fp32, packed to the operand type of `dtype` on every call; taps 1 or 7,
+ * K a multiple of 16. workspace: pm_vocos_gemm_workspace_bytes.             */
+size_t pm_vocos_gemm_workspace_bytes(int dtype, int taps, int in_channels,
+                                     int out_channels);
+int pm_vocos_gemm_cl(int dtype, int taps, int channels_first, const float* x,
+                     const float* w, const float* bias, const float* gbias,
+                     int gbatch, float* out, int batch, int frames,
+                     int in_channels, int out_channels, void* workspace,
+                     size_t workspace_bytes, void* stream);
 /* ISTFTHead (vocos.py:154-172): x (B, T, 512) channels-last, w (1026, 512),
  * bias (1026), window (1024) -> audio (B, 256 T).                          */
 size_t pm_vocos_head_workspace_bytes(int dtype, int batch, int frames);

@@ -146,6 +146,9 @@ SIGNATURES = {
         _I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _S, _P]),
     'pm_convnext_block_workspace_bytes': (_S, [_I, _I, _I]),
     'pm_convnext_block_cl': (_I, [_I] + [_P] * 11 + [_I] * 4 + [_P, _S, _P]),
+    'pm_vocos_gemm_workspace_bytes': (_S, [_I, _I, _I, _I]),
+    'pm_vocos_gemm_cl': (_I, [_I] * 3 + [_P] * 4 + [_I, _P] + [_I] * 4
+                         + [_P, _S, _P]),
     'pm_vocos_head_workspace_bytes': (_S, [_I, _I, _I]),
     'pm_vocos_head': (_I, [_I] + [_P] * 5 + [_I, _I, _P, _S, _P]),
     'pm_istft_workspace_bytes': (_S, [_I, _I]),

@@ -527,6 +527,54 @@ extern "C" int pm_convnext_block_cl(
     return PM_OK;
 }
 
+extern "C" size_t pm_vocos_gemm_workspace_bytes(int dtype, int taps,
+                                                int in_channels,
+                                                int out_channels) {
+    if (!known_dtype(dtype) || (taps != 1 && taps != 7) || in_channels < 1 ||
+        out_channels < 1)
+        return 0;
+    return packed_bytes(dtype, out_channels, in_channels, taps);
+}
+
+extern "C" int pm_vocos_gemm_cl(int dtype, int taps, int channels_first,
+                                const float* x, const float* w,
+                                const float* bias, const float* gbias,
+                                int gbatch, float* out, int batch, int frames,
+                                int in_channels, int out_channels,
+                                void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    if (!x || !w || !bias || !out) return vfail(PM_EINVAL, "null argument");
+    if (!known_dtype(dtype))
+        return vfail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
+    // (the instantiations of gemm(): k7 in both layouts, k1 channels-last)
+    if (taps != 1 && taps != 7)
+        return vfail(PM_EINVAL, "taps must be 1 or 7, got %d", taps);
+    if (channels_first && taps != 7)
+        return vfail(PM_EINVAL, "channels-first input needs taps 7");
+    if (batch < 1 || frames < 1)
+        return vfail(PM_EINVAL, "batch and frames must be positive");
+    if (in_channels < 16 || in_channels % 16)
+        return vfail(PM_EINVAL,
+                     "input channels must be a positive multiple of 16, got %d",
+                     in_channels);
+    if (out_channels < 1)
+        return vfail(PM_EINVAL, "output channels must be positive, got %d",
+                     out_channels);
+    if (gbias && gbatch != 1 && gbatch != batch)
+        return vfail(PM_EINVAL, "global batch must be 1 or batch");
+    if (!workspace || workspace_bytes < pm_vocos_gemm_workspace_bytes(
+            dtype, taps, in_channels, out_channels))
+        return vfail(PM_ENOMEM, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    VC_TRY(pack(dtype, w, workspace, out_channels, in_channels, taps, s));
+    VocosGemmArgs g = {};
+    g.x = x; g.w = workspace; g.bias = bias; g.gbias = gbias;
+    g.gbatch = gbatch; g.out = out; g.B = batch; g.T = frames;
+    g.K = in_channels; g.N = out_channels; g.ldo = out_channels;
+    VC_TRY(gemm(dtype, taps, channels_first != 0, g, s));
+    return PM_OK;
+}
+
 extern "C" size_t pm_vocos_head_workspace_bytes(int dtype, int batch,
                                                 int frames) {
     if (!known_dtype(dtype) || batch < 1 || frames < 1) return 0;
