@@ -14,11 +14,15 @@ LIB = promonet_amd/lib/libpromonet_hip.so
 OBJS = $(OBJ)/pm_api.o $(OBJ)/pm_conv_f16.o $(OBJ)/pm_conv_bf16.o $(OBJ)/pm_conv_f32.o \
        $(OBJ)/pm_conv_f16x3.o $(OBJ)/pm_conv_f16a2.o \
        $(OBJ)/pm_conv_f16_mrf.o $(OBJ)/pm_conv_bf16_mrf.o $(OBJ)/pm_vocos.o $(OBJ)/pm_harmonics.o \
-       $(OBJ)/pm_loss.o $(OBJ)/pm_limit.o
+       $(OBJ)/pm_loss.o $(OBJ)/pm_limit.o $(OBJ)/pm_lpc.o
 # the spectral head keeps torch.clip's NaN (a NaN magnitude stays NaN)
 $(OBJ)/pm_vocos.o: CXXFLAGS += -fhonor-nans
 # the harmonic contours carry NaN (an unvoiced prior, a harmonic that is absent)
 $(OBJ)/pm_harmonics.o: CXXFLAGS += -fhonor-nans
+# NaN audio gives NaN LPC features; the lattice steps contract to fma. No SLP
+# vectorisation: packed fp32 pairs break on the one-element shift of every
+# order and cost 82 moves an order to re-pair (pm_lpc.h)
+$(OBJ)/pm_lpc.o: CXXFLAGS += -fhonor-nans -fno-slp-vectorize
 # the limiter is bit for bit the reference's: every product and sum rounds on
 # its own (pm_limit.h)
 $(OBJ)/pm_limit.o: CXXFLAGS += -ffp-contract=off

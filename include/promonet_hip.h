@@ -615,6 +615,30 @@ int pm_harmonics_peaks(const float* x, const float* frequencies,
                        const int* row_frames, float* out, int rows, int frames,
                        int states, int peaks, void* stream);
 
+/* ---- LPC features: promonet/preprocess/harmonics.py:305-330 ---------------
+ * lpc_coefficients on the device. audio: `rows` rows of up to `samples`
+ * samples, `stride` floats apart; lengths: device int32 per row, clamped to
+ * [0, samples] on the device and never read on the host (NULL: every row has
+ * `samples`). Frame t of a row of len samples is samples [256 t - 384,
+ * 256 t + 640) of it, zero outside [0, len), times `window` (1024 floats,
+ * 16-byte aligned); a row has max(0, (len - 256) / 256 + 1) frames. Per frame
+ * Burg's predictor of `order` (1 to 32; librosa.lpc restated, parity
+ * unpinned), its denominator recomputed as sum(f^2 + b^2) every order, and
+ *   features[row][t][k] = -log10 |sum_j a[j] e^(-i pi j k / 512)|, k < 512,
+ * with table (1024, 4) = the float64 (cos, sin)(2 pi m / 1024) split by the
+ * caller into float heads (cos, sin) and float tails (cos, sin), 16-byte
+ * aligned: the response is summed in float64. features (rows, frames, 512);
+ * coefficients (rows, frames, order + 1) = a, or NULL. A silent frame gives
+ * a = [1, 0, ...] and features +0; frames from a row's count on give zeros in
+ * both. One wave a frame: a frame's bits depend on its samples alone. At most
+ * 2^32 - 1 threads a launch (67 108 860 frames). Asynchronous, no allocation,
+ * no workspace, no atomics, capturable; argument errors are reported before
+ * any GPU call.                                                             */
+int pm_harmonics_lpc(const float* audio, const int* lengths,
+                     const float* window, const float* table, float* features,
+                     float* coefficients, int rows, long long stride,
+                     int samples, int frames, int order, void* stream);
+
 /* ---- training losses of the FARGAN configurations: promonet/train/loss.py --
  * Spectral convergence (:61-150): s = sqrt(max(|STFT(x)|, 1e-7)) with
  * torch.stft's center = True reflect padding (samples > fft_size / 2), the

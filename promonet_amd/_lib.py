@@ -127,6 +127,7 @@ SIGNATURES = {
                                           _P]),
     'pm_harmonics_observation': (_I, [_P] * 6 + [_I, _I, _I, _F, _F, _P]),
     'pm_harmonics_peaks': (_I, [_P] * 4 + [_I, _I, _I, _I, _P]),
+    'pm_harmonics_lpc': (_I, [_P] * 6 + [_I, ctypes.c_int64, _I, _I, _I, _P]),
     'pm_sc_forward_workspace_bytes': (_S, [_I] * 5),
     'pm_sc_adjoint_workspace_bytes': (_S, [_I] * 4),
     'pm_sc_stft': (_I, [_P] * 6 + [_I] * 4 + [_P]),

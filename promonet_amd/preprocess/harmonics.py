@@ -1,11 +1,15 @@
 """Speech harmonic contours on the device.
 
-API of `promonet.preprocess.harmonics` (promonet/preprocess/harmonics.py),
-its default path: `features='stft'` and the 'viterbi' (or 'peak') decoder. A
-high-pass biquad, a 4096-point STFT magnitude, one softmax and one Viterbi
-decode per harmonic; every stage is a HIP kernel (pm_harmonics.h,
-pm_viterbi.h). `features='lpc'` needs librosa and `'posteriorgram'` needs
-penn: they raise.
+API of `promonet.preprocess.harmonics` (promonet/preprocess/harmonics.py):
+`features='stft'` (the default) or `'lpc'`, and the 'viterbi' (or 'peak')
+decoder. 'stft': a high-pass biquad, a 4096-point STFT magnitude, one softmax
+and one Viterbi decode per harmonic. 'lpc' (`lpc_coefficients`, :305-330):
+Hamming-windowed 1024-sample frames, Burg's order-24 predictor and log10 of
+the all-pole response at 512 frequencies, one kernel, one wave a frame: the
+spectral envelope, whose peaks are the formants. Every stage is a HIP kernel
+(pm_harmonics.h, pm_lpc.h, pm_viterbi.h). `'posteriorgram'` needs penn: it
+raises; so does 'lpc' for a tensor that is not on a device (the reference's
+host path needs librosa).
 
 Beyond the reference: `audio` may be a batch (B, samples), ragged with
 `lengths=`; each row then equals its stand-alone call bit for bit.
@@ -17,9 +21,21 @@ Where this differs from the reference, on purpose:
 - a frame whose mask is empty or whose f0 is NaN gives NaN in the
   reference's softmax and an undefined path. Here its observation is a row
   of zeros (log-probabilities: it adds nothing to any path) and its output
-  is NaN for that harmonic. Frames past a row's end are NaN too.
-Parity with torchaudio (the biquad) and torbi (the decoder) is unpinned:
-neither is a dependency. tests/harmonics_oracle.py restates both.
+  is NaN for that harmonic. Frames past a row's end are NaN too;
+- 'lpc' with the 'viterbi' decoder decodes bins 1 to 511 only. The
+  reference's frequencies start at 0 Hz, log2 gives -inf, cdist gives NaN at
+  [0, 0] and the column-wise normalisation spreads it over all of column 0:
+  its decoder's transition matrix holds NaN and the path is undefined.
+  Without bin 0 the matrix is finite (band of at most 167 of 511 states).
+  The 'peak' decoder and `return_features` keep all 512 bins: bin 0 can
+  never be a peak;
+- Burg's denominator is recomputed as sum(f^2 + b^2) at every order, not
+  updated as librosa does: equal in exact arithmetic, and the update cancels
+  in fp32. The target is the float64 recursion.
+Parity with torchaudio (the biquad), torbi (the decoder) and librosa (Burg's
+recursion, `librosa.lpc`) is unpinned: none is a dependency.
+tests/harmonics_oracle.py and tests/lpc_oracle.py restate them from their
+published behaviour.
 """
 import math
 
@@ -60,7 +76,8 @@ def from_audio(
             Optional pitch contour prior: (1, frames) / (frames,), or
             (batch, frames). It becomes harmonic 0.
         features
-            'stft'. ('lpc' and 'posteriorgram' raise.)
+            'stft' or 'lpc'. ('posteriorgram' raises; so does 'lpc' for a
+            tensor that is not on a device when `gpu` is None.)
         decoder
             One of ['peak', 'viterbi']
         max_harmonics
@@ -78,15 +95,16 @@ def from_audio(
         batch > 1 or with `lengths`. With return_features also the features
         (states, frames) / (batch, states, frames).
     """
-    if features == 'lpc':
+    if features == 'lpc' and gpu is None and \
+            isinstance(audio, torch.Tensor) and not audio.is_cuda:
         raise ValueError(
-            "features='lpc' needs the third-party `librosa` package: only "
-            "'stft' runs here")
+            "features='lpc' on the CPU needs the third-party `librosa` "
+            "package; pass a device tensor or gpu=")
     if features == 'posteriorgram':
         raise ValueError(
             "features='posteriorgram' needs the third-party `penn` package: "
-            "only 'stft' runs here")
-    if features != 'stft':
+            "only 'stft' and 'lpc' run here")
+    if features not in ('stft', 'lpc'):
         raise ValueError(f'unknown features {features!r}')
     if decoder not in ('peak', 'viterbi'):
         raise ValueError(f'unknown decoder {decoder!r}')
@@ -97,8 +115,12 @@ def from_audio(
         raise ValueError(
             f'audio must be (batch, samples), got {tuple(audio.shape)}')
     single = audio.shape[0] == 1 and lengths is None
-    frames, frequencies, counts = stft(
-        audio, sample_rate, lengths=lengths, _counts=True)
+    if features == 'lpc':
+        frames, frequencies, counts = lpc_coefficients(
+            audio, sample_rate, lengths=lengths, _counts=True)
+    else:
+        frames, frequencies, counts = stft(
+            audio, sample_rate, lengths=lengths, _counts=True)
     if decoder == 'peak':
         harmonics = peak_pick(
             frames, frequencies, max_harmonics, lengths=counts)
@@ -107,8 +129,13 @@ def from_audio(
         if pitch is not None:
             pitch = _on_device(pitch, audio.device.index).to(torch.float32)
             pitch = pitch.reshape(-1, pitch.shape[-1])
+        decoded, states = frames, frequencies
+        if features == 'lpc':
+            # 0 Hz makes the decoder's transition matrix NaN: see above
+            decoded = frames[..., 1:]
+            states = _lpc_tables(frames.device)[1]
         harmonics, debug = viterbi(
-            frames, frequencies, pitch=pitch, max_harmonics=max_harmonics,
+            decoded, states, pitch=pitch, max_harmonics=max_harmonics,
             lengths=counts, _debug=True)
     result = (harmonics[0] if single else harmonics,)
     if return_features:
@@ -125,7 +152,8 @@ def from_file(
     pitch_file=None,
     max_harmonics=None,
     return_features=False,
-    gpu=None
+    gpu=None,
+    features='stft'
 ):
     """Compute speech harmonic contours from audio file
     (harmonics.py:80-112)"""
@@ -133,6 +161,7 @@ def from_file(
     return from_audio(
         promonet_amd.load.audio(file, gpu=gpu),
         pitch=pitch,
+        features=features,
         max_harmonics=max_harmonics,
         return_features=return_features,
         gpu=gpu)
@@ -144,7 +173,8 @@ def from_file_to_file(
     pitch_file=None,
     output_feature_file=None,
     max_harmonics=None,
-    gpu=None
+    gpu=None,
+    features='stft'
 ):
     """Compute speech harmonic contours from audio file and save
     (harmonics.py:115-148)"""
@@ -153,7 +183,8 @@ def from_file_to_file(
         pitch_file=pitch_file,
         max_harmonics=max_harmonics,
         return_features=output_feature_file is not None,
-        gpu=gpu)
+        gpu=gpu,
+        features=features)
     if output_feature_file is not None:
         torch.save(result[-1].cpu(), output_feature_file)
         result = result[0]
@@ -509,6 +540,141 @@ def stft(
     if _counts:
         return frames, frequencies, counts
     return (frames[0] if single else frames), frequencies
+
+
+LPC_BINS = 512
+
+_lpc = {}
+
+
+def _lpc_tables(device):
+    """(frequencies (512), frequencies[1:], Hamming window (1024), table
+    (1024, 4) = the float64 (cos, sin)(2 pi m / 1024) as float heads and
+    float tails) on `device`, built once"""
+    key = str(device)
+    if key not in _lpc:
+        # Real FFT frequencies in Hz (:320-322): spaced rate / 1023
+        frequencies = promonet_amd.SAMPLE_RATE * torch.linspace(
+            0., 1., promonet_amd.NUM_FFT)
+        frequencies = frequencies[0:len(frequencies) // 2]
+        angle = 2. * math.pi * torch.arange(
+            promonet_amd.WINDOW_SIZE, dtype=torch.float64
+        ) / promonet_amd.WINDOW_SIZE
+        exact = torch.stack([angle.cos(), angle.sin()], dim=1)
+        head = exact.to(torch.float32)
+        tail = (exact - head.to(torch.float64)).to(torch.float32)
+        table = torch.cat([head, tail], dim=1)
+        _lpc[key] = (
+            frequencies.contiguous().to(device),
+            frequencies[1:].contiguous().to(device),
+            torch.hamming_window(
+                promonet_amd.WINDOW_SIZE, dtype=torch.float32).to(device),
+            table.contiguous().to(device))
+    return _lpc[key]
+
+
+def lpc_frames(samples):
+    """Frames of `samples` samples (an int or an integer tensor): the unfold
+    of the zero-padded audio (:307-315)"""
+    padding = promonet_amd.WINDOW_SIZE - promonet_amd.HOPSIZE
+    if isinstance(samples, torch.Tensor):
+        count = (samples + (padding - promonet_amd.WINDOW_SIZE)).div(
+            promonet_amd.HOPSIZE, rounding_mode='floor') + 1
+        return count.clamp(min=0)
+    return max(
+        0,
+        (samples + padding - promonet_amd.WINDOW_SIZE) // promonet_amd.HOPSIZE
+        + 1)
+
+
+def lpc(audio, lengths=None, order=None, return_coefficients=False):
+    """One launch of pm_harmonics_lpc on device audio (B, samples) at
+    SAMPLE_RATE: log10 |H| (B, T, 512) of Burg's predictor of `order`
+    (default SAMPLE_RATE / 1000 + 2 = 24) of every Hamming-windowed frame,
+    T = lpc_frames(samples), and with return_coefficients the predictors
+    (B, T, order + 1). lengths: device int32 (B) or None; it is read on the
+    device only, frames past a row's count are zeros, and the launch can be
+    captured in a graph."""
+    _lib.require_gpu(audio)
+    if audio.ndim != 2:
+        raise ValueError(
+            f'audio must be (batch, samples), got {tuple(audio.shape)}')
+    if order is None:
+        order = int(promonet_amd.SAMPLE_RATE / 1000 + 2)
+    x = audio.to(torch.float32)
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    device = x.device
+    rows, samples = x.shape
+    if lengths is not None and lengths.numel() != rows:
+        raise ValueError(f'{lengths.numel()} lengths for {rows} rows')
+    count = lpc_frames(samples)
+    _, _, window, table = _lpc_tables(device)
+    out = torch.empty(rows, count, LPC_BINS, device=device)
+    coefficients = None
+    if return_coefficients:
+        coefficients = torch.empty(rows, count, order + 1, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().pm_harmonics_lpc(
+            x.data_ptr(), _lib.ptr(lengths, torch.int32), _lib.ptr(window),
+            _lib.ptr(table), _lib.ptr(out), _lib.ptr(coefficients), rows,
+            x.stride(0) if rows > 1 else samples, samples, count, order,
+            _lib.stream()))
+    return (out, coefficients) if return_coefficients else out
+
+
+def lpc_coefficients(
+    audio,
+    sample_rate=None,
+    lengths=None,
+    gpu=None,
+    return_coefficients=False,
+    _counts=False
+):
+    """Compute linear predictive coding features (harmonics.py:305-330):
+    log10 of the all-pole response of Burg's order-24 predictor of every
+    frame, and the frequencies (512,) it is evaluated at. audio (1, samples)
+    -> frames (T, 512); (B, samples), or ragged with `lengths` (a list or a
+    tensor, samples of each row, never read back) -> (B, T, 512), zeros past
+    a row's frames. Audio at another `sample_rate` is resampled to
+    SAMPLE_RATE first, this module's convention: the order is always 24.
+    With return_coefficients also the predictors (..., T, 25). Burg's
+    recursion restates librosa.lpc; parity with librosa is unpinned."""
+    sample_rate = int(sample_rate or promonet_amd.SAMPLE_RATE)
+    audio = _on_device(audio, gpu).to(torch.float32)
+    if audio.ndim != 2:
+        raise ValueError(
+            f'audio must be (batch, samples), got {tuple(audio.shape)}')
+    device = audio.device
+    rows = audio.shape[0]
+    single = rows == 1 and lengths is None
+    if lengths is not None:
+        lengths = _row_counts(lengths, rows, device)
+    if sample_rate != promonet_amd.SAMPLE_RATE:
+        if lengths is None:
+            audio = promonet_amd.load.resample(
+                audio, sample_rate, promonet_amd.SAMPLE_RATE)
+        else:
+            audio, lengths = promonet_amd.load.resample(
+                audio, sample_rate, promonet_amd.SAMPLE_RATE, lengths=lengths)
+            lengths = lengths.to(torch.int32)
+    result = lpc(audio, lengths, return_coefficients=return_coefficients)
+    frames, coefficients = result if return_coefficients else (result, None)
+    frequencies = _lpc_tables(device)[0]
+    if _counts:
+        samples = audio.shape[-1]
+        if lengths is None:
+            counts = torch.full(
+                (rows,), lpc_frames(samples), dtype=torch.int32, device=device)
+        else:
+            counts = lpc_frames(lengths.clamp(0, samples)).to(torch.int32)
+        return frames, frequencies, counts
+    if single:
+        frames = frames[0]
+        coefficients = coefficients[0] if return_coefficients else None
+    if return_coefficients:
+        return frames, frequencies, coefficients
+    return frames, frequencies
 
 
 ###############################################################################
