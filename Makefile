@@ -14,7 +14,7 @@ LIB = promonet_amd/lib/libpromonet_hip.so
 OBJS = $(OBJ)/pm_api.o $(OBJ)/pm_conv_f16.o $(OBJ)/pm_conv_bf16.o $(OBJ)/pm_conv_f32.o \
        $(OBJ)/pm_conv_f16x3.o $(OBJ)/pm_conv_f16a2.o \
        $(OBJ)/pm_conv_f16_mrf.o $(OBJ)/pm_conv_bf16_mrf.o $(OBJ)/pm_vocos.o $(OBJ)/pm_harmonics.o \
-       $(OBJ)/pm_loss.o $(OBJ)/pm_limit.o $(OBJ)/pm_lpc.o
+       $(OBJ)/pm_loss.o $(OBJ)/pm_limit.o $(OBJ)/pm_lpc.o $(OBJ)/pm_adv.o
 # the spectral head keeps torch.clip's NaN (a NaN magnitude stays NaN)
 $(OBJ)/pm_vocos.o: CXXFLAGS += -fhonor-nans
 # the harmonic contours carry NaN (an unvoiced prior, a harmonic that is absent)
@@ -26,6 +26,9 @@ $(OBJ)/pm_lpc.o: CXXFLAGS += -fhonor-nans -fno-slp-vectorize
 # the limiter is bit for bit the reference's: every product and sum rounds on
 # its own (pm_limit.h)
 $(OBJ)/pm_limit.o: CXXFLAGS += -ffp-contract=off
+# the multi-tensor mean rounds every product and sum on its own, as the fp32
+# restatement of its tests does; its division stays correctly rounded (pm_adv.h)
+$(OBJ)/pm_adv.o: CXXFLAGS += -ffp-contract=off
 # the whole-MRF kernels: see pm_conv_bf16_mrf.hip
 MRF_FLAGS = -mllvm -amdgpu-sched-strategy=max-ilp
 HDRS = $(wildcard $(SRC)/*.h) include/promonet_hip.h

@@ -692,6 +692,59 @@ int pm_signal_loss_backward(const float* y_true, const float* y_pred,
                             int samples, const void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- adversarial losses: promonet/train/loss.py:11-53 ---------------------
+ * feature_matching, discriminator and generator are each a sum of means over
+ * a list of tensors of unrelated sizes. pm_multi_mean takes the whole list:
+ * for entry k of `count`,  mean_k = (1 / numel[k]) sum_i op_k(a_k[i], b_k[i])
+ * in fp32, a_k and b_k read as fp32 whatever they are stored as:
+ *   PM_ADV_ABS_DIFF         |a - b|           (feature matching: a real, b fake)
+ *   PM_ADV_SQ_ONE_MINUS     (1 - a)^2
+ *   PM_ADV_SQ               a^2
+ *   PM_ADV_HINGE_ONE_MINUS  max(1 - a, 0)
+ *   PM_ADV_HINGE_ONE_PLUS   max(1 + a, 0)
+ * a, b, numel, op and dtype are HOST arrays of `count` values; a[k] and b[k]
+ * are device pointers to numel[k] dense elements of dtype[k] = PM_F32, PM_F16
+ * or PM_BF16. b is read by PM_ADV_ABS_DIFF only (the array may be NULL when no
+ * entry has that op). out is count + 1 device floats: the means, then their
+ * total. A tensor is cut into chunks of pm_multi_mean_chunk() elements, one
+ * workgroup a chunk, summed in a fixed order; a chunk never spans two tensors,
+ * so a tensor's mean is the same bits alone and in any list, at any alignment
+ * (16-byte aligned pointers take 16-byte loads). One final workgroup sums a
+ * tensor's partials in ascending order in double, divides by numel in double
+ * and rounds once; the total is the double means summed in list order,
+ * rounded once. The table of entries travels in the kernel arguments, 64
+ * entries a launch: no host-to-device copy, any count. No float atomics: every
+ * output is bit-identical from run to run.
+ * pm_multi_mean_backward: with c_k = grad_out[0] / (float)numel[k] (grad_out a
+ * device scalar, one fp32 division), grad_b[k] = -sign(a - b) c_k for
+ * PM_ADV_ABS_DIFF (0 where a = b; nothing goes to a: the reference detaches
+ * the real maps, and a non-NULL grad_a[k] is an error), and grad_a[k] =
+ * 2 (a - 1) c_k, 2 a c_k, -c_k where 1 - a >= 0, c_k where 1 + a >= 0 (else 0)
+ * for the other four, rounded to dtype[k]. grad_a and grad_b are host arrays
+ * of device pointers; a NULL entry (or a NULL array) asks for no gradient. The
+ * backward reads nothing from the workspace, which may be NULL.
+ * Both are asynchronous, allocate nothing and capture into a graph. Bad
+ * arguments (count <= 0, a NULL array or pointer, numel <= 0, an unknown op
+ * or dtype, a workspace smaller than pm_multi_mean_workspace_bytes) return
+ * PM_EINVAL before any device work; the workspace query returns 0 for them. */
+#define PM_ADV_ABS_DIFF 0
+#define PM_ADV_SQ_ONE_MINUS 1
+#define PM_ADV_SQ 2
+#define PM_ADV_HINGE_ONE_MINUS 3
+#define PM_ADV_HINGE_ONE_PLUS 4
+int pm_multi_mean_chunk(void);
+size_t pm_multi_mean_workspace_bytes(const long long* numel, int count);
+int pm_multi_mean(const void* const* a, const void* const* b,
+                  const long long* numel, const int* op, const int* dtype,
+                  int count, float* out, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int pm_multi_mean_backward(const void* const* a, const void* const* b,
+                           const long long* numel, const int* op,
+                           const int* dtype, int count, const float* grad_out,
+                           void* const* grad_a, void* const* grad_b,
+                           void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* ---- Vocos mel vocoder engine: replaces promonet.model.Vocos --------------
  * (promonet/model/vocos.py, config/baselines/vocos.py MODEL = 'vocos').
  * conv_pre (k7) + cond, backbone embed (k7) + LayerNorm, `layers` fused

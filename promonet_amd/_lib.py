@@ -20,6 +20,9 @@ DTYPES = {'fp32': PM_F32, 'f32': PM_F32, 'f16': PM_F16, 'fp16': PM_F16,
           'mixed': 16}
 MAX_STAGES, MAX_RESBLOCKS, MAX_DILATIONS = 8, 4, 4
 SPARSE_METHODS = {None: 0, 'percentile': 1, 'constant': 2, 'topk': 3}
+# the ops of pm_multi_mean (PM_ADV_*, promonet_hip.h)
+(ADV_ABS_DIFF, ADV_SQ_ONE_MINUS, ADV_SQ, ADV_HINGE_ONE_MINUS,
+ ADV_HINGE_ONE_PLUS) = range(5)
 
 c_float_p = ctypes.c_void_p
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -136,6 +139,10 @@ SIGNATURES = {
     'pm_signal_loss_workspace_bytes': (_S, [_I]),
     'pm_signal_loss': (_I, [_P] * 3 + [_I, _I, _P, _S, _P]),
     'pm_signal_loss_backward': (_I, [_P] * 4 + [_I, _I, _P, _S, _P]),
+    'pm_multi_mean_chunk': (_I, []),
+    'pm_multi_mean_workspace_bytes': (_S, [_P, _I]),
+    'pm_multi_mean': (_I, [_P] * 5 + [_I, _P, _P, _S, _P]),
+    'pm_multi_mean_backward': (_I, [_P] * 5 + [_I] + [_P] * 4 + [_S, _P]),
     'pm_vocos_create': (_I, [_I] * 8 + [ctypes.POINTER(_P)]),
     'pm_vocos_destroy': (_I, [_P]),
     'pm_vocos_load_tensor': (_I, [_P, ctypes.c_char_p, _P, c_int64_p, _I, _P]),

@@ -69,6 +69,10 @@ VOCOS_POINTWISE_CHANNELS = 1536
 WAVLM_EMBEDDING_CHANNELS = 512
 ZERO_SHOT = False
 STEPS = 800000
+
+# Loss parameters (defaults.py:316-331), read by promonet_amd.loss at each call
+ADVERSARIAL_HINGE_LOSS = False      # hinge instead of least-squares GAN terms
+FEATURE_MATCHING_OMIT_FIRST = False  # skip each discriminator's first map
 NUM_WORKERS = 10
 
 # Storage type of the streamed FARGAN weights (math is fp32): 'fp32', 'f16'

@@ -1,15 +1,19 @@
-"""Training-side losses of the FARGAN configurations on the HIP kernels.
+"""Training-side losses on the HIP kernels.
 
-API of `promonet.loss` (promonet/train/loss.py:61-162): `stft`,
-`SpectralConvergence`, `MultiResolutionSpectralConvergence` and `signal`,
-differentiable in the prediction through HIP backward passes (pm_loss.h). The
-target is a constant. Neither direction syncs with the host, and both capture
-into a graph on one stream.
+API of `promonet.loss` (promonet/train/loss.py): the adversarial losses
+`feature_matching`, `discriminator` and `generator` (:11-53) as one
+multi-tensor mean each (pm_adv.h), and `stft`, `SpectralConvergence`,
+`MultiResolutionSpectralConvergence` and `signal` (:61-162), differentiable in
+the prediction through HIP backward passes (pm_loss.h), the target a constant.
+Neither direction syncs with the host, and both capture into a graph on one
+stream.
 """
+import ctypes
+
 import numpy as np
 import torch
 
-from promonet_amd import _lib
+from promonet_amd import _lib, config
 
 MIN_FFT, MAX_FFT = 64, 2560
 
@@ -363,3 +367,200 @@ def signal(y_true, y_pred):
     return _Signal.apply(
         y_true.reshape(-1, samples).to(torch.float32).contiguous(),
         y_pred.reshape(-1, samples).to(torch.float32).contiguous())
+
+
+###############################################################################
+# Adversarial losses: one multi-tensor mean a call
+###############################################################################
+
+
+_ADV_DTYPES = {torch.float32: _lib.PM_F32, torch.float16: _lib.PM_F16,
+               torch.bfloat16: _lib.PM_BF16}
+_DENSE_FORMATS = {4: (torch.channels_last,), 5: (torch.channels_last_3d,)}
+
+
+def _dense(tensor):
+    """Whether the tensor fills its memory in one of torch's memory formats
+    (a mean does not depend on the order of its elements)"""
+    return tensor.is_contiguous() or any(
+        tensor.is_contiguous(memory_format=memory_format)
+        for memory_format in _DENSE_FORMATS.get(tensor.ndim, ()))
+
+
+def _adv_tensor(tensor, name):
+    if not isinstance(tensor, torch.Tensor) or \
+            not tensor.is_floating_point():
+        raise ValueError(f'{name} must be a float tensor')
+    if not tensor.numel():
+        raise ValueError(f'{name} is empty')
+
+
+def _adv_single(tensor):
+    """fp32 / f16 / bf16 as stored, anything else as fp32; dense"""
+    if tensor.dtype not in _ADV_DTYPES:
+        tensor = tensor.to(torch.float32)
+    return tensor if _dense(tensor) else tensor.contiguous()
+
+
+def _adv_pair(real, fake):
+    """A pair shares one dtype and one order in memory"""
+    if real.dtype != fake.dtype or real.dtype not in _ADV_DTYPES:
+        real, fake = real.to(torch.float32), fake.to(torch.float32)
+    if real.stride() != fake.stride() or not _dense(fake):
+        real, fake = real.contiguous(), fake.contiguous()
+    return real, fake
+
+
+def _adv_lists(first, second, names):
+    if len(first) != len(second):
+        raise ValueError(
+            f'{names[0]} has {len(first)} entries, {names[1]} '
+            f'{len(second)}')
+    if not len(first):
+        raise ValueError(f'{names[0]} is empty')
+    for index, (one, other) in enumerate(zip(first, second)):
+        _adv_tensor(one, f'{names[0]}[{index}]')
+        _adv_tensor(other, f'{names[1]}[{index}]')
+        if one.shape != other.shape:
+            raise ValueError(
+                f'{names[0]}[{index}] {tuple(one.shape)} and '
+                f'{names[1]}[{index}] {tuple(other.shape)} differ in shape')
+
+
+def _adv_arrays(a, b, ops):
+    """The host arrays of pm_multi_mean for tensors a, b (or None)"""
+    count = len(a)
+    pointers = ctypes.c_void_p * count
+    return (
+        pointers(*(t.data_ptr() for t in a)),
+        pointers(*(t.data_ptr() for t in b)) if b else None,
+        (ctypes.c_longlong * count)(*(t.numel() for t in a)),
+        (ctypes.c_int * count)(*ops),
+        (ctypes.c_int * count)(*(_ADV_DTYPES[t.dtype] for t in a)))
+
+
+class _MultiMean(torch.autograd.Function):
+    """(total, means) of op_k over tensor k of a flattened list: `count`
+    tensors a, then (feature matching) their `count` partners b. The means
+    are for logging and carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, ops, count, *tensors):
+        lib = _lib.lib()
+        a, b = tensors[:count], tensors[count:]
+        arrays = _adv_arrays(a, b, ops)
+        device = a[0].device
+        out = torch.empty(count + 1, device=device)
+        with torch.cuda.device(device):
+            size = lib.pm_multi_mean_workspace_bytes(arrays[2], count)
+            workspace = torch.empty(size, dtype=torch.uint8, device=device)
+            _lib.check(lib.pm_multi_mean(
+                *arrays, count, _lib.ptr(out), workspace.data_ptr(), size,
+                _lib.stream()))
+        ctx.ops, ctx.count = ops, count
+        ctx.save_for_backward(*tensors)
+        total, means = out[count], out[:count]
+        ctx.mark_non_differentiable(means)
+        return total, means
+
+    @staticmethod
+    def backward(ctx, grad, _):
+        lib = _lib.lib()
+        ops, count = ctx.ops, ctx.count
+        tensors = ctx.saved_tensors
+        a, b = tensors[:count], tensors[count:]
+        # (torch.empty_like keeps the strides of a dense tensor)
+        grads = [
+            torch.empty_like(t)
+            if ctx.needs_input_grad[2 + i] and
+            (i >= count) == (ops[i % count] == _lib.ADV_ABS_DIFF) else None
+            for i, t in enumerate(tensors)]
+        if any(g is not None for g in grads):
+            grad = grad.to(torch.float32).reshape(1).contiguous()
+            pointers = ctypes.c_void_p * count
+            grad_a = pointers(*(
+                None if g is None else g.data_ptr() for g in grads[:count]))
+            grad_b = pointers(*(
+                None if g is None else g.data_ptr()
+                for g in grads[count:])) if b else None
+            with torch.cuda.device(grad.device):
+                _lib.check(lib.pm_multi_mean_backward(
+                    *_adv_arrays(a, b, ops), count, _lib.ptr(grad), grad_a,
+                    grad_b, None, 0, _lib.stream()))
+        return (None, None) + tuple(grads)
+
+
+def _multi_mean(ops, a, b=()):
+    for tensor in tuple(a) + tuple(b):
+        _lib.require_gpu(tensor)
+    total, means = _MultiMean.apply(tuple(ops), len(a), *a, *b)
+    return total, list(means.unbind())
+
+
+def feature_matching(real_feature_maps, fake_feature_maps):
+    """Feature matching loss (loss.py:11-26): the sum over every pair of maps
+    of mean |real - fake|, as a 0-d fp32 device tensor. Lists (one per
+    discriminator) of lists of maps; FEATURE_MATCHING_OMIT_FIRST skips each
+    discriminator's first map. fp32, f16 and bf16 maps are read as stored.
+    The gradient goes to the fake maps only: the real ones are constants, as
+    the reference detaches them."""
+    if len(real_feature_maps) != len(fake_feature_maps):
+        raise ValueError(
+            f'real_feature_maps has {len(real_feature_maps)} lists, '
+            f'fake_feature_maps {len(fake_feature_maps)}')
+    skip = int(bool(config.FEATURE_MATCHING_OMIT_FIRST))
+    real, fake = [], []
+    for index, (reals, fakes) in enumerate(
+            zip(real_feature_maps, fake_feature_maps)):
+        if len(reals) != len(fakes):
+            raise ValueError(
+                f'discriminator {index} has {len(reals)} real maps and '
+                f'{len(fakes)} fake maps')
+        if len(reals) > skip:
+            _adv_lists(reals[skip:], fakes[skip:],
+                       (f'real_feature_maps[{index}]',
+                        f'fake_feature_maps[{index}]'))
+        real.extend(reals[skip:])
+        fake.extend(fakes[skip:])
+    if not real:
+        raise ValueError('no feature maps')
+    pairs = [_adv_pair(r.detach(), f) for r, f in zip(real, fake)]
+    return _multi_mean(
+        (_lib.ADV_ABS_DIFF,) * len(pairs), [p[0] for p in pairs],
+        [p[1] for p in pairs])[0]
+
+
+def discriminator(real_outputs, fake_outputs):
+    """Discriminator loss (loss.py:29-40) -> (total, real_losses,
+    fake_losses): mean (1 - real)^2 and mean fake^2 per discriminator, or
+    with ADVERSARIAL_HINGE_LOSS mean max(1 - real, 0) and mean max(1 + fake,
+    0), in one launch set over both lists. The gradient of `total` goes to
+    both lists; the per-discriminator losses are for logging and carry no
+    gradient."""
+    _adv_lists(real_outputs, fake_outputs, ('real_outputs', 'fake_outputs'))
+    count = len(real_outputs)
+    if config.ADVERSARIAL_HINGE_LOSS:
+        ops = (_lib.ADV_HINGE_ONE_MINUS,) * count + \
+            (_lib.ADV_HINGE_ONE_PLUS,) * count
+    else:
+        ops = (_lib.ADV_SQ_ONE_MINUS,) * count + (_lib.ADV_SQ,) * count
+    total, losses = _multi_mean(
+        ops, [_adv_single(t) for t in real_outputs] +
+        [_adv_single(t) for t in fake_outputs])
+    return total, losses[:count], losses[count:]
+
+
+def generator(discriminator_outputs):
+    """Generator adversarial loss (loss.py:43-53) -> (total, losses): mean
+    (1 - output)^2 per discriminator, or with ADVERSARIAL_HINGE_LOSS mean
+    max(1 - output, 0). The per-discriminator losses are for logging and
+    carry no gradient."""
+    if not len(discriminator_outputs):
+        raise ValueError('discriminator_outputs is empty')
+    for index, tensor in enumerate(discriminator_outputs):
+        _adv_tensor(tensor, f'discriminator_outputs[{index}]')
+    op = _lib.ADV_HINGE_ONE_MINUS if config.ADVERSARIAL_HINGE_LOSS else \
+        _lib.ADV_SQ_ONE_MINUS
+    return _multi_mean(
+        (op,) * len(discriminator_outputs),
+        [_adv_single(t) for t in discriminator_outputs])
