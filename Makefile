@@ -4,17 +4,18 @@ ARCH ?= gfx950
 # TUNING=1: A/B scaffolding (PM_FUSION / PM_NO_NARROW / PM_FARGAN environment
 # switches, phase-timeline stamps, ablation defines). Never in the shipped .so.
 TUNING ?= 0
-CXXFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-value -fno-honor-nans
+# A/B variants (scripts/build_variant.sh): more flags for every object, and
+# OBJ / LIB on the command line for a build beside the shipped one
+EXTRA ?=
+CXXFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-value -fno-honor-nans $(EXTRA)
 ifeq ($(TUNING),1)
 CXXFLAGS += -DPM_TUNING
 endif
 SRC = promonet_amd/csrc
 OBJ = build/obj
 LIB = promonet_amd/lib/libpromonet_hip.so
-OBJS = $(OBJ)/pm_api.o $(OBJ)/pm_conv_f16.o $(OBJ)/pm_conv_bf16.o $(OBJ)/pm_conv_f32.o \
-       $(OBJ)/pm_conv_f16x3.o $(OBJ)/pm_conv_f16a2.o \
-       $(OBJ)/pm_conv_f16_mrf.o $(OBJ)/pm_conv_bf16_mrf.o $(OBJ)/pm_vocos.o $(OBJ)/pm_harmonics.o \
-       $(OBJ)/pm_loss.o $(OBJ)/pm_limit.o $(OBJ)/pm_lpc.o $(OBJ)/pm_adv.o
+# every .hip is an object of the library: the one place that lists them
+OBJS = $(patsubst $(SRC)/%.hip,$(OBJ)/%.o,$(sort $(wildcard $(SRC)/*.hip)))
 # the spectral head keeps torch.clip's NaN (a NaN magnitude stays NaN)
 $(OBJ)/pm_vocos.o: CXXFLAGS += -fhonor-nans
 # the harmonic contours carry NaN (an unvoiced prior, a harmonic that is absent)
@@ -30,7 +31,7 @@ $(OBJ)/pm_limit.o: CXXFLAGS += -ffp-contract=off
 # restatement of its tests does; its division stays correctly rounded (pm_adv.h)
 $(OBJ)/pm_adv.o: CXXFLAGS += -ffp-contract=off
 # the whole-MRF kernels: see pm_conv_bf16_mrf.hip
-MRF_FLAGS = -mllvm -amdgpu-sched-strategy=max-ilp
+MRF_FLAGS ?= -mllvm -amdgpu-sched-strategy=max-ilp
 HDRS = $(wildcard $(SRC)/*.h) include/promonet_hip.h
 
 all: $(LIB)
@@ -44,13 +45,17 @@ $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)
-	@mkdir -p promonet_amd/lib
+	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJS) -o $@
 	@python3 scripts/check_spills.py $(OBJS) || true
 
 # fails when any kernel spills VGPRs or uses scratch memory
 check: $(LIB)
 	python3 scripts/check_spills.py $(OBJS)
+
+# the object list, for the scripts that link a variant of one object
+objs:
+	@echo $(OBJS)
 
 clean:
 	rm -rf build $(LIB)

@@ -4,48 +4,17 @@
 // without a GPU.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-
-#include "promonet_hip.h"
+#include "pm_host.h"
 #include "pm_adv.h"
 
-// pm_api.hip: sets the message pm_last_error() returns
-int pm_fail_message(int code, const char* message);
-
 namespace {
-
-int afail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int afail(int code, const char* fmt, ...) {
-    char buffer[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buffer, sizeof(buffer), fmt, ap);
-    va_end(ap);
-    return pm_fail_message(code, buffer);
-}
-
-#define ADV_TRY(expr)                                                        \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess)                                                \
-            return afail(PM_EHIP, "%s failed: %s (%s:%d)", #expr,            \
-                         hipGetErrorString(e_), __FILE__, __LINE__);         \
-    } while (0)
-
-const long long MAX_GRID = 0x7fffffffll;
 
 static_assert(sizeof(AdvTable) <= 3072, "the table must stay well under the "
                                         "4 KB of kernel arguments");
 
-size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
 long long chunks_of(long long numel) {
     return (numel + ADV_CHUNK - 1) / ADV_CHUNK;
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // What is wrong with the list, or NULL; *groups = its workgroups
 const char* check_list(const long long* numel, int count, long long* groups) {
@@ -54,7 +23,7 @@ const char* check_list(const long long* numel, int count, long long* groups) {
     *groups = 0;
     for (int k = 0; k < count; ++k) {
         if (numel[k] <= 0) return "every numel must be at least 1";
-        if (chunks_of(numel[k]) > MAX_GRID)
+        if (chunks_of(numel[k]) > PM_MAX_GRID)
             return "a tensor has too many elements for one launch";
         *groups += chunks_of(numel[k]);
     }
@@ -81,16 +50,17 @@ struct Layout { size_t wide, partials, total; };
 
 Layout layout_of(int count, long long groups) {
     Layout l;
-    l.wide = round256((size_t)count * sizeof(AdvMeta));
-    l.partials = l.wide + round256((size_t)count * sizeof(double));
-    l.total = l.partials + round256((size_t)groups * sizeof(float));
+    l.wide = pm_align256((size_t)count * sizeof(AdvMeta));
+    l.partials = l.wide + pm_align256((size_t)count * sizeof(double));
+    l.total = l.partials + pm_align256((size_t)groups * sizeof(float));
     return l;
 }
 
 // Adds entry k to the table; false when the launch is full
 bool add_entry(AdvTable* t, int* groups, const AdvEntry& e) {
     const long long more = chunks_of(e.numel);
-    if (t->count == ADV_MAX_ENTRIES || *groups + more > MAX_GRID) return false;
+    if (t->count == ADV_MAX_ENTRIES || *groups + more > PM_MAX_GRID)
+        return false;
     t->e[t->count] = e;
     t->e[t->count].first = *groups;
     ++t->count;
@@ -116,14 +86,14 @@ extern "C" int pm_multi_mean(const void* const* a, const void* const* b,
                              void* stream) {
     long long groups;
     if (const char* why = check_list(numel, count, &groups))
-        return afail(PM_EINVAL, "pm_multi_mean: %s", why);
+        return pm_fail(PM_EINVAL, "pm_multi_mean: %s", why);
     if (const char* why = check_entries(a, b, op, dtype, count))
-        return afail(PM_EINVAL, "pm_multi_mean: %s", why);
+        return pm_fail(PM_EINVAL, "pm_multi_mean: %s", why);
     if (!out || !workspace)
-        return afail(PM_EINVAL, "pm_multi_mean: null argument");
+        return pm_fail(PM_EINVAL, "pm_multi_mean: null argument");
     const Layout l = layout_of(count, groups);
     if (workspace_bytes < l.total)
-        return afail(PM_EINVAL, "pm_multi_mean: workspace too small");
+        return pm_fail(PM_EINVAL, "pm_multi_mean: workspace too small");
     AdvMeta* meta = (AdvMeta*)workspace;
     double* wide = (double*)((char*)workspace + l.wide);
     float* partials = (float*)((char*)workspace + l.partials);
@@ -143,20 +113,20 @@ extern "C" int pm_multi_mean(const void* const* a, const void* const* b,
             e.numel = numel[k];
             e.op = (unsigned char)op[k];
             e.dtype = (unsigned char)dtype[k];
-            e.aligned = aligned16(e.a) && aligned16(e.b);
+            e.aligned = pm_aligned16(e.a) && pm_aligned16(e.b);
             e.unused = 0;
             if (!add_entry(&t, &launch_groups, e)) break;
         }
         hipLaunchKernelGGL(adv_partials_kernel, dim3(launch_groups),
                            dim3(ADV_THREADS), 0, (hipStream_t)stream, t,
                            partials, meta);
-        ADV_TRY(hipGetLastError());
+        PM_HIP_TRY(hipGetLastError());
         base += launch_groups;
     }
     hipLaunchKernelGGL(adv_final_kernel, dim3(1), dim3(ADV_FINAL_THREADS), 0,
                        (hipStream_t)stream, (const float*)partials,
                        (const AdvMeta*)meta, wide, count, out);
-    ADV_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }
 
@@ -172,16 +142,16 @@ extern "C" int pm_multi_mean_backward(const void* const* a,
     (void)workspace_bytes;
     long long groups;
     if (const char* why = check_list(numel, count, &groups))
-        return afail(PM_EINVAL, "pm_multi_mean_backward: %s", why);
+        return pm_fail(PM_EINVAL, "pm_multi_mean_backward: %s", why);
     if (const char* why = check_entries(a, b, op, dtype, count))
-        return afail(PM_EINVAL, "pm_multi_mean_backward: %s", why);
+        return pm_fail(PM_EINVAL, "pm_multi_mean_backward: %s", why);
     if (!grad_out || (!grad_a && !grad_b))
-        return afail(PM_EINVAL, "pm_multi_mean_backward: null argument");
+        return pm_fail(PM_EINVAL, "pm_multi_mean_backward: null argument");
     for (int k = 0; k < count; ++k)
         if (op[k] == PM_ADV_ABS_DIFF && grad_a && grad_a[k])
-            return afail(PM_EINVAL,
-                         "pm_multi_mean_backward: PM_ADV_ABS_DIFF has no "
-                         "gradient for a (the real maps are constants)");
+            return pm_fail(PM_EINVAL,
+                           "pm_multi_mean_backward: PM_ADV_ABS_DIFF has no "
+                           "gradient for a (the real maps are constants)");
     AdvTable t;
     t.index0 = 0;
     t.base = 0;
@@ -199,7 +169,8 @@ extern "C" int pm_multi_mean_backward(const void* const* a,
             e.numel = numel[k];
             e.op = (unsigned char)op[k];
             e.dtype = (unsigned char)dtype[k];
-            e.aligned = aligned16(e.a) && aligned16(e.b) && aligned16(e.grad);
+            e.aligned = pm_aligned16(e.a) && pm_aligned16(e.b) &&
+                        pm_aligned16(e.grad);
             e.unused = 0;
             if (!add_entry(&t, &launch_groups, e)) break;
         }
@@ -207,7 +178,7 @@ extern "C" int pm_multi_mean_backward(const void* const* a,
         hipLaunchKernelGGL(adv_backward_kernel, dim3(launch_groups),
                            dim3(ADV_THREADS), 0, (hipStream_t)stream, t,
                            grad_out);
-        ADV_TRY(hipGetLastError());
+        PM_HIP_TRY(hipGetLastError());
     }
     return PM_OK;
 }

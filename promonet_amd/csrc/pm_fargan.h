@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void pm_fargan_pack_kernel(
 // All packed layers live in ONE buffer at compile-time offsets (elements), so
 // a kernel carries a single base pointer: with one pointer per layer the 23
 // of them exhausted the scalar registers and spilled into vector registers.
-// Order = the layer table of pm_api.hip (fargan_layers); the K-split copies
+// Order = the layer table of pm_fargan.hip (fargan_layers); the K-split copies
 // used by the cluster kernel follow the row-packed layers.
 // Mixed storage (round 4): the matrices whose rounding the audio does not feel
 // - the three GRU cells' W_ih / W_hh (U(-1/16, 1/16) entries in front of a

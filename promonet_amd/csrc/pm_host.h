@@ -1,0 +1,70 @@
+// Host helpers shared by every .hip that implements part of the C ABI
+// (include/promonet_hip.h). No kernels: what is declared here and not inline
+// is defined once, in pm_api.hip, next to the state or the kernels it needs.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "promonet_hip.h"
+
+// Sets the message pm_last_error() returns on this thread; returns `code`
+int pm_fail(int code, const char* fmt, ...)
+    __attribute__((format(printf, 2, 3)));
+
+#define PM_HIP_TRY(expr)                                                     \
+    do {                                                                     \
+        hipError_t e_ = (expr);                                              \
+        if (e_ != hipSuccess)                                                \
+            return pm_fail(PM_EHIP, "%s failed: %s (%s:%d)", #expr,          \
+                           hipGetErrorString(e_), __FILE__, __LINE__);       \
+    } while (0)
+
+// the most workgroups one grid dimension takes
+static const long long PM_MAX_GRID = 0x7fffffffll;
+
+static inline int pm_pad32(int c) { return (c + 31) / 32 * 32; }
+static inline size_t pm_align256(size_t v) { return (v + 255) / 256 * 256; }
+static inline bool pm_aligned16(const void* p) {
+    return ((uintptr_t)p & 15) == 0;
+}
+
+// Do the byte ranges [a, a + an) and [b, b + bn) share a byte? A null or an
+// empty range overlaps nothing.
+static inline bool pm_overlap(
+    const void* a, size_t an, const void* b, size_t bn) {
+    const char* p = (const char*)a;
+    const char* q = (const char*)b;
+    return p && q && an && bn && p < q + bn && q < p + an;
+}
+
+// Opt a kernel into `bytes` of dynamic LDS (> 48 KB needs the attribute).
+// The grant is a property of (kernel, DEVICE): cached per pair, so one process
+// driving several GPUs sets it on each, and guarded so that concurrent
+// launches from several host threads / streams are safe.
+hipError_t pm_ensure_dynamic_lds(const void* kern, int bytes);
+
+// Compute units of the current device, queried once per device (the walked
+// launches size their grids from it on every forward).
+int pm_device_cus();
+
+// *dst (allocated when null) = n floats of device memory copied from src
+int pm_copy_dev(float** dst, const float* src, size_t n, hipStream_t s);
+
+// The exact-fp32 convs of the framed DFT (pm_audio.hip), whose kernels are
+// compiled with the other convs: pack a (cout, cin, k) basis, plain conv
+// layout of 64-channel chunks, and run it over x (B, L, Cin) with epilogue
+// `epi` (pm_launch_stft). bins / maxbits / grad: SingleArgs (pm_conv.h).
+struct PmDftConv {
+    const float* x; float* out; const void* w; const float* bias;
+    int B, L, Lout, Cin, M, pad, bins;
+    unsigned* maxbits; const float* grad;
+};
+hipError_t pm_dft_pack(const float* w, void* out, int cout, int cout_pad,
+                       int cin, int k, hipStream_t s);
+hipError_t pm_dft_conv(int epi, const PmDftConv& c, hipStream_t s);
+
+#ifdef PM_TUNING
+unsigned long long* pm_timeline();   // what pm_debug_timeline set, or null
+#endif

@@ -12,46 +12,7 @@
 #include <utility>
 
 #include "pm_conv.h"
-#include "promonet_hip.h"
-
-// Opt a kernel into `bytes` of dynamic LDS (> 48 KB needs the attribute).
-// The grant is a property of (kernel, DEVICE): cached per pair, so one process
-// driving several GPUs sets it on each, and guarded so that concurrent
-// launches from several host threads / streams are safe.
-inline hipError_t pm_ensure_dynamic_lds(const void* kern, int bytes) {
-    static std::mutex guard;
-    static std::map<std::pair<const void*, int>, int> granted;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(guard);
-    int& have = granted[std::make_pair(kern, dev)];
-    if (bytes > have) {
-        e = hipFuncSetAttribute(
-            kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        have = bytes;
-    }
-    return hipSuccess;
-}
-
-// Compute units of the current device, queried once per device (the walked
-// launches size their grids from it on every forward).
-inline int pm_device_cus() {
-    static std::mutex guard;
-    static std::map<int, int> cus_of;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lock(guard);
-    auto it = cus_of.find(dev);
-    if (it != cus_of.end()) return it->second;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
-                              dev) != hipSuccess)
-        cus = 0;
-    cus_of[dev] = cus;
-    return cus;
-}
+#include "pm_host.h"
 
 // Test hooks (pm_debug_force): the walked kernels and the multi-block path of
 // the wide upsampler are chosen from the grid size, which unit-sized inputs

@@ -3,43 +3,16 @@
 // the first HIP call, so the checks answer on a machine without a GPU.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-
-#include "promonet_hip.h"
+#include "pm_host.h"
 #include "pm_limit.h"
 
-// pm_api.hip: sets the message pm_last_error() returns
-int pm_fail_message(int code, const char* message);
-
 namespace {
-
-int lfail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int lfail(int code, const char* fmt, ...) {
-    char buffer[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buffer, sizeof(buffer), fmt, ap);
-    va_end(ap);
-    return pm_fail_message(code, buffer);
-}
-
-#define LM_TRY(expr)                                                         \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess)                                                \
-            return lfail(PM_EHIP, "%s failed: %s (%s:%d)", #expr,            \
-                         hipGetErrorString(e_), __FILE__, __LINE__);         \
-    } while (0)
 
 // [p, p + rows * stride) of floats against [q, ...)
 bool overlap(const float* p, long long p_stride, const float* q,
              long long q_stride, int rows, int samples) {
-    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-    const uintptr_t p1 = p0 + ((uintptr_t)(rows - 1) * p_stride + samples) * 4;
-    const uintptr_t q1 = q0 + ((uintptr_t)(rows - 1) * q_stride + samples) * 4;
-    return p0 < q1 && q0 < p1;
+    return pm_overlap(p, ((size_t)(rows - 1) * p_stride + samples) * 4,
+                      q, ((size_t)(rows - 1) * q_stride + samples) * 4);
 }
 
 bool unit(float v) { return v > 0.f && v < 1.f; }
@@ -54,8 +27,7 @@ extern "C" int pm_limit_tile(int* chunk, int* tile) {
 
 extern "C" size_t pm_limit_workspace_bytes(int rows) {
     if (rows < 1) return 0;
-    const size_t bytes = (size_t)rows * LM_STATS * sizeof(int);
-    return (bytes + 255) / 256 * 256;
+    return pm_align256((size_t)rows * LM_STATS * sizeof(int));
 }
 
 extern "C" int pm_limit(const float* x, const int* lengths, float* out,
@@ -64,21 +36,21 @@ extern "C" int pm_limit(const float* x, const int* lengths, float* out,
                         float attack_complement, float release,
                         float threshold, void* workspace,
                         size_t workspace_bytes, void* stream) {
-    if (rows < 0 || samples < 0) return lfail(PM_EINVAL, "negative size");
-    if (delay < 1) return lfail(PM_EINVAL, "delay must be at least 1");
+    if (rows < 0 || samples < 0) return pm_fail(PM_EINVAL, "negative size");
+    if (delay < 1) return pm_fail(PM_EINVAL, "delay must be at least 1");
     if (!unit(attack) || !unit(attack_complement) || !unit(release))
-        return lfail(PM_EINVAL, "the attack coefficient, its complement and "
-                     "the release coefficient must lie inside (0, 1)");
+        return pm_fail(PM_EINVAL, "the attack coefficient, its complement and "
+                       "the release coefficient must lie inside (0, 1)");
     if (!(threshold > 0.f) || threshold > 3e38f)
-        return lfail(PM_EINVAL, "the threshold must be positive and finite");
+        return pm_fail(PM_EINVAL, "the threshold must be positive and finite");
     if (x_stride < samples || out_stride < samples)
-        return lfail(PM_EINVAL, "a row stride is below its row's length");
+        return pm_fail(PM_EINVAL, "a row stride is below its row's length");
     if (rows == 0 || samples == 0) return PM_OK;
-    if (!x || !out || !workspace) return lfail(PM_EINVAL, "null argument");
+    if (!x || !out || !workspace) return pm_fail(PM_EINVAL, "null argument");
     if (overlap(x, x_stride, out, out_stride, rows, samples))
-        return lfail(PM_EINVAL, "out must not alias x");
+        return pm_fail(PM_EINVAL, "out must not alias x");
     if (workspace_bytes < pm_limit_workspace_bytes(rows))
-        return lfail(PM_ENOMEM, "workspace too small");
+        return pm_fail(PM_ENOMEM, "workspace too small");
     LimitArgs a;
     a.x = x; a.lengths = lengths; a.out = out; a.gain = gain;
     a.stats = (int*)workspace;
@@ -87,7 +59,7 @@ extern "C" int pm_limit(const float* x, const int* lengths, float* out,
     a.a = attack; a.b = attack_complement; a.r = release; a.th = threshold;
     hipLaunchKernelGGL(pm_limit_kernel, dim3(rows), dim3(LM_THREADS), 0,
                        (hipStream_t)stream, a);
-    LM_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }
 
@@ -97,16 +69,16 @@ extern "C" int pm_loudness_shift(const float* x, const float* db,
                                  long long x_stride, int frames,
                                  long long db_stride, long long out_stride,
                                  void* stream) {
-    if (rows < 0 || samples < 0) return lfail(PM_EINVAL, "negative size");
-    if (frames < 1) return lfail(PM_EINVAL, "frames must be at least 1");
+    if (rows < 0 || samples < 0) return pm_fail(PM_EINVAL, "negative size");
+    if (frames < 1) return pm_fail(PM_EINVAL, "frames must be at least 1");
     if (x_stride < samples || out_stride < samples)
-        return lfail(PM_EINVAL, "a row stride is below its row's length");
+        return pm_fail(PM_EINVAL, "a row stride is below its row's length");
     if (db_stride != 0 && db_stride < frames)
-        return lfail(PM_EINVAL, "the stride of db is below `frames` (0 "
-                     "shares one contour among the rows)");
-    if (rows > 65535) return lfail(PM_EINVAL, "at most 65535 rows");
+        return pm_fail(PM_EINVAL, "the stride of db is below `frames` (0 "
+                       "shares one contour among the rows)");
+    if (rows > 65535) return pm_fail(PM_EINVAL, "at most 65535 rows");
     if (rows == 0 || samples == 0) return PM_OK;
-    if (!x || !db || !out) return lfail(PM_EINVAL, "null argument");
+    if (!x || !db || !out) return pm_fail(PM_EINVAL, "null argument");
     ShiftArgs a;
     a.x = x; a.db = db; a.lengths = lengths; a.frame_lengths = frame_lengths;
     a.out = out; a.x_stride = x_stride; a.db_stride = db_stride;
@@ -114,6 +86,6 @@ extern "C" int pm_loudness_shift(const float* x, const float* db,
     hipLaunchKernelGGL(pm_loudness_shift_kernel,
                        dim3((samples + LS_THREADS - 1) / LS_THREADS, rows),
                        dim3(LS_THREADS), 0, (hipStream_t)stream, a);
-    LM_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }

@@ -4,39 +4,12 @@
 // checks answer on a machine without a GPU.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
-#include "promonet_hip.h"
+#include "pm_host.h"
 #include "pm_loss.h"
-
-// pm_api.hip: sets the message pm_last_error() returns
-int pm_fail_message(int code, const char* message);
 
 namespace {
 
-int lfail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int lfail(int code, const char* fmt, ...) {
-    char buffer[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buffer, sizeof(buffer), fmt, ap);
-    va_end(ap);
-    return pm_fail_message(code, buffer);
-}
-
-#define SC_TRY(expr)                                                         \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess)                                                \
-            return lfail(PM_EHIP, "%s failed: %s (%s:%d)", #expr,            \
-                         hipGetErrorString(e_), __FILE__, __LINE__);         \
-    } while (0)
-
-const long long MAX_GRID = 0x7fffffffll;
 const int MAX_SAMPLES = 1 << 30;
-
-size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 
 // The radix plan of a size and the split of a row's frames over workgroups:
 // 5 first where N = 5 2^a, then 4s, then one 2 where a power of 4 does not
@@ -67,14 +40,16 @@ const char* make_plan(int batch, int samples, int fft_size, int hop_size,
     if (m % 5 == 0) { p->radix[p->stages++] = 5; m /= 5; }
     while (m % 4 == 0) { p->radix[p->stages++] = 4; m /= 4; }
     if (m == 2) p->radix[p->stages++] = 2;
-    if ((long long)batch * p->groups > MAX_GRID ||
-        ((long long)batch * samples + SC_THREADS - 1) / SC_THREADS > MAX_GRID)
+    if ((long long)batch * p->groups > PM_MAX_GRID ||
+        ((long long)batch * samples + SC_THREADS - 1) / SC_THREADS >
+            PM_MAX_GRID)
         return "too many frames or samples for one launch";
     return nullptr;
 }
 
 size_t gradient_bytes(int batch, const ScPlan& p) {
-    return round256((size_t)batch * (p.M + 1) * p.frames * 2 * sizeof(float));
+    return pm_align256((size_t)batch * (p.M + 1) * p.frames * 2 *
+                       sizeof(float));
 }
 
 }  // namespace
@@ -85,14 +60,14 @@ extern "C" size_t pm_sc_forward_workspace_bytes(int batch, int samples,
     ScPlan p;
     if (make_plan(batch, samples, fft_size, hop_size, &p)) return 0;
     return (with_gradient ? gradient_bytes(batch, p) : 0) +
-           round256((size_t)batch * p.groups * 2 * sizeof(float));
+           pm_align256((size_t)batch * p.groups * 2 * sizeof(float));
 }
 
 extern "C" size_t pm_sc_adjoint_workspace_bytes(int batch, int samples,
                                                 int fft_size, int hop_size) {
     ScPlan p;
     if (make_plan(batch, samples, fft_size, hop_size, &p)) return 0;
-    return round256((size_t)batch * p.frames * p.N * sizeof(float));
+    return pm_align256((size_t)batch * p.frames * p.N * sizeof(float));
 }
 
 extern "C" int pm_sc_stft(const float* x, const float* window,
@@ -101,15 +76,15 @@ extern "C" int pm_sc_stft(const float* x, const float* window,
                           int fft_size, int hop_size, void* stream) {
     ScForwardArgs a;
     if (const char* why = make_plan(batch, samples, fft_size, hop_size, &a.p))
-        return lfail(PM_EINVAL, "pm_sc_stft: %s", why);
+        return pm_fail(PM_EINVAL, "pm_sc_stft: %s", why);
     if (!x || !window || !twiddle || (!s && !gradient))
-        return lfail(PM_EINVAL, "null argument");
+        return pm_fail(PM_EINVAL, "null argument");
     a.x = x; a.y = nullptr; a.window = window; a.twiddle = twiddle;
     a.upstream = upstream; a.s = s; a.G = gradient; a.partials = nullptr;
     const size_t lds = 2 * (size_t)a.p.fpg * a.p.M * sizeof(float2);
     hipLaunchKernelGGL(sc_forward_kernel<false>, dim3(batch * a.p.groups),
                        dim3(SC_THREADS), lds, (hipStream_t)stream, a);
-    SC_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }
 
@@ -121,12 +96,12 @@ extern "C" int pm_sc_forward(const float* x, const float* y,
                              void* stream) {
     ScForwardArgs a;
     if (const char* why = make_plan(batch, samples, fft_size, hop_size, &a.p))
-        return lfail(PM_EINVAL, "pm_sc_forward: %s", why);
+        return pm_fail(PM_EINVAL, "pm_sc_forward: %s", why);
     if (!x || !y || !window || !twiddle || !sums || !workspace)
-        return lfail(PM_EINVAL, "null argument");
+        return pm_fail(PM_EINVAL, "null argument");
     if (workspace_bytes < pm_sc_forward_workspace_bytes(
             batch, samples, fft_size, hop_size, with_gradient))
-        return lfail(PM_ENOMEM, "workspace too small");
+        return pm_fail(PM_ENOMEM, "workspace too small");
     const size_t offset = with_gradient ? gradient_bytes(batch, a.p) : 0;
     a.x = x; a.y = y; a.window = window; a.twiddle = twiddle;
     a.upstream = nullptr; a.s = nullptr;
@@ -136,11 +111,11 @@ extern "C" int pm_sc_forward(const float* x, const float* y,
     const int groups = batch * a.p.groups;
     hipLaunchKernelGGL(sc_forward_kernel<true>, dim3(groups),
                        dim3(SC_THREADS), lds, (hipStream_t)stream, a);
-    SC_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(sc_sums_kernel, dim3(1), dim3(SC_THREADS), 0,
                        (hipStream_t)stream, (const float*)a.partials,
                        (long long)groups, sums);
-    SC_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }
 
@@ -152,18 +127,18 @@ extern "C" int pm_sc_adjoint(const float* gradient, const float* window,
                              void* stream) {
     ScAdjointArgs a;
     if (const char* why = make_plan(batch, samples, fft_size, hop_size, &a.p))
-        return lfail(PM_EINVAL, "pm_sc_adjoint: %s", why);
+        return pm_fail(PM_EINVAL, "pm_sc_adjoint: %s", why);
     if (!gradient || !window || !twiddle || !scale || !grad_x || !workspace)
-        return lfail(PM_EINVAL, "null argument");
+        return pm_fail(PM_EINVAL, "null argument");
     if (workspace_bytes < pm_sc_adjoint_workspace_bytes(
             batch, samples, fft_size, hop_size))
-        return lfail(PM_ENOMEM, "workspace too small");
+        return pm_fail(PM_ENOMEM, "workspace too small");
     a.G = gradient; a.window = window; a.twiddle = twiddle;
     a.frames_out = (float*)workspace;
     const size_t lds = 2 * (size_t)a.p.fpg * a.p.M * sizeof(float2);
     hipLaunchKernelGGL(sc_adjoint_frames_kernel, dim3(batch * a.p.groups),
                        dim3(SC_THREADS), lds, (hipStream_t)stream, a);
-    SC_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     ScOverlapArgs o;
     o.frames_in = (const float*)workspace; o.scale = scale; o.grad_x = grad_x;
     o.N = a.p.N; o.M = a.p.M; o.hop = a.p.hop; o.frames = a.p.frames;
@@ -172,19 +147,19 @@ extern "C" int pm_sc_adjoint(const float* gradient, const float* window,
     hipLaunchKernelGGL(sc_overlap_kernel,
                        dim3((o.total + SC_THREADS - 1) / SC_THREADS),
                        dim3(SC_THREADS), 0, (hipStream_t)stream, o);
-    SC_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }
 
 extern "C" size_t pm_signal_loss_workspace_bytes(int rows) {
     if (rows < 1) return 0;
-    return round256((size_t)rows * 4 * sizeof(float));
+    return pm_align256((size_t)rows * 4 * sizeof(float));
 }
 
 namespace {
 const char* check_signal(int rows, int samples) {
     if (rows < 1 || samples < 1) return "rows and samples must be at least 1";
-    if (((long long)rows * samples + SC_THREADS - 1) / SC_THREADS > MAX_GRID)
+    if (((long long)rows * samples + SC_THREADS - 1) / SC_THREADS > PM_MAX_GRID)
         return "too many samples for one launch";
     return nullptr;
 }
@@ -195,19 +170,19 @@ extern "C" int pm_signal_loss(const float* y_true, const float* y_pred,
                               void* workspace, size_t workspace_bytes,
                               void* stream) {
     if (const char* why = check_signal(rows, samples))
-        return lfail(PM_EINVAL, "pm_signal_loss: %s", why);
+        return pm_fail(PM_EINVAL, "pm_signal_loss: %s", why);
     if (!y_true || !y_pred || !out || !workspace)
-        return lfail(PM_EINVAL, "null argument");
+        return pm_fail(PM_EINVAL, "null argument");
     if (workspace_bytes < pm_signal_loss_workspace_bytes(rows))
-        return lfail(PM_ENOMEM, "workspace too small");
+        return pm_fail(PM_ENOMEM, "workspace too small");
     hipLaunchKernelGGL(sc_signal_rows_kernel, dim3(rows), dim3(SC_THREADS), 0,
                        (hipStream_t)stream, y_true, y_pred, (float*)workspace,
                        samples);
-    SC_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(sc_signal_mean_kernel, dim3(1), dim3(SC_THREADS), 0,
                        (hipStream_t)stream, (const float*)workspace, rows,
                        out);
-    SC_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }
 
@@ -218,17 +193,17 @@ extern "C" int pm_signal_loss_backward(const float* y_true,
                                        const void* workspace,
                                        size_t workspace_bytes, void* stream) {
     if (const char* why = check_signal(rows, samples))
-        return lfail(PM_EINVAL, "pm_signal_loss_backward: %s", why);
+        return pm_fail(PM_EINVAL, "pm_signal_loss_backward: %s", why);
     if (!y_true || !y_pred || !grad_out || !grad || !workspace)
-        return lfail(PM_EINVAL, "null argument");
+        return pm_fail(PM_EINVAL, "null argument");
     if (workspace_bytes < pm_signal_loss_workspace_bytes(rows))
-        return lfail(PM_ENOMEM, "workspace too small");
+        return pm_fail(PM_ENOMEM, "workspace too small");
     const long long total = (long long)rows * samples;
     hipLaunchKernelGGL(sc_signal_backward_kernel,
                        dim3((total + SC_THREADS - 1) / SC_THREADS),
                        dim3(SC_THREADS), 0, (hipStream_t)stream, y_true,
                        y_pred, (const float*)workspace, grad_out, grad, rows,
                        samples);
-    SC_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }

@@ -3,27 +3,10 @@
 // checks answer on a machine without a GPU.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-
-#include "promonet_hip.h"
+#include "pm_host.h"
 #include "pm_lpc.h"
 
-// pm_api.hip: sets the message pm_last_error() returns
-int pm_fail_message(int code, const char* message);
-
 namespace {
-
-int lfail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int lfail(int code, const char* fmt, ...) {
-    char buffer[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buffer, sizeof(buffer), fmt, ap);
-    va_end(ap);
-    return pm_fail_message(code, buffer);
-}
 
 // workgroups of LPC_THREADS a launch takes: 2^32 - 1 threads in all
 const long long MAX_GRID = 0xffffffffll / LPC_THREADS;
@@ -36,21 +19,21 @@ extern "C" int pm_harmonics_lpc(const float* audio, const int* lengths,
                                 long long stride, int samples, int frames,
                                 int order, void* stream) {
     if (rows < 0 || samples < 0 || frames < 0)
-        return lfail(PM_EINVAL, "negative size");
+        return pm_fail(PM_EINVAL, "negative size");
     if (order < 1 || order > LPC_MAX_ORDER)
-        return lfail(PM_EINVAL, "order %d: the kernel takes orders 1 to %d",
-                     order, LPC_MAX_ORDER);
+        return pm_fail(PM_EINVAL, "order %d: the kernel takes orders 1 to %d",
+                       order, LPC_MAX_ORDER);
     if (stride < samples)
-        return lfail(PM_EINVAL, "the row stride is below the row's length");
+        return pm_fail(PM_EINVAL, "the row stride is below the row's length");
     const long long total = (long long)rows * frames;
     if ((total + LPC_WAVES - 1) / LPC_WAVES > MAX_GRID)
-        return lfail(PM_EINVAL, "too many frames");
+        return pm_fail(PM_EINVAL, "too many frames");
     if (total == 0) return PM_OK;
     if (!audio || !window || !table || !features)
-        return lfail(PM_EINVAL, "null argument");
-    if (((uintptr_t)window & 15) || ((uintptr_t)table & 15))
-        return lfail(PM_EINVAL, "the window and the table must be 16-byte "
-                     "aligned");
+        return pm_fail(PM_EINVAL, "null argument");
+    if (!pm_aligned16(window) || !pm_aligned16(table))
+        return pm_fail(PM_EINVAL, "the window and the table must be 16-byte "
+                       "aligned");
     LpcArgs a;
     a.x = audio; a.lengths = lengths; a.window = window; a.table = table;
     a.out = features; a.coefficients = coefficients; a.stride = stride;
@@ -60,7 +43,7 @@ extern "C" int pm_harmonics_lpc(const float* audio, const int* lengths,
                        dim3(LPC_THREADS), 0, (hipStream_t)stream, a);
     const hipError_t status = hipGetLastError();
     if (status != hipSuccess)
-        return lfail(PM_EHIP, "hm_lpc_kernel launch failed: %s",
-                     hipGetErrorString(status));
+        return pm_fail(PM_EHIP, "hm_lpc_kernel launch failed: %s",
+                       hipGetErrorString(status));
     return PM_OK;
 }

@@ -2,64 +2,22 @@
 // Kernels: pm_vocos.h. Reference: promonet/model/vocos.py.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <map>
-#include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
 
-#include "promonet_hip.h"
+#include "pm_host.h"
 #include "pm_vocos.h"
-
-// pm_api.hip: sets the message pm_last_error() returns
-int pm_fail_message(int code, const char* message);
 
 namespace {
 
-int vfail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int vfail(int code, const char* fmt, ...) {
-    char buffer[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buffer, sizeof(buffer), fmt, ap);
-    va_end(ap);
-    return pm_fail_message(code, buffer);
-}
-
-#define VC_TRY(expr)                                                         \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess)                                                \
-            return vfail(PM_EHIP, "%s failed: %s (%s:%d)", #expr,            \
-                         hipGetErrorString(e_), __FILE__, __LINE__);         \
-    } while (0)
-
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 bool known_dtype(int dtype) {
     return dtype == PM_F32 || dtype == PM_F16 || dtype == PM_BF16;
 }
 size_t esz(int dtype) { return dtype == PM_F32 ? 4 : 2; }
-
-hipError_t ensure_lds(const void* kern, int bytes) {
-    static std::mutex guard;
-    static std::map<std::pair<const void*, int>, int> granted;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(guard);
-    int& have = granted[std::make_pair(kern, dev)];
-    if (bytes > have) {
-        e = hipFuncSetAttribute(
-            kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        have = bytes;
-    }
-    return hipSuccess;
-}
 
 template <class F> hipError_t with_elem(int dtype, F&& f) {
     switch (dtype) {
@@ -83,8 +41,8 @@ hipError_t pack(int dtype, const float* w, void* out, int N, int K, int taps,
     });
 }
 size_t packed_bytes(int dtype, int N, int K, int taps) {
-    return align256((size_t)round_up(N, PM_VOCOS_GEMM_COLS) * taps * K *
-                    esz(dtype));
+    return pm_align256((size_t)round_up(N, PM_VOCOS_GEMM_COLS) * taps * K *
+                       esz(dtype));
 }
 
 hipError_t gemm(int dtype, int taps, bool cf, const VocosGemmArgs& a,
@@ -129,8 +87,8 @@ hipError_t block(int dtype, const VocosBlockArgs& a, hipStream_t s) {
         typedef VocosTile<ET> Tile;
         auto kern = a.rg.map ? vocos_block_kernel<ET, true>
                              : vocos_block_kernel<ET, false>;
-        hipError_t e = ensure_lds(reinterpret_cast<const void*>(kern),
-                                  Tile::SMEM);
+        hipError_t e = pm_ensure_dynamic_lds(
+            reinterpret_cast<const void*>(kern), Tile::SMEM);
         if (e != hipSuccess) return e;
         const int rows = a.B * a.T;
         hipLaunchKernelGGL(kern, dim3((rows + Tile::MT - 1) / Tile::MT),
@@ -181,8 +139,8 @@ hipError_t head(int dtype, const float* x, const void* w, const float* bias,
 }
 
 size_t block_weight_bytes(int dtype, int C, int H) {
-    return 2 * align256((size_t)C * H * esz(dtype)) +
-           align256((size_t)7 * C * 4);
+    return 2 * pm_align256((size_t)C * H * esz(dtype)) +
+           pm_align256((size_t)7 * C * 4);
 }
 
 }  // namespace
@@ -218,29 +176,30 @@ extern "C" int pm_vocos_create(int num_features, int global_channels,
                                int channels, int hidden, int layers,
                                int n_fft, int hop, int dtype,
                                pm_vocos_t* out) {
-    if (!out) return vfail(PM_EINVAL, "null argument");
+    if (!out) return pm_fail(PM_EINVAL, "null argument");
     *out = nullptr;
     if (num_features < 16 || num_features % 16)
-        return vfail(PM_EINVAL,
-                     "features must be a positive multiple of 16, got %d",
-                     num_features);
+        return pm_fail(PM_EINVAL,
+                       "features must be a positive multiple of 16, got %d",
+                       num_features);
     if (global_channels < 1)
-        return vfail(PM_EINVAL, "global channels must be positive, got %d",
-                     global_channels);
+        return pm_fail(PM_EINVAL, "global channels must be positive, got %d",
+                       global_channels);
     if (channels != PM_VOCOS_C)
-        return vfail(PM_EINVAL, "the kernels are built for %d channels, got %d",
-                     PM_VOCOS_C, channels);
+        return pm_fail(PM_EINVAL,
+                       "the kernels are built for %d channels, got %d",
+                       PM_VOCOS_C, channels);
     if (hidden < PM_VOCOS_HC || hidden % PM_VOCOS_HC)
-        return vfail(PM_EINVAL,
-                     "pointwise channels must be a positive multiple of %d, "
-                     "got %d", PM_VOCOS_HC, hidden);
+        return pm_fail(PM_EINVAL,
+                       "pointwise channels must be a positive multiple of %d, "
+                       "got %d", PM_VOCOS_HC, hidden);
     if (layers < 0 || layers > 64)
-        return vfail(PM_EINVAL, "layers must be in [0, 64], got %d", layers);
+        return pm_fail(PM_EINVAL, "layers must be in [0, 64], got %d", layers);
     if (n_fft != PM_VOCOS_NFFT || hop != PM_VOCOS_HOP)
-        return vfail(PM_EINVAL, "the iSTFT is built for n_fft %d, hop %d",
-                     PM_VOCOS_NFFT, PM_VOCOS_HOP);
+        return pm_fail(PM_EINVAL, "the iSTFT is built for n_fft %d, hop %d",
+                       PM_VOCOS_NFFT, PM_VOCOS_HOP);
     if (!known_dtype(dtype))
-        return vfail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
+        return pm_fail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
     auto* h = new pm_vocos_s();
     h->F = num_features; h->G = global_channels; h->C = channels;
     h->H = hidden; h->layers = layers; h->dtype = dtype;
@@ -288,10 +247,11 @@ extern "C" int pm_vocos_destroy(pm_vocos_t h) {
 extern "C" int pm_vocos_load_tensor(pm_vocos_t h, const char* name,
                                     const float* dev, const int64_t* shape,
                                     int ndim, void* stream) {
-    if (!h || !name || !dev || !shape) return vfail(PM_EINVAL, "null argument");
+    if (!h || !name || !dev || !shape)
+        return pm_fail(PM_EINVAL, "null argument");
     auto it = h->tensors.find(name);
     if (it == h->tensors.end())
-        return vfail(PM_EINVAL, "unexpected tensor %s", name);
+        return pm_fail(PM_EINVAL, "unexpected tensor %s", name);
     auto& t = it->second;
     bool same = (size_t)ndim == t.shape.size();
     size_t numel = 1;
@@ -299,19 +259,19 @@ extern "C" int pm_vocos_load_tensor(pm_vocos_t h, const char* name,
         numel *= t.shape[d];
         if (same && shape[d] != t.shape[d]) same = false;
     }
-    if (!same) return vfail(PM_EINVAL, "%s: unexpected shape", name);
-    if (!t.data) VC_TRY(hipMalloc(&t.data, numel * 4));
-    VC_TRY(hipMemcpyAsync(t.data, dev, numel * 4, hipMemcpyDeviceToDevice,
-                          (hipStream_t)stream));
+    if (!same) return pm_fail(PM_EINVAL, "%s: unexpected shape", name);
+    if (!t.data) PM_HIP_TRY(hipMalloc(&t.data, numel * 4));
+    PM_HIP_TRY(hipMemcpyAsync(t.data, dev, numel * 4, hipMemcpyDeviceToDevice,
+                              (hipStream_t)stream));
     h->finalized = false;
     return PM_OK;
 }
 
 extern "C" int pm_vocos_finalize(pm_vocos_t h, void* stream) {
-    if (!h) return vfail(PM_EINVAL, "null argument");
+    if (!h) return pm_fail(PM_EINVAL, "null argument");
     for (auto& kv : h->tensors)
         if (!kv.second.data)
-            return vfail(PM_ESTATE, "%s was not loaded", kv.first.c_str());
+            return pm_fail(PM_ESTATE, "%s was not loaded", kv.first.c_str());
     hipStream_t s = (hipStream_t)stream;
     const int d = h->dtype, C = h->C, H = h->H;
     const size_t pre = packed_bytes(d, C, h->F, 7);
@@ -319,28 +279,30 @@ extern "C" int pm_vocos_finalize(pm_vocos_t h, void* stream) {
     const size_t hd = packed_bytes(d, PM_VOCOS_HEAD_OUT, C, 1);
     const size_t per = block_weight_bytes(d, C, H);
     const size_t total = pre + emb + hd + per * h->layers;
-    if (!h->packed) VC_TRY(hipMalloc(&h->packed, total));
+    if (!h->packed) PM_HIP_TRY(hipMalloc(&h->packed, total));
     char* base = (char*)h->packed;
-    VC_TRY(pack(d, h->at("conv_pre.weight"), base, C, h->F, 7, s));
+    PM_HIP_TRY(pack(d, h->at("conv_pre.weight"), base, C, h->F, 7, s));
     h->conv_pre = base;
     base += pre;
-    VC_TRY(pack(d, h->at("backbone.embed.weight"), base, C, C, 7, s));
+    PM_HIP_TRY(pack(d, h->at("backbone.embed.weight"), base, C, C, 7, s));
     h->embed = base;
     base += emb;
-    VC_TRY(pack(d, h->at("head.out.weight"), base, PM_VOCOS_HEAD_OUT, C, 1, s));
+    PM_HIP_TRY(pack(d, h->at("head.out.weight"), base, PM_VOCOS_HEAD_OUT, C, 1,
+                    s));
     h->head = base;
     base += hd;
     h->w1.clear(); h->w2.clear(); h->dw.clear();
-    const size_t wsz = align256((size_t)C * H * esz(d));
+    const size_t wsz = pm_align256((size_t)C * H * esz(d));
     for (int i = 0; i < h->layers; ++i) {
-        VC_TRY(pack(d, h->at(layer_key(i, "pwconv1.weight")), base, H, C, 1, s));
-        VC_TRY(pack(d, h->at(layer_key(i, "pwconv2.weight")), base + wsz, C, H,
-                    1, s));
+        PM_HIP_TRY(pack(d, h->at(layer_key(i, "pwconv1.weight")), base, H, C,
+                        1, s));
+        PM_HIP_TRY(pack(d, h->at(layer_key(i, "pwconv2.weight")), base + wsz,
+                        C, H, 1, s));
         float* dw = (float*)(base + 2 * wsz);
         hipLaunchKernelGGL(vocos_dw_pack_kernel, dim3((7 * C + 255) / 256),
                            dim3(256), 0, s, h->at(layer_key(i, "dwconv.weight")),
                            dw, C);
-        VC_TRY(hipGetLastError());
+        PM_HIP_TRY(hipGetLastError());
         h->w1.push_back(base);
         h->w2.push_back(base + wsz);
         h->dw.push_back(dw);
@@ -356,9 +318,9 @@ extern "C" size_t pm_vocos_workspace_bytes(pm_vocos_t h, int batch,
                                            int frames) {
     if (!h || batch < 1 || frames < 1) return 0;
     const size_t rows = (size_t)batch * frames;
-    return 2 * align256(rows * h->C * 4) +
-           align256(rows * PM_VOCOS_HEAD_OUT * 4) +
-           align256((size_t)batch * h->C * 4);
+    return 2 * pm_align256(rows * h->C * 4) +
+           pm_align256(rows * PM_VOCOS_HEAD_OUT * 4) +
+           pm_align256((size_t)batch * h->C * 4);
 }
 
 // the uniform workspace | row map (rows x 16 bytes) | offsets (B + 1)
@@ -366,8 +328,8 @@ extern "C" size_t pm_vocos_ragged_workspace_bytes(pm_vocos_t h, int batch,
                                                   int frames) {
     const size_t uniform = pm_vocos_workspace_bytes(h, batch, frames);
     if (!uniform) return 0;
-    return uniform + align256((size_t)batch * frames * sizeof(VocosRow)) +
-           align256(((size_t)batch + 1) * 4);
+    return uniform + pm_align256((size_t)batch * frames * sizeof(VocosRow)) +
+           pm_align256(((size_t)batch + 1) * 4);
 }
 
 // lengths null: the uniform batch; else the ragged one, rows packed
@@ -377,36 +339,36 @@ static int vocos_forward(pm_vocos_t h, const float* features,
                          int batch, int frames, void* workspace,
                          size_t workspace_bytes, void* stream) {
     if (!h || !features || !audio || (ragged && !lengths))
-        return vfail(PM_EINVAL, "null argument");
+        return pm_fail(PM_EINVAL, "null argument");
     if (!h->finalized)
-        return vfail(PM_ESTATE, "pm_vocos_finalize not called");
+        return pm_fail(PM_ESTATE, "pm_vocos_finalize not called");
     if (batch < 1 || frames < 1)
-        return vfail(PM_EINVAL, "batch and frames must be positive");
+        return pm_fail(PM_EINVAL, "batch and frames must be positive");
     if (global_features && global_batch != 1 && global_batch != batch)
-        return vfail(PM_EINVAL, "global batch must be 1 or batch");
+        return pm_fail(PM_EINVAL, "global batch must be 1 or batch");
     const size_t uniform = pm_vocos_workspace_bytes(h, batch, frames);
     if (!workspace || workspace_bytes <
             (ragged ? pm_vocos_ragged_workspace_bytes(h, batch, frames)
                     : uniform))
-        return vfail(PM_ENOMEM, "workspace too small");
+        return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t rows = (size_t)batch * frames;
     const int C = h->C, d = h->dtype;
     char* ws = (char*)workspace;
     float* x0 = (float*)ws;
-    float* x1 = (float*)(ws + align256(rows * C * 4));
-    float* logits = (float*)(ws + 2 * align256(rows * C * 4));
+    float* x1 = (float*)(ws + pm_align256(rows * C * 4));
+    float* logits = (float*)(ws + 2 * pm_align256(rows * C * 4));
     float* cond = (float*)((char*)logits +
-                           align256(rows * PM_VOCOS_HEAD_OUT * 4));
+                           pm_align256(rows * PM_VOCOS_HEAD_OUT * 4));
     float* frames_buf = x0;         // 2 x rows x 512 == rows x 1024 floats
     VocosRagged rg = {nullptr, nullptr};
     if (ragged) {
         VocosRow* map = (VocosRow*)(ws + uniform);
-        int* off = (int*)(ws + uniform + align256(rows * sizeof(VocosRow)));
+        int* off = (int*)(ws + uniform + pm_align256(rows * sizeof(VocosRow)));
         hipLaunchKernelGGL(vocos_rowmap_kernel,
                            dim3((frames + 255) / 256, batch), dim3(256), 0, s,
                            lengths, off, map, batch, frames);
-        VC_TRY(hipGetLastError());
+        PM_HIP_TRY(hipGetLastError());
         rg.map = map;
         rg.off = off;
     }
@@ -419,22 +381,22 @@ static int vocos_forward(pm_vocos_t h, const float* features,
                            dim3(256), 0, s, global_features,
                            h->at("cond.weight"), h->at("cond.bias"), cond,
                            h->G, C);
-        VC_TRY(hipGetLastError());
+        PM_HIP_TRY(hipGetLastError());
     }
     VocosGemmArgs g = {};
     g.x = features; g.w = h->conv_pre; g.bias = h->at("conv_pre.bias");
     g.gbias = global_features ? cond : nullptr; g.gbatch = global_batch;
     g.out = x1; g.B = batch; g.T = frames; g.K = h->F; g.N = C; g.ldo = C;
     g.rg = rg;
-    VC_TRY(gemm(d, 7, true, g, s));
+    PM_HIP_TRY(gemm(d, 7, true, g, s));
     // backbone embed + norm                                vocos.py:96-98
     g = {};
     g.x = x1; g.w = h->embed; g.bias = h->at("backbone.embed.bias");
     g.out = x0; g.B = batch; g.T = frames; g.K = C; g.N = C; g.ldo = C;
     g.rg = rg;
-    VC_TRY(gemm(d, 7, false, g, s));
-    VC_TRY(layer_norm(x0, h->at("backbone.norm.weight"),
-                      h->at("backbone.norm.bias"), (int)rows, total, s));
+    PM_HIP_TRY(gemm(d, 7, false, g, s));
+    PM_HIP_TRY(layer_norm(x0, h->at("backbone.norm.weight"),
+                          h->at("backbone.norm.bias"), (int)rows, total, s));
     float* cur = x0;
     float* nxt = x1;
     for (int i = 0; i < h->layers; ++i) {
@@ -447,16 +409,16 @@ static int vocos_forward(pm_vocos_t h, const float* features,
         a.w2 = h->w2[i]; a.b2 = h->at(layer_key(i, "pwconv2.bias"));
         a.gamma = h->at(layer_key(i, "gamma"));
         a.B = batch; a.T = frames; a.H = h->H; a.rg = rg;
-        VC_TRY(block(d, a, s));
+        PM_HIP_TRY(block(d, a, s));
         std::swap(cur, nxt);
     }
-    VC_TRY(layer_norm(cur, h->at("backbone.final_layer_norm.weight"),
-                      h->at("backbone.final_layer_norm.bias"), (int)rows, total,
-                      s));
+    PM_HIP_TRY(layer_norm(cur, h->at("backbone.final_layer_norm.weight"),
+                          h->at("backbone.final_layer_norm.bias"), (int)rows,
+                          total, s));
     // head: cur -> logits, then the frames overwrite the residual buffers
-    VC_TRY(head(d, cur, h->head, h->at("head.out.bias"),
-                h->at("head.istft.window"), logits, frames_buf, audio, batch,
-                frames, rg, s));
+    PM_HIP_TRY(head(d, cur, h->head, h->at("head.out.bias"),
+                    h->at("head.istft.window"), logits, frames_buf, audio,
+                    batch, frames, rg, s));
     return PM_OK;
 }
 
@@ -498,32 +460,33 @@ extern "C" int pm_convnext_block_cl(
     size_t workspace_bytes, void* stream) {
     if (!x || !y || !dw_w || !dw_b || !ln_w || !ln_b || !w1 || !b1 || !w2 ||
         !b2 || !gamma)
-        return vfail(PM_EINVAL, "null argument");
-    if (x == y) return vfail(PM_EINVAL, "the block cannot run in place");
+        return pm_fail(PM_EINVAL, "null argument");
+    if (x == y) return pm_fail(PM_EINVAL, "the block cannot run in place");
     if (!known_dtype(dtype))
-        return vfail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
+        return pm_fail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
     if (channels != PM_VOCOS_C || hidden < PM_VOCOS_HC ||
         hidden % PM_VOCOS_HC)
-        return vfail(PM_EINVAL, "unsupported block %d x %d", channels, hidden);
+        return pm_fail(PM_EINVAL,
+                       "unsupported block %d x %d", channels, hidden);
     if (batch < 1 || frames < 1)
-        return vfail(PM_EINVAL, "batch and frames must be positive");
+        return pm_fail(PM_EINVAL, "batch and frames must be positive");
     if (!workspace ||
         workspace_bytes < block_weight_bytes(dtype, channels, hidden))
-        return vfail(PM_ENOMEM, "workspace too small");
+        return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)workspace;
-    const size_t wsz = align256((size_t)channels * hidden * esz(dtype));
-    VC_TRY(pack(dtype, w1, base, hidden, channels, 1, s));
-    VC_TRY(pack(dtype, w2, base + wsz, channels, hidden, 1, s));
+    const size_t wsz = pm_align256((size_t)channels * hidden * esz(dtype));
+    PM_HIP_TRY(pack(dtype, w1, base, hidden, channels, 1, s));
+    PM_HIP_TRY(pack(dtype, w2, base + wsz, channels, hidden, 1, s));
     float* dw = (float*)(base + 2 * wsz);
     hipLaunchKernelGGL(vocos_dw_pack_kernel, dim3((7 * channels + 255) / 256),
                        dim3(256), 0, s, dw_w, dw, channels);
-    VC_TRY(hipGetLastError());
+    PM_HIP_TRY(hipGetLastError());
     VocosBlockArgs a = {};
     a.x = x; a.y = y; a.dw_w = dw; a.dw_b = dw_b; a.ln_w = ln_w; a.ln_b = ln_b;
     a.w1 = base; a.b1 = b1; a.w2 = base + wsz; a.b2 = b2; a.gamma = gamma;
     a.B = batch; a.T = frames; a.H = hidden;
-    VC_TRY(block(dtype, a, s));
+    PM_HIP_TRY(block(dtype, a, s));
     return PM_OK;
 }
 
@@ -543,35 +506,35 @@ extern "C" int pm_vocos_gemm_cl(int dtype, int taps, int channels_first,
                                 int in_channels, int out_channels,
                                 void* workspace, size_t workspace_bytes,
                                 void* stream) {
-    if (!x || !w || !bias || !out) return vfail(PM_EINVAL, "null argument");
+    if (!x || !w || !bias || !out) return pm_fail(PM_EINVAL, "null argument");
     if (!known_dtype(dtype))
-        return vfail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
+        return pm_fail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
     // (the instantiations of gemm(): k7 in both layouts, k1 channels-last)
     if (taps != 1 && taps != 7)
-        return vfail(PM_EINVAL, "taps must be 1 or 7, got %d", taps);
+        return pm_fail(PM_EINVAL, "taps must be 1 or 7, got %d", taps);
     if (channels_first && taps != 7)
-        return vfail(PM_EINVAL, "channels-first input needs taps 7");
+        return pm_fail(PM_EINVAL, "channels-first input needs taps 7");
     if (batch < 1 || frames < 1)
-        return vfail(PM_EINVAL, "batch and frames must be positive");
+        return pm_fail(PM_EINVAL, "batch and frames must be positive");
     if (in_channels < 16 || in_channels % 16)
-        return vfail(PM_EINVAL,
-                     "input channels must be a positive multiple of 16, got %d",
-                     in_channels);
+        return pm_fail(PM_EINVAL,
+                       "input channels must be a positive multiple of 16, got %d",
+                       in_channels);
     if (out_channels < 1)
-        return vfail(PM_EINVAL, "output channels must be positive, got %d",
-                     out_channels);
+        return pm_fail(PM_EINVAL, "output channels must be positive, got %d",
+                       out_channels);
     if (gbias && gbatch != 1 && gbatch != batch)
-        return vfail(PM_EINVAL, "global batch must be 1 or batch");
+        return pm_fail(PM_EINVAL, "global batch must be 1 or batch");
     if (!workspace || workspace_bytes < pm_vocos_gemm_workspace_bytes(
             dtype, taps, in_channels, out_channels))
-        return vfail(PM_ENOMEM, "workspace too small");
+        return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    VC_TRY(pack(dtype, w, workspace, out_channels, in_channels, taps, s));
+    PM_HIP_TRY(pack(dtype, w, workspace, out_channels, in_channels, taps, s));
     VocosGemmArgs g = {};
     g.x = x; g.w = workspace; g.bias = bias; g.gbias = gbias;
     g.gbatch = gbatch; g.out = out; g.B = batch; g.T = frames;
     g.K = in_channels; g.N = out_channels; g.ldo = out_channels;
-    VC_TRY(gemm(dtype, taps, channels_first != 0, g, s));
+    PM_HIP_TRY(gemm(dtype, taps, channels_first != 0, g, s));
     return PM_OK;
 }
 
@@ -580,8 +543,8 @@ extern "C" size_t pm_vocos_head_workspace_bytes(int dtype, int batch,
     if (!known_dtype(dtype) || batch < 1 || frames < 1) return 0;
     const size_t rows = (size_t)batch * frames;
     return packed_bytes(dtype, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1) +
-           align256(rows * PM_VOCOS_HEAD_OUT * 4) +
-           align256(rows * PM_VOCOS_NFFT * 4);
+           pm_align256(rows * PM_VOCOS_HEAD_OUT * 4) +
+           pm_align256(rows * PM_VOCOS_NFFT * 4);
 }
 
 extern "C" int pm_vocos_head(int dtype, const float* x, const float* w,
@@ -590,41 +553,42 @@ extern "C" int pm_vocos_head(int dtype, const float* x, const float* w,
                              void* workspace, size_t workspace_bytes,
                              void* stream) {
     if (!x || !w || !bias || !window || !audio)
-        return vfail(PM_EINVAL, "null argument");
+        return pm_fail(PM_EINVAL, "null argument");
     if (!known_dtype(dtype))
-        return vfail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
+        return pm_fail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
     if (batch < 1 || frames < 1)
-        return vfail(PM_EINVAL, "batch and frames must be positive");
+        return pm_fail(PM_EINVAL, "batch and frames must be positive");
     if (!workspace ||
         workspace_bytes < pm_vocos_head_workspace_bytes(dtype, batch, frames))
-        return vfail(PM_ENOMEM, "workspace too small");
+        return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t rows = (size_t)batch * frames;
     char* base = (char*)workspace;
     char* logits = base + packed_bytes(dtype, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1);
-    char* frames_buf = logits + align256(rows * PM_VOCOS_HEAD_OUT * 4);
-    VC_TRY(pack(dtype, w, base, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1, s));
-    VC_TRY(head(dtype, x, base, bias, window, (float*)logits,
-                (float*)frames_buf, audio, batch, frames,
-                VocosRagged{nullptr, nullptr}, s));
+    char* frames_buf = logits + pm_align256(rows * PM_VOCOS_HEAD_OUT * 4);
+    PM_HIP_TRY(pack(dtype, w, base, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1, s));
+    PM_HIP_TRY(head(dtype, x, base, bias, window, (float*)logits,
+                    (float*)frames_buf, audio, batch, frames,
+                    VocosRagged{nullptr, nullptr}, s));
     return PM_OK;
 }
 
 extern "C" size_t pm_istft_workspace_bytes(int batch, int frames) {
     if (batch < 1 || frames < 1) return 0;
-    return align256((size_t)batch * frames * PM_VOCOS_NFFT * 4);
+    return pm_align256((size_t)batch * frames * PM_VOCOS_NFFT * 4);
 }
 
 extern "C" int pm_istft(const float* spectrum, const float* window,
                         float* audio, int batch, int frames, void* workspace,
                         size_t workspace_bytes, void* stream) {
-    if (!spectrum || !window || !audio) return vfail(PM_EINVAL, "null argument");
+    if (!spectrum || !window || !audio)
+        return pm_fail(PM_EINVAL, "null argument");
     if (batch < 1 || frames < 1)
-        return vfail(PM_EINVAL, "batch and frames must be positive");
+        return pm_fail(PM_EINVAL, "batch and frames must be positive");
     if (!workspace ||
         workspace_bytes < pm_istft_workspace_bytes(batch, frames))
-        return vfail(PM_ENOMEM, "workspace too small");
-    VC_TRY(istft(1, spectrum, window, (float*)workspace, audio, batch, frames,
-                 nullptr, (hipStream_t)stream));
+        return pm_fail(PM_ENOMEM, "workspace too small");
+    PM_HIP_TRY(istft(1, spectrum, window, (float*)workspace, audio, batch,
+                     frames, nullptr, (hipStream_t)stream));
     return PM_OK;
 }

@@ -32,7 +32,7 @@ SKIP = P + 'skip_dense'
 SKIP_GLU = P + 'skip_glu.gate'
 OUT = P + 'output_layer'
 
-# prefix -> weight-normed; the order of fargan_layers() (pm_api.hip)
+# prefix -> weight-normed; the order of fargan_layers() (pm_fargan.hip)
 NORMED = (FWCONV, FWCONV_GLU) + GRU_GLU + (SKIP_GLU,)
 GATES_GLU = (FWCONV_GLU,) + GRU_GLU + (SKIP_GLU,)
 DENSE = CONDITIONING + (FWCONV, SKIP, OUT)

@@ -326,11 +326,38 @@ def test_no_kernel_spills():
         pytest.skip('objects not built here (make)')
     done = subprocess.run(
         [sys.executable, str(root / 'scripts' / 'check_spills.py')] +
-        [str(o) for o in objects if o.name in (
-            'pm_api.o', 'pm_conv_f16.o', 'pm_conv_bf16.o', 'pm_conv_f32.o',
-            'pm_conv_f16_mrf.o', 'pm_conv_bf16_mrf.o')],
+        [str(o) for o in objects],
         capture_output=True, text=True)
     assert done.returncode == 0, done.stderr[-2000:]
+
+
+def test_makefile_objects_are_the_hip_sources():
+    """The Makefile is the one place that lists the library's objects, and it
+    lists every promonet_amd/csrc/*.hip (the variant scripts take the list
+    from it: `make -s objs`)."""
+    import subprocess
+    done = subprocess.run(['make', '-s', 'objs'], cwd=ROOT, check=True,
+                          capture_output=True, text=True)
+    listed = sorted(Path(o).stem for o in done.stdout.split())
+    sources = sorted(
+        p.stem for p in (ROOT / 'promonet_amd' / 'csrc').glob('*.hip'))
+    assert len(sources) >= 16
+    assert listed == sources
+
+
+def test_library_exports_exactly_the_signatures():
+    """The pm_* symbols the built library defines are the entries of
+    _lib.SIGNATURES, no more and no fewer: _lib.lib() resolves every entry, so
+    a library linked from a stale object list does not load at all."""
+    import subprocess
+    if not _lib.LIB_PATH.exists():
+        pytest.skip('library not built here (make)')
+    done = subprocess.run(['nm', '-D', '--defined-only', str(_lib.LIB_PATH)],
+                          check=True, capture_output=True, text=True)
+    exported = {line.split()[-1] for line in done.stdout.splitlines()
+                if line.strip()}
+    exported = {name for name in exported if name.startswith('pm_')}
+    assert exported == set(_lib.SIGNATURES), exported ^ set(_lib.SIGNATURES)
 
 
 def test_debug_hooks_are_off_in_a_production_process():
