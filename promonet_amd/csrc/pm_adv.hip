@@ -45,15 +45,13 @@ const char* check_entries(const void* const* a, const void* const* b,
     return nullptr;
 }
 
-// Offsets of the three parts of the workspace
-struct Layout { size_t wide, partials, total; };
+// The three parts of the workspace
+struct Layout { AdvMeta* meta; double* wide; float* partials; size_t total; };
 
-Layout layout_of(int count, long long groups) {
-    Layout l;
-    l.wide = pm_align256((size_t)count * sizeof(AdvMeta));
-    l.partials = l.wide + pm_align256((size_t)count * sizeof(double));
-    l.total = l.partials + pm_align256((size_t)groups * sizeof(float));
-    return l;
+Layout layout_of(int count, long long groups, void* base) {
+    PmCarve c(base);
+    return {c.take<AdvMeta>(count), c.take<double>(count),
+            c.take<float>((size_t)groups), c.used};
 }
 
 // Adds entry k to the table; false when the launch is full
@@ -76,7 +74,7 @@ extern "C" size_t pm_multi_mean_workspace_bytes(const long long* numel,
                                                 int count) {
     long long groups;
     if (check_list(numel, count, &groups)) return 0;
-    return layout_of(count, groups).total;
+    return layout_of(count, groups, nullptr).total;
 }
 
 extern "C" int pm_multi_mean(const void* const* a, const void* const* b,
@@ -91,12 +89,9 @@ extern "C" int pm_multi_mean(const void* const* a, const void* const* b,
         return pm_fail(PM_EINVAL, "pm_multi_mean: %s", why);
     if (!out || !workspace)
         return pm_fail(PM_EINVAL, "pm_multi_mean: null argument");
-    const Layout l = layout_of(count, groups);
+    const Layout l = layout_of(count, groups, workspace);
     if (workspace_bytes < l.total)
         return pm_fail(PM_EINVAL, "pm_multi_mean: workspace too small");
-    AdvMeta* meta = (AdvMeta*)workspace;
-    double* wide = (double*)((char*)workspace + l.wide);
-    float* partials = (float*)((char*)workspace + l.partials);
     AdvTable t;
     long long base = 0;
     int k = 0;
@@ -119,13 +114,13 @@ extern "C" int pm_multi_mean(const void* const* a, const void* const* b,
         }
         hipLaunchKernelGGL(adv_partials_kernel, dim3(launch_groups),
                            dim3(ADV_THREADS), 0, (hipStream_t)stream, t,
-                           partials, meta);
+                           l.partials, l.meta);
         PM_HIP_TRY(hipGetLastError());
         base += launch_groups;
     }
     hipLaunchKernelGGL(adv_final_kernel, dim3(1), dim3(ADV_FINAL_THREADS), 0,
-                       (hipStream_t)stream, (const float*)partials,
-                       (const AdvMeta*)meta, wide, count, out);
+                       (hipStream_t)stream, (const float*)l.partials,
+                       (const AdvMeta*)l.meta, l.wide, count, out);
     PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }

@@ -640,8 +640,12 @@ extern "C" int pm_hifigan_features_cl_channels(pm_hifigan_t h) {
     return h ? h->cfp : 0;
 }
 
+// channels-last features | speaker bias | four activation buffers | the
+// skewed walks' scratch (or none)
 struct Plan {
-    size_t off_feat, off_gbias, off_buf, buf_elems, off_scratch, scratch, total;
+    float *feat, *gbias, *buf[4];
+    char* scratch;
+    size_t scratch_bytes, total;
 };
 
 // Scratch of the skewed whole-Block walk: one workgroup per (utterance,
@@ -651,7 +655,7 @@ static size_t walk_scratch_bytes(int B) {
     return (size_t)std::max(B, cus > 0 ? cus : 256) * PM_SKEW_WG_SCRATCH;
 }
 
-static Plan make_plan(pm_hifigan_t h, int B, int T) {
+static Plan make_plan(pm_hifigan_t h, int B, int T, void* base) {
     Plan p;
     size_t mx = (size_t)T * h->c0p;
     size_t L = T;
@@ -659,11 +663,10 @@ static Plan make_plan(pm_hifigan_t h, int B, int T) {
         L *= s.r;
         mx = std::max(mx, L * (size_t)s.cout_pad);
     }
-    p.buf_elems = pm_align256((size_t)B * mx * sizeof(float)) / sizeof(float);
-    p.off_feat = 0;
-    p.off_gbias = pm_align256((size_t)B * T * h->cfp * sizeof(float));
-    p.off_buf = p.off_gbias + pm_align256((size_t)B * h->c0p * sizeof(float));
-    p.off_scratch = p.off_buf + 4 * p.buf_elems * sizeof(float);
+    PmCarve c(base);
+    p.feat = c.take<float>((size_t)B * T * h->cfp);
+    p.gbias = c.take<float>((size_t)B * h->c0p);
+    for (float*& b : p.buf) b = c.take<float>((size_t)B * mx);
     // (the skewed walks are only planned with >= 4 steps per segment,
     // max(1, CUs / B) segments per utterance: short calls - a streaming
     // frame, a single 2 s utterance - carry no scratch. The planner tests
@@ -674,17 +677,18 @@ static Plan make_plan(pm_hifigan_t h, int B, int T) {
     {
         const int cus = pm_device_cus();
         const size_t nseg = std::max(1, (cus > 0 ? cus : 256) / B);
-        p.scratch = pm_force().walk_nseg || pm_force().skew > 0 ||
-                    L / 256 / nseg >= 4
+        p.scratch_bytes = pm_force().walk_nseg || pm_force().skew > 0 ||
+                          L / 256 / nseg >= 4
             ? walk_scratch_bytes(B) : 0;   // (a forced walk / skew: tests)
     }
-    p.total = p.off_scratch + p.scratch;
+    p.scratch = p.scratch_bytes ? c.take<char>(p.scratch_bytes) : nullptr;
+    p.total = c.used;
     return p;
 }
 
 extern "C" size_t pm_hifigan_workspace_bytes(pm_hifigan_t h, int B, int T) {
     if (!h || B < 1 || T < 1) return 0;
-    return make_plan(h, B, T).total;
+    return make_plan(h, B, T, nullptr).total;
 }
 
 static int forward_impl(
@@ -698,16 +702,11 @@ static int forward_impl(
     if (B < 1 || T < 1) return pm_fail(PM_EINVAL, "empty batch or sequence");
     if (gbatch != 1 && gbatch != B)
         return pm_fail(PM_EINVAL, "global_batch must be 1 or batch");
-    const Plan p = make_plan(h, B, T);
+    const Plan p = make_plan(h, B, T, ws);
     if (ws_bytes < p.total)
         return pm_fail(PM_ENOMEM,
                        "workspace %zu < required %zu", ws_bytes, p.total);
-    char* base = (char*)ws;
-    float* feat = (float*)(base + p.off_feat);
-    float* gbias = (float*)(base + p.off_gbias);
-    float* buf[4];
-    for (int i = 0; i < 4; ++i)
-        buf[i] = (float*)(base + p.off_buf) + (size_t)i * p.buf_elems;
+    float* const* buf = p.buf;
 
     const float* feat_cl = features;
     if (!features_cl) {
@@ -715,21 +714,21 @@ static int forward_impl(
         PROF(h, s, "to_channels_last", 0,
              (double)B * T * (h->cfg.num_features + h->cfp) * 4, {
             hipLaunchKernelGGL(pm_to_channels_last_kernel, grid, dim3(256), 0,
-                               s, features, feat, h->cfg.num_features, T,
+                               s, features, p.feat, h->cfg.num_features, T,
                                h->cfp);
             PM_HIP_TRY(hipGetLastError());
         });
-        feat_cl = feat;
+        feat_cl = p.feat;
     }
     // speaker conditioning as a per-utterance bias of the input conv
     hipLaunchKernelGGL(pm_speaker_bias_kernel, dim3((h->c0p + 3) / 4, gbatch),
-                       dim3(256), 0, s, g, h->spk_w, h->spk_b, gbias,
+                       dim3(256), 0, s, g, h->spk_w, h->spk_b, p.gbias,
                        h->cfg.global_channels, h->c0, h->c0p);
     PM_HIP_TRY(hipGetLastError());
     {
         SingleArgs a = {};
         a.x = feat_cl; a.out = buf[0]; a.w = h->in_conv.w;
-        a.bias = h->in_conv.bias; a.gbias = gbias; a.gbias_batch = gbatch;
+        a.bias = h->in_conv.bias; a.gbias = p.gbias; a.gbias_batch = gbatch;
         a.B = B; a.L = T; a.Lout = T; a.Cin = h->cfp; a.M = h->c0p;
         a.lrelu = 0; a.pad = 3; a.phase_r = 0; a.phase_c = 1;
         a.lengths = lengths; a.len_scale = 1;
@@ -781,8 +780,8 @@ static int forward_impl(
         PmStage d = stage_desc(st.cout_pad, buf[ui], buf[si], B, L, 1, scale,
                                nb, ni);
         d.lengths = lengths; d.len_scale = rate;
-        d.scratch = p.scratch ? base + p.off_scratch : nullptr;
-        d.scratch_bytes = p.scratch;
+        d.scratch = p.scratch;
+        d.scratch_bytes = p.scratch_bytes;
         for (int j = 0; j < nb; ++j) {
             d.blk[j].K = h->cfg.resblock_kernel_sizes[j];
             for (int n = 0; n < ni; ++n) {
@@ -1047,11 +1046,20 @@ extern "C" int pm_prepare_global_features_linear(
 // ---------------------------------------------------------------------------
 // per-kernel entry points
 // ---------------------------------------------------------------------------
-extern "C" size_t pm_op_workspace_bytes(int c_in, int c_out, int k) {
+// One Block iteration: two packed weight streams (fp32-sized, + bias steps)
+// and two padded biases
+struct IterationLayout { float *w1, *w2, *b1, *b2; size_t total; };
+static IterationLayout iteration_layout(int c_in, int c_out, int k,
+                                        void* base) {
     const size_t ci = pm_pad32(c_in), co = pm_pad32(c_out);
-    // two packed weight streams (fp32-sized, + bias steps) and two padded biases
-    return 2 * pm_align256((ci * co * (size_t)k + co * 16) * 4) +
-           2 * pm_align256(co * 64 * 4);
+    PmCarve c(base);
+    return {c.take<float>(ci * co * k + co * 16),
+            c.take<float>(ci * co * k + co * 16), c.take<float>(co * 64),
+            c.take<float>(co * 64), c.used};
+}
+
+extern "C" size_t pm_op_workspace_bytes(int c_in, int c_out, int k) {
+    return iteration_layout(c_in, c_out, k, nullptr).total;
 }
 
 // Pack one Block iteration - conv1 and conv2 weights (C, C, K) and biases (C)
@@ -1065,18 +1073,14 @@ static int pack_iteration(
     ConvGeom g;
     g.mode = 0; g.cout = g.cin = C; g.k = K; g.cout_pad = g.cin_pad = g.M = Cp;
     g.kt = K; g.ch = std::min(Cp, 64); g.bias_step = true;
-    const size_t stream_bytes =
-        pm_align256(((size_t)Cp * Cp * K + Cp * 16) * 4);
-    void* q1 = base; void* q2 = base + stream_bytes;
-    float* pb1 = (float*)(base + 2 * stream_bytes);
-    float* pb2 = pb1 + pm_align256(Cp * 64 * 4) / 4;
-    PM_HIP_TRY(pack_weights(dtype, g, w1, q1, s));
-    PM_HIP_TRY(pack_weights(dtype, g, w2, q2, s));
-    PM_HIP_TRY(pad_bias(b1, pb1, C, Cp, 1, s));
-    PM_HIP_TRY(pad_bias(b2, pb2, C, Cp, 1, s));
-    PM_HIP_TRY(pack_bias_step(dtype, g, pb1, q1, s));
-    PM_HIP_TRY(pack_bias_step(dtype, g, pb2, q2, s));
-    *p1 = q1; *p2 = q2;
+    const IterationLayout l = iteration_layout(C, C, K, base);
+    PM_HIP_TRY(pack_weights(dtype, g, w1, l.w1, s));
+    PM_HIP_TRY(pack_weights(dtype, g, w2, l.w2, s));
+    PM_HIP_TRY(pad_bias(b1, l.b1, C, Cp, 1, s));
+    PM_HIP_TRY(pad_bias(b2, l.b2, C, Cp, 1, s));
+    PM_HIP_TRY(pack_bias_step(dtype, g, l.b1, l.w1, s));
+    PM_HIP_TRY(pack_bias_step(dtype, g, l.b2, l.w2, s));
+    *p1 = l.w1; *p2 = l.w2;
     return PM_OK;
 }
 
@@ -1134,10 +1138,10 @@ static int block_cl_impl(
     if ((K != 3 && K != 7 && K != 11) || niter < 1 || niter > 3)
         return pm_fail(PM_EINVAL,
                        "kernel %d / %d iterations unsupported", K, niter);
-    if (ws_bytes < 3 * pm_op_workspace_bytes(C, C, K))
+    const size_t per = iteration_layout(C, C, K, nullptr).total;
+    if (ws_bytes < 3 * per)
         return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const size_t per = pm_op_workspace_bytes(C, C, K);
     PmStage d = stage_desc(Cp, x, out, B, L, mode, scale, 1, niter);
     d.blk[0].K = K;
     for (int n = 0; n < niter; ++n) {
@@ -1211,7 +1215,7 @@ extern "C" int pm_mrf_cl(
     if (Cp != 32)
         return pm_fail(PM_EINVAL, "whole-MRF kernel exists for <= 32 channels");
     if (niter < 1 || niter > 3) return pm_fail(PM_EINVAL, "1..3 dilations");
-    const size_t per = pm_op_workspace_bytes(C, C, 11);
+    const size_t per = iteration_layout(C, C, 11, nullptr).total;
     if (ws_bytes < 3 * (size_t)niter * per)
         return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
@@ -1250,6 +1254,18 @@ extern "C" int pm_mrf_cl(
 // of the (B|1, G) global features, added as a per-utterance bias.
 //   x_cl (B, L, pad32(c_in)), w (c_out, c_in, 7), bias (c_out),
 //   global (gbatch, G), ws_w (c_out, G), ws_b (c_out)  ->  (B, L, pad32(c_out))
+// The weights and the bias lie where a Block iteration (c_in, c_out, 7) has
+// its first stream and its first bias; the speaker bias (B, pad32(c_out))
+// follows that whole iteration, the public pm_op_workspace_bytes
+struct InputConvLayout { float *w, *bias, *gbias; size_t total; };
+static InputConvLayout input_conv_layout(int c_in, int c_out, int B,
+                                         void* base) {
+    const IterationLayout it = iteration_layout(c_in, c_out, 7, base);
+    PmCarve c(base ? (char*)base + it.total : nullptr);
+    return {it.w1, it.b1, c.take<float>((size_t)B * pm_pad32(c_out)),
+            it.total + c.used};
+}
+
 extern "C" int pm_input_conv_cl(
     int dtype, const float* x, float* out, const float* w, const float* bias,
     const float* global, const float* ws_w, const float* ws_b, int gbatch,
@@ -1262,8 +1278,8 @@ extern "C" int pm_input_conv_cl(
     const int cip = pm_pad32(c_in), cop = pm_pad32(c_out);
     if (cop % 64 && cop != 32)
         return pm_fail(PM_EINVAL, "output channels %d unsupported", c_out);
-    if (ws_bytes < pm_op_workspace_bytes(c_in, c_out, 7) +
-                       pm_align256((size_t)B * cop * 4))
+    const InputConvLayout l = input_conv_layout(c_in, c_out, B, ws);
+    if (ws_bytes < l.total)
         return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     ConvGeom g;
@@ -1271,22 +1287,30 @@ extern "C" int pm_input_conv_cl(
     g.cout_pad = g.M = cop; g.cin_pad = cip; g.kt = 7;
     g.ch = (cip % 64 == 0) ? 64 : 32;
     const int cfg = single_cfg(g.M, g.ch, 1);
-    char* base = (char*)ws;
-    const size_t wsz = 2 * pm_align256(((size_t)cip * cop * 7 + cop * 16) * 4);
-    float* pb = (float*)(base + wsz);
-    float* gbias = (float*)(base + pm_op_workspace_bytes(c_in, c_out, 7));
-    PM_HIP_TRY(pack_weights(dtype, g, w, base, s));
-    PM_HIP_TRY(pad_bias(bias, pb, c_out, cop, 1, s));
+    PM_HIP_TRY(pack_weights(dtype, g, w, l.w, s));
+    PM_HIP_TRY(pad_bias(bias, l.bias, c_out, cop, 1, s));
     hipLaunchKernelGGL(pm_speaker_bias_kernel, dim3((cop + 3) / 4, gbatch),
-                       dim3(256), 0, s, global, ws_w, ws_b, gbias, G, c_out,
+                       dim3(256), 0, s, global, ws_w, ws_b, l.gbias, G, c_out,
                        cop);
     PM_HIP_TRY(hipGetLastError());
     SingleArgs a = {};
-    a.x = x; a.out = out; a.w = base; a.bias = pb; a.gbias = gbias;
+    a.x = x; a.out = out; a.w = l.w; a.bias = l.bias; a.gbias = l.gbias;
     a.gbias_batch = gbatch; a.B = B; a.L = L; a.Lout = L; a.Cin = cip;
     a.M = cop; a.lrelu = 0; a.pad = 3; a.phase_r = 0; a.phase_c = 1;
     PM_HIP_TRY(launch_single(dtype, 0, g.ch, cfg, a, s));
     return PM_OK;
+}
+
+// Packed weights in two fp32-sized streams' room (no bias steps: less than a
+// Block iteration's), then the bias, once per phase
+struct TransposeLayout { float *w, *bias; size_t total; };
+static TransposeLayout transpose_layout(int c_in, int c_out, int r,
+                                        void* base) {
+    const size_t ci = pm_pad32(c_in), co = pm_pad32(c_out);
+    PmCarve c(base);
+    float* w = c.take<float>(ci * co * 2 * r);
+    c.take<float>(ci * co * 2 * r);
+    return {w, c.take<float>(co * r), c.used};
 }
 
 static int conv_transpose_cl_impl(
@@ -1298,6 +1322,9 @@ static int conv_transpose_cl_impl(
     if (r < 2 || (r & 1)) return pm_fail(PM_EINVAL, "rate %d unsupported", r);
     if (ws_bytes < pm_op_workspace_bytes(c_in, c_out, 2 * r))
         return pm_fail(PM_ENOMEM, "workspace too small");
+    const TransposeLayout l = transpose_layout(c_in, c_out, r, ws);
+    if (l.total > pm_op_workspace_bytes(c_in, c_out, 2 * r))
+        return pm_fail(PM_ESTATE, "the layout outgrew its public bound");
     hipStream_t s = (hipStream_t)stream;
     ConvGeom g;
     g.mode = 1; g.cout = c_out; g.cin = c_in; g.k = 2 * r;
@@ -1307,14 +1334,10 @@ static int conv_transpose_cl_impl(
     const int cfg = upsample_whole_k(dtype, g)
         ? 4
         : single_cfg(g.M, g.ch, ((r / 2) * g.cout_pad) % 64 == 0);
-    char* base = (char*)ws;
-    const size_t wsz =
-        2 * pm_align256((size_t)g.cin_pad * g.cout_pad * g.k * 4);
-    float* pb = (float*)(base + wsz);
-    PM_HIP_TRY(pack_weights(dtype, g, w, base, s));
-    PM_HIP_TRY(pad_bias(bias, pb, c_out, g.cout_pad, r, s));
+    PM_HIP_TRY(pack_weights(dtype, g, w, l.w, s));
+    PM_HIP_TRY(pad_bias(bias, l.bias, c_out, g.cout_pad, r, s));
     SingleArgs a = {};
-    a.x = x; a.out = out; a.w = base; a.bias = pb; a.gbias = nullptr;
+    a.x = x; a.out = out; a.w = l.w; a.bias = l.bias; a.gbias = nullptr;
     a.gbias_batch = 1; a.B = B; a.L = L; a.Lout = L; a.Cin = g.cin_pad;
     a.M = g.M; a.lrelu = lrelu; a.pad = 1;
     a.phase_c = g.cout_pad; a.phase_p = r / 2; a.phase_r = r;

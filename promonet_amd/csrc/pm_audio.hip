@@ -275,9 +275,15 @@ extern "C" int pm_stft_magnitude(
 // from the FFT workgroup's LDS tile (the (B, 513, T) magnitudes never reach
 // HBM). basis (mels, 513) -> pm_stft_mel_prepare -> `prepared`
 // (pm_stft_mel_scratch_bytes(mels) bytes, reusable)
+struct MelLayout { int* table; float* vals; size_t total; };
+static MelLayout mel_layout(int mels, void* base) {
+    PmCarve c(base);
+    return {c.take<int>((size_t)3 * mels + 1),
+            c.take<float>((size_t)mels * BINS), c.used};
+}
+
 extern "C" size_t pm_stft_mel_scratch_bytes(int mels) {
-    return mels < 1 ? 0 : pm_align256((size_t)(3 * mels + 1) * sizeof(int)) +
-                              pm_align256((size_t)mels * BINS * sizeof(float));
+    return mels < 1 ? 0 : mel_layout(mels, nullptr).total;
 }
 
 // Compact the (mels, 513) filterbank once (per basis): `prepared` then feeds
@@ -288,13 +294,11 @@ extern "C" int pm_stft_mel_prepare(
     if (!basis || !prepared) return pm_fail(PM_EINVAL, "null argument");
     if (mels < 1 || mels > 1024)
         return pm_fail(PM_EINVAL, "1..1024 mel filters");
-    if (prepared_bytes < pm_stft_mel_scratch_bytes(mels))
+    const MelLayout l = mel_layout(mels, prepared);
+    if (prepared_bytes < l.total)
         return pm_fail(PM_ENOMEM, "buffer too small");
-    int* table = (int*)prepared;
-    float* vals = (float*)((char*)prepared +
-                           pm_align256((size_t)(3 * mels + 1) * sizeof(int)));
     hipLaunchKernelGGL(pm_mel_csr_kernel, dim3(1), dim3(256), 0,
-                       (hipStream_t)stream, basis, table, vals, mels, BINS);
+                       (hipStream_t)stream, basis, l.table, l.vals, mels, BINS);
     PM_HIP_TRY(hipGetLastError());
     return PM_OK;
 }
@@ -306,12 +310,10 @@ extern "C" int pm_stft_mel(
     if (mels < 1 || mels > 1024)
         return pm_fail(PM_EINVAL, "1..1024 mel filters");
     hipStream_t s = (hipStream_t)stream;
-    const int* table = (const int*)prepared;
-    const float* vals = (const float*)((const char*)prepared +
-                           pm_align256((size_t)(3 * mels + 1) * sizeof(int)));
+    const MelLayout l = mel_layout(mels, const_cast<void*>(prepared));
     FftArgs a = {};
     a.audio = audio; a.out = out; a.B = B; a.N = N;
-    a.mel_span = table; a.mel_vals = vals; a.rows = mels;
+    a.mel_span = l.table; a.mel_vals = l.vals; a.rows = mels;
     a.use_thr = use_threshold; a.thr = log_threshold;
     return fft_launch<4>(a, s);
 }
@@ -321,12 +323,18 @@ extern "C" int pm_stft_mel(
 // convs: the framed DFT again, its epilogue turning the incoming gradient into
 // the DFT cotangent grad / |X| * (re, im); then the overlap-add of that
 // cotangent against the transposed basis; then the adjoint of the reflect pad.
+struct StftBackwardLayout { char* stft; float *cot, *gpad; size_t total; };
+static StftBackwardLayout stft_backward_layout(int B, int N, void* base) {
+    const size_t T = N / HOP;
+    PmCarve c(base);
+    return {c.take<char>(pm_stft_scratch_bytes(B, N)),   // stft_launch's own
+            c.take<float>((size_t)B * T * DFT_M),        // (B, T, 1088)
+            c.take<float>((size_t)B * (T + 3) * HOP), c.used};
+}
+
 extern "C" size_t pm_stft_backward_scratch_bytes(int B, int N) {
     if (B < 1 || N < HOP) return 0;
-    const size_t T = N / HOP;
-    return pm_stft_scratch_bytes(B, N) +
-           pm_align256((size_t)B * T * DFT_M * sizeof(float)) +
-           pm_align256((size_t)B * (T + 3) * HOP * sizeof(float));
+    return stft_backward_layout(B, N, nullptr).total;
 }
 
 extern "C" int pm_stft_magnitude_backward(
@@ -339,25 +347,21 @@ extern "C" int pm_stft_magnitude_backward(
     hipStream_t s = (hipStream_t)stream;
     const int T = N / HOP;
     const int pad = (NFFT - HOP) / 2;
-    char* base = (char*)scratch;
-    const size_t stft_bytes = pm_stft_scratch_bytes(B, N);
-    float* cot = (float*)(base + stft_bytes);               // (B, T, 1088)
-    float* gpad = (float*)(base + stft_bytes +
-                           pm_align256((size_t)B * T * DFT_M * sizeof(float)));
-    int rc = stft_launch(3, audio, cot, nullptr, B, N, base, stft_bytes, s,
-                         grad_out);
+    const StftBackwardLayout l = stft_backward_layout(B, N, scratch);
+    int rc = stft_launch(3, audio, l.cot, nullptr, B, N, l.stft,
+                         pm_stft_scratch_bytes(B, N), s, grad_out);
     if (rc) return rc;
     DftBasis basis;
     rc = get_dft_basis(&basis, s);
     if (rc) return rc;
     PmDftConv a = {};
-    a.x = cot; a.out = gpad; a.w = basis.backward; a.bias = basis.zeros;
+    a.x = l.cot; a.out = l.gpad; a.w = basis.backward; a.bias = basis.zeros;
     a.B = B; a.L = T; a.Lout = T + 3; a.Cin = DFT_M; a.M = HOP;
     a.pad = 3;
     PM_HIP_TRY(pm_dft_conv(0, a, s));
     const int Np = (T + 3) * HOP;
     hipLaunchKernelGGL(pm_reflect_pad_adjoint_kernel,
-                       dim3((N + 255) / 256, B), dim3(256), 0, s, gpad,
+                       dim3((N + 255) / 256, B), dim3(256), 0, s, l.gpad,
                        grad_audio, N, pad, Np);
     PM_HIP_TRY(hipGetLastError());
     return PM_OK;
@@ -395,12 +399,19 @@ extern "C" int pm_linear_to_mel(
     return PM_OK;
 }
 
+// one maximum and one minimum per FFT workgroup (>= 16 frames each) and
+// utterance
+struct LoudnessLayout { float *group_max, *group_min; size_t total; };
+static LoudnessLayout loudness_layout(int B, int N, void* base) {
+    const size_t groups = ((size_t)(N / HOP) + 15) / 16;
+    PmCarve c(base);
+    return {c.take<float>((size_t)B * groups),
+            c.take<float>((size_t)B * groups), c.used};
+}
+
 extern "C" size_t pm_loudness_scratch_bytes(int B, int N) {
     if (B < 1 || N < HOP) return 0;
-    // one maximum and one minimum per FFT workgroup (>= 16 frames each) and
-    // utterance
-    const size_t groups = ((size_t)(N / HOP) + 15) / 16;
-    return 2 * pm_align256((size_t)B * groups * sizeof(float));
+    return loudness_layout(B, N, nullptr).total;
 }
 
 // Two passes over the audio (4 B / sample each) instead of a (B, 513, T) dB
@@ -426,7 +437,8 @@ extern "C" int pm_loudness(
     hipStream_t s = (hipStream_t)stream;
     FftArgs a = {};
     a.audio = audio; a.out = out; a.B = B; a.N = N;
-    a.group_max = (float*)scratch;
+    const LoudnessLayout l = loudness_layout(B, N, scratch);
+    a.group_max = l.group_max;
     const int frames_per_group = g_fft_frames_per_group;   // both passes
     a.weights = a_weights; a.rows = bands;
     const double step = (double)BINS / (double)bands;   // loudness.py:96
@@ -443,8 +455,7 @@ extern "C" int pm_loudness(
 #endif
     aligned8 = aligned8 && a.band_start[8] == BINS;
     if (aligned8 && g_loudness_passes == 1) {
-        a.group_min = (float*)((char*)scratch +
-                               pm_loudness_scratch_bytes(B, N) / 2);
+        a.group_min = l.group_min;
         int rc = fft_launch<6>(a, s, frames_per_group);
         if (rc) return rc;
         return fft_launch<5>(a, s, frames_per_group);

@@ -272,46 +272,57 @@ extern "C" int pm_fargan_set_mode(pm_fargan_t h, int mode) {
     return PM_OK;
 }
 
-static size_t fargan_state_bytes() {
-    return pm_align256((size_t)FG_MAX_CLUSTERS * FG_CSTATE * 4 + 256);
-}
+// channels-last features | cluster state | its error word | conditioning
+struct FarganLayout {
+    float* features; unsigned* state; unsigned* error; float* cond;
+    size_t total;
+};
+static const size_t FG_STATE_WORDS = (size_t)FG_MAX_CLUSTERS * FG_CSTATE;
+static_assert(FG_STATE_WORDS % 64 == 0, "the error word follows the state");
 
-// (B * T, 512) conditioning vectors of pm_fargan_cond_kernel: fp32-stored
-// conditioning weights only (f16 storage keeps them inside the cluster kernel)
-static size_t fargan_precond_bytes(pm_fargan_t h, int B, int T) {
-    return h->dtype == PM_F16
-        ? 0 : pm_align256((size_t)B * T * 512 * sizeof(float));
+static FarganLayout fargan_layout(pm_fargan_t h, int B, int T, void* base) {
+    PmCarve c(base);
+    // cond: (B * T, 512) conditioning vectors of pm_fargan_cond_kernel,
+    // fp32-stored conditioning weights only (f16 storage keeps them inside
+    // the cluster kernel)
+    return {c.take<float>((size_t)B * T * pm_pad32(h->nfeat + 1)),
+            c.take<unsigned>(FG_STATE_WORDS), c.take<unsigned>(1),
+            h->dtype != PM_F16 ? c.take<float>((size_t)B * T * 512) : nullptr,
+            c.used};
 }
 
 extern "C" size_t pm_fargan_workspace_bytes(pm_fargan_t h, int B, int T) {
     if (!h || B < 1 || T < 1) return 0;
-    return pm_align256((size_t)B * T * pm_pad32(h->nfeat + 1) * sizeof(float)) +
-           fargan_state_bytes() + fargan_precond_bytes(h, B, T);
+    return fargan_layout(h, B, T, nullptr).total;
 }
 
 // st.states_out != null: the stateful instantiations (pm_fargan_forward_stateful)
+// cl: the workspace of the cluster kernels, or null for one workgroup per
+// utterance
 template <class WT>
 static int fargan_launch(
-    pm_fargan_t h, const FarganArgs& a, hipStream_t s, void* cluster_state,
+    pm_fargan_t h, const FarganArgs& a, hipStream_t s, const FarganLayout* cl,
     const FarganState& st) {
     const bool stateful = st.states_out != nullptr;
     FarganWeights<WT> w;
     w.base = (const typename FarganWeights<WT>::S*)h->weights;
     w.base_i = (const typename FarganWeights<WT>::I*)(
         h->weights_i ? h->weights_i : h->weights);
-    if (cluster_state) {
+    if (cl) {
         // counters / payload / error word are re-initialised on every call
-        PM_HIP_TRY(hipMemsetAsync(cluster_state, 0, fargan_state_bytes(), s));
+        // (the state's slot and, straight behind it, the error word's)
+        PM_HIP_TRY(hipMemsetAsync(
+            cl->state, 0, (FG_STATE_WORDS + 64) * sizeof(unsigned), s));
         FarganClusterArgs ca;
         ca.f = a;
-        ca.state = (unsigned*)cluster_state;
-        ca.error = ca.state + (size_t)FG_MAX_CLUSTERS * FG_CSTATE;
+        ca.state = cl->state;
+        ca.error = cl->error;
         ca.precond = nullptr;
         if constexpr (std::is_same<typename FarganWeights<WT>::S, float>::value) {
             // the conditioning network of every frame, ahead of the walk
             FarganCondArgs cn;
             cn.features_cl = a.features_cl; cn.global = a.global;
-            cn.cond = (float*)((char*)cluster_state + fargan_state_bytes());
+            cn.cond = cl->cond;
             cn.B = a.B; cn.T = a.T; cn.cstride = a.cstride; cn.nfeat = a.nfeat;
             cn.G = a.G; cn.global_batch = a.global_batch;
             const size_t cond_lds =
@@ -387,11 +398,9 @@ extern "C" int pm_fargan_check(
     if (!h || !ws) return pm_fail(PM_EINVAL, "null argument");
     if (!fargan_use_cluster(h, B)) return PM_OK;
     unsigned flag = 0;
-    const char* state = (const char*)ws +
-        pm_align256((size_t)B * T * pm_pad32(h->nfeat + 1) * sizeof(float));
     PM_HIP_TRY(hipMemcpyAsync(
-        &flag, state + (size_t)FG_MAX_CLUSTERS * FG_CSTATE * 4, 4,
-        hipMemcpyDeviceToHost, (hipStream_t)stream));
+        &flag, fargan_layout(h, B, T, ws).error, 4, hipMemcpyDeviceToHost,
+        (hipStream_t)stream));
     PM_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     if (flag) return pm_fail(PM_ETIMEOUT, "FARGAN cluster exchange timed out");
     return PM_OK;
@@ -415,26 +424,24 @@ static int fargan_forward_impl(
     hipStream_t s = (hipStream_t)stream;
     const int cpad = pm_pad32(h->nfeat + 1);
     const float* fcl = features;
-    if (!ws || ws_bytes < pm_fargan_workspace_bytes(h, B, T))
+    const FarganLayout l = fargan_layout(h, B, T, ws);
+    if (!ws || ws_bytes < l.total)
         return pm_fail(PM_ENOMEM, "workspace too small");
-    void* cluster_state = fargan_use_cluster(h, B)
-        ? (char*)ws + pm_align256((size_t)B * T * pm_pad32(h->nfeat + 1) *
-                                  sizeof(float))
-        : nullptr;
+    const FarganLayout* cl = fargan_use_cluster(h, B) ? &l : nullptr;
     if (!features_cl) {
-        int rc = pm_to_channels_last(features, (float*)ws, B, h->nfeat + 1, T,
+        int rc = pm_to_channels_last(features, l.features, B, h->nfeat + 1, T,
                                      cpad, s);
         if (rc) return rc;
-        fcl = (const float*)ws;
+        fcl = l.features;
     }
     FarganArgs a;
     a.features_cl = fcl; a.global = g; a.previous = previous; a.out = out;
     a.B = B; a.T = T; a.cstride = cpad; a.nfeat = h->nfeat; a.G = h->G;
     a.global_batch = gbatch; a.previous_batch = pbatch;
     a.lengths = lengths;
-    return h->dtype == PM_F32 ? fargan_launch<float>(h, a, s, cluster_state, st)
-         : h->dtype == PM_F16 ? fargan_launch<_Float16>(h, a, s, cluster_state, st)
-                              : fargan_launch<FgMixed>(h, a, s, cluster_state, st);
+    return h->dtype == PM_F32 ? fargan_launch<float>(h, a, s, cl, st)
+         : h->dtype == PM_F16 ? fargan_launch<_Float16>(h, a, s, cl, st)
+                              : fargan_launch<FgMixed>(h, a, s, cl, st);
 }
 
 extern "C" int pm_fargan_forward(

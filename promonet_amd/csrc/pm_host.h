@@ -30,6 +30,22 @@ static inline bool pm_aligned16(const void* p) {
     return ((uintptr_t)p & 15) == 0;
 }
 
+// A caller-provided workspace is laid out by one function that carves its
+// slots in order: on a null base the carve only counts (the *_bytes entries
+// read `used`), on the caller's pointer it places (the launches). A layout
+// returned as a braced list takes its slots in member order (the elements of
+// a braced list are evaluated left to right), `used` last.
+struct PmCarve {
+    char* base; size_t used = 0;
+    explicit PmCarve(void* b) : base((char*)b) {}
+    // a 256-byte slot of `count` T; null when base is null
+    template <class T> T* take(size_t count) {
+        T* p = base ? (T*)(base + used) : nullptr;
+        used += pm_align256(count * sizeof(T));
+        return p;
+    }
+};
+
 // Do the byte ranges [a, a + an) and [b, b + bn) share a byte? A null or an
 // empty range overlaps nothing.
 static inline bool pm_overlap(

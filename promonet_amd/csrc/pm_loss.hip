@@ -47,9 +47,14 @@ const char* make_plan(int batch, int samples, int fft_size, int hop_size,
     return nullptr;
 }
 
-size_t gradient_bytes(int batch, const ScPlan& p) {
-    return pm_align256((size_t)batch * (p.M + 1) * p.frames * 2 *
-                       sizeof(float));
+// the gradient spectrum (only with_gradient) | the groups' partial sums
+struct ScForwardLayout { float *gradient, *partials; size_t total; };
+ScForwardLayout sc_forward_layout(int batch, const ScPlan& p,
+                                  int with_gradient, void* base) {
+    const size_t gradient = (size_t)batch * (p.M + 1) * p.frames * 2;
+    PmCarve c(base);
+    return {with_gradient ? c.take<float>(gradient) : nullptr,
+            c.take<float>((size_t)batch * p.groups * 2), c.used};
 }
 
 }  // namespace
@@ -59,8 +64,7 @@ extern "C" size_t pm_sc_forward_workspace_bytes(int batch, int samples,
                                                 int with_gradient) {
     ScPlan p;
     if (make_plan(batch, samples, fft_size, hop_size, &p)) return 0;
-    return (with_gradient ? gradient_bytes(batch, p) : 0) +
-           pm_align256((size_t)batch * p.groups * 2 * sizeof(float));
+    return sc_forward_layout(batch, p, with_gradient, nullptr).total;
 }
 
 extern "C" size_t pm_sc_adjoint_workspace_bytes(int batch, int samples,
@@ -99,14 +103,14 @@ extern "C" int pm_sc_forward(const float* x, const float* y,
         return pm_fail(PM_EINVAL, "pm_sc_forward: %s", why);
     if (!x || !y || !window || !twiddle || !sums || !workspace)
         return pm_fail(PM_EINVAL, "null argument");
-    if (workspace_bytes < pm_sc_forward_workspace_bytes(
-            batch, samples, fft_size, hop_size, with_gradient))
+    const ScForwardLayout l =
+        sc_forward_layout(batch, a.p, with_gradient, workspace);
+    if (workspace_bytes < l.total)
         return pm_fail(PM_ENOMEM, "workspace too small");
-    const size_t offset = with_gradient ? gradient_bytes(batch, a.p) : 0;
     a.x = x; a.y = y; a.window = window; a.twiddle = twiddle;
     a.upstream = nullptr; a.s = nullptr;
-    a.G = with_gradient ? (float*)workspace : nullptr;
-    a.partials = (float*)((char*)workspace + offset);
+    a.G = l.gradient;
+    a.partials = l.partials;
     const size_t lds = 4 * (size_t)a.p.fpg * a.p.M * sizeof(float2);
     const int groups = batch * a.p.groups;
     hipLaunchKernelGGL(sc_forward_kernel<true>, dim3(groups),

@@ -138,9 +138,23 @@ hipError_t head(int dtype, const float* x, const void* w, const float* bias,
     return istft(0, logits, window, frames, audio, B, T, rg.off, s);
 }
 
-size_t block_weight_bytes(int dtype, int C, int H) {
-    return 2 * pm_align256((size_t)C * H * esz(dtype)) +
-           pm_align256((size_t)7 * C * 4);
+// one ConvNeXt block's operand-type pointwise weights and depthwise taps
+struct BlockWeights { char* w1; char* w2; float* dw; size_t total; };
+BlockWeights block_weights(int dtype, int C, int H, void* base) {
+    PmCarve c(base);
+    return {c.take<char>((size_t)C * H * esz(dtype)),
+            c.take<char>((size_t)C * H * esz(dtype)),
+            c.take<float>((size_t)7 * C), c.used};
+}
+
+// pm_vocos_head: packed weight | logits (rows x 1026) | frames (rows x 1024)
+struct HeadLayout { char* w; float* logits; float* frames; size_t total; };
+HeadLayout head_layout(int dtype, int batch, int frames, void* base) {
+    const size_t rows = (size_t)batch * frames;
+    PmCarve c(base);
+    return {c.take<char>(packed_bytes(dtype, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1)),
+            c.take<float>(rows * PM_VOCOS_HEAD_OUT),
+            c.take<float>(rows * PM_VOCOS_NFFT), c.used};
 }
 
 }  // namespace
@@ -277,7 +291,7 @@ extern "C" int pm_vocos_finalize(pm_vocos_t h, void* stream) {
     const size_t pre = packed_bytes(d, C, h->F, 7);
     const size_t emb = packed_bytes(d, C, C, 7);
     const size_t hd = packed_bytes(d, PM_VOCOS_HEAD_OUT, C, 1);
-    const size_t per = block_weight_bytes(d, C, H);
+    const size_t per = block_weights(d, C, H, nullptr).total;
     const size_t total = pre + emb + hd + per * h->layers;
     if (!h->packed) PM_HIP_TRY(hipMalloc(&h->packed, total));
     char* base = (char*)h->packed;
@@ -292,44 +306,62 @@ extern "C" int pm_vocos_finalize(pm_vocos_t h, void* stream) {
     h->head = base;
     base += hd;
     h->w1.clear(); h->w2.clear(); h->dw.clear();
-    const size_t wsz = pm_align256((size_t)C * H * esz(d));
     for (int i = 0; i < h->layers; ++i) {
-        PM_HIP_TRY(pack(d, h->at(layer_key(i, "pwconv1.weight")), base, H, C,
+        const BlockWeights bw = block_weights(d, C, H, base);
+        PM_HIP_TRY(pack(d, h->at(layer_key(i, "pwconv1.weight")), bw.w1, H, C,
                         1, s));
-        PM_HIP_TRY(pack(d, h->at(layer_key(i, "pwconv2.weight")), base + wsz,
-                        C, H, 1, s));
-        float* dw = (float*)(base + 2 * wsz);
+        PM_HIP_TRY(pack(d, h->at(layer_key(i, "pwconv2.weight")), bw.w2, C, H,
+                        1, s));
         hipLaunchKernelGGL(vocos_dw_pack_kernel, dim3((7 * C + 255) / 256),
                            dim3(256), 0, s, h->at(layer_key(i, "dwconv.weight")),
-                           dw, C);
+                           bw.dw, C);
         PM_HIP_TRY(hipGetLastError());
-        h->w1.push_back(base);
-        h->w2.push_back(base + wsz);
-        h->dw.push_back(dw);
-        base += per;
+        h->w1.push_back(bw.w1);
+        h->w2.push_back(bw.w2);
+        h->dw.push_back(bw.dw);
+        base += bw.total;
     }
     h->finalized = true;
     return PM_OK;
 }
 
-// residual ping-pong (2 x rows x C fp32, reused as the iSTFT frames) | head
-// logits (rows x 1026) | cond output (B x C)
+// residual ping-pong (2 x rows x C fp32) | head logits (rows x 1026) | cond
+// output (B x C); ragged: | row map (rows x 16 bytes) | offsets (B + 1)
+struct VocosLayout {
+    float *x0, *x1, *logits, *cond, *frames;
+    VocosRow* map; int* off;
+    size_t total;
+};
+static VocosLayout vocos_layout(pm_vocos_t h, int batch, int frames,
+                                bool ragged, void* base) {
+    const size_t rows = (size_t)batch * frames;
+    PmCarve c(base);
+    VocosLayout l = {};
+    l.x0 = c.take<float>(rows * h->C);
+    l.x1 = c.take<float>(rows * h->C);
+    l.logits = c.take<float>(rows * PM_VOCOS_HEAD_OUT);
+    l.cond = c.take<float>((size_t)batch * h->C);
+    // the iSTFT frames overwrite the residual buffers, both dead once the
+    // head has its logits: 2 x rows x 512 == rows x 1024 floats
+    l.frames = l.x0;
+    if (ragged) {
+        l.map = c.take<VocosRow>(rows);
+        l.off = c.take<int>((size_t)batch + 1);
+    }
+    l.total = c.used;
+    return l;
+}
+
 extern "C" size_t pm_vocos_workspace_bytes(pm_vocos_t h, int batch,
                                            int frames) {
     if (!h || batch < 1 || frames < 1) return 0;
-    const size_t rows = (size_t)batch * frames;
-    return 2 * pm_align256(rows * h->C * 4) +
-           pm_align256(rows * PM_VOCOS_HEAD_OUT * 4) +
-           pm_align256((size_t)batch * h->C * 4);
+    return vocos_layout(h, batch, frames, false, nullptr).total;
 }
 
-// the uniform workspace | row map (rows x 16 bytes) | offsets (B + 1)
 extern "C" size_t pm_vocos_ragged_workspace_bytes(pm_vocos_t h, int batch,
                                                   int frames) {
-    const size_t uniform = pm_vocos_workspace_bytes(h, batch, frames);
-    if (!uniform) return 0;
-    return uniform + pm_align256((size_t)batch * frames * sizeof(VocosRow)) +
-           pm_align256(((size_t)batch + 1) * 4);
+    if (!h || batch < 1 || frames < 1) return 0;
+    return vocos_layout(h, batch, frames, true, nullptr).total;
 }
 
 // lengths null: the uniform batch; else the ragged one, rows packed
@@ -346,31 +378,18 @@ static int vocos_forward(pm_vocos_t h, const float* features,
         return pm_fail(PM_EINVAL, "batch and frames must be positive");
     if (global_features && global_batch != 1 && global_batch != batch)
         return pm_fail(PM_EINVAL, "global batch must be 1 or batch");
-    const size_t uniform = pm_vocos_workspace_bytes(h, batch, frames);
-    if (!workspace || workspace_bytes <
-            (ragged ? pm_vocos_ragged_workspace_bytes(h, batch, frames)
-                    : uniform))
+    const VocosLayout l = vocos_layout(h, batch, frames, ragged, workspace);
+    if (!workspace || workspace_bytes < l.total)
         return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t rows = (size_t)batch * frames;
     const int C = h->C, d = h->dtype;
-    char* ws = (char*)workspace;
-    float* x0 = (float*)ws;
-    float* x1 = (float*)(ws + pm_align256(rows * C * 4));
-    float* logits = (float*)(ws + 2 * pm_align256(rows * C * 4));
-    float* cond = (float*)((char*)logits +
-                           pm_align256(rows * PM_VOCOS_HEAD_OUT * 4));
-    float* frames_buf = x0;         // 2 x rows x 512 == rows x 1024 floats
-    VocosRagged rg = {nullptr, nullptr};
+    const VocosRagged rg = {l.map, l.off};
     if (ragged) {
-        VocosRow* map = (VocosRow*)(ws + uniform);
-        int* off = (int*)(ws + uniform + pm_align256(rows * sizeof(VocosRow)));
         hipLaunchKernelGGL(vocos_rowmap_kernel,
                            dim3((frames + 255) / 256, batch), dim3(256), 0, s,
-                           lengths, off, map, batch, frames);
+                           lengths, l.off, l.map, batch, frames);
         PM_HIP_TRY(hipGetLastError());
-        rg.map = map;
-        rg.off = off;
     }
     const int* total = ragged ? rg.off + batch : nullptr;
 
@@ -379,26 +398,26 @@ static int vocos_forward(pm_vocos_t h, const float* features,
         hipLaunchKernelGGL(vocos_cond_kernel, dim3((C + 255) / 256,
                                                    global_batch),
                            dim3(256), 0, s, global_features,
-                           h->at("cond.weight"), h->at("cond.bias"), cond,
+                           h->at("cond.weight"), h->at("cond.bias"), l.cond,
                            h->G, C);
         PM_HIP_TRY(hipGetLastError());
     }
     VocosGemmArgs g = {};
     g.x = features; g.w = h->conv_pre; g.bias = h->at("conv_pre.bias");
-    g.gbias = global_features ? cond : nullptr; g.gbatch = global_batch;
-    g.out = x1; g.B = batch; g.T = frames; g.K = h->F; g.N = C; g.ldo = C;
+    g.gbias = global_features ? l.cond : nullptr; g.gbatch = global_batch;
+    g.out = l.x1; g.B = batch; g.T = frames; g.K = h->F; g.N = C; g.ldo = C;
     g.rg = rg;
     PM_HIP_TRY(gemm(d, 7, true, g, s));
     // backbone embed + norm                                vocos.py:96-98
     g = {};
-    g.x = x1; g.w = h->embed; g.bias = h->at("backbone.embed.bias");
-    g.out = x0; g.B = batch; g.T = frames; g.K = C; g.N = C; g.ldo = C;
+    g.x = l.x1; g.w = h->embed; g.bias = h->at("backbone.embed.bias");
+    g.out = l.x0; g.B = batch; g.T = frames; g.K = C; g.N = C; g.ldo = C;
     g.rg = rg;
     PM_HIP_TRY(gemm(d, 7, false, g, s));
-    PM_HIP_TRY(layer_norm(x0, h->at("backbone.norm.weight"),
+    PM_HIP_TRY(layer_norm(l.x0, h->at("backbone.norm.weight"),
                           h->at("backbone.norm.bias"), (int)rows, total, s));
-    float* cur = x0;
-    float* nxt = x1;
+    float* cur = l.x0;
+    float* nxt = l.x1;
     for (int i = 0; i < h->layers; ++i) {
         VocosBlockArgs a = {};
         a.x = cur; a.y = nxt; a.dw_w = h->dw[i];
@@ -417,7 +436,7 @@ static int vocos_forward(pm_vocos_t h, const float* features,
                           total, s));
     // head: cur -> logits, then the frames overwrite the residual buffers
     PM_HIP_TRY(head(d, cur, h->head, h->at("head.out.bias"),
-                    h->at("head.istft.window"), logits, frames_buf, audio,
+                    h->at("head.istft.window"), l.logits, l.frames, audio,
                     batch, frames, rg, s));
     return PM_OK;
 }
@@ -449,7 +468,7 @@ extern "C" int pm_vocos_forward_ragged(pm_vocos_t h, const float* features,
 extern "C" size_t pm_convnext_block_workspace_bytes(int dtype, int channels,
                                                     int hidden) {
     if (!known_dtype(dtype) || channels < 1 || hidden < 1) return 0;
-    return block_weight_bytes(dtype, channels, hidden);
+    return block_weights(dtype, channels, hidden, nullptr).total;
 }
 
 extern "C" int pm_convnext_block_cl(
@@ -470,21 +489,19 @@ extern "C" int pm_convnext_block_cl(
                        "unsupported block %d x %d", channels, hidden);
     if (batch < 1 || frames < 1)
         return pm_fail(PM_EINVAL, "batch and frames must be positive");
-    if (!workspace ||
-        workspace_bytes < block_weight_bytes(dtype, channels, hidden))
+    const BlockWeights bw = block_weights(dtype, channels, hidden, workspace);
+    if (!workspace || workspace_bytes < bw.total)
         return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)workspace;
-    const size_t wsz = pm_align256((size_t)channels * hidden * esz(dtype));
-    PM_HIP_TRY(pack(dtype, w1, base, hidden, channels, 1, s));
-    PM_HIP_TRY(pack(dtype, w2, base + wsz, channels, hidden, 1, s));
-    float* dw = (float*)(base + 2 * wsz);
+    PM_HIP_TRY(pack(dtype, w1, bw.w1, hidden, channels, 1, s));
+    PM_HIP_TRY(pack(dtype, w2, bw.w2, channels, hidden, 1, s));
     hipLaunchKernelGGL(vocos_dw_pack_kernel, dim3((7 * channels + 255) / 256),
-                       dim3(256), 0, s, dw_w, dw, channels);
+                       dim3(256), 0, s, dw_w, bw.dw, channels);
     PM_HIP_TRY(hipGetLastError());
     VocosBlockArgs a = {};
-    a.x = x; a.y = y; a.dw_w = dw; a.dw_b = dw_b; a.ln_w = ln_w; a.ln_b = ln_b;
-    a.w1 = base; a.b1 = b1; a.w2 = base + wsz; a.b2 = b2; a.gamma = gamma;
+    a.x = x; a.y = y; a.dw_w = bw.dw; a.dw_b = dw_b; a.ln_w = ln_w;
+    a.ln_b = ln_b;
+    a.w1 = bw.w1; a.b1 = b1; a.w2 = bw.w2; a.b2 = b2; a.gamma = gamma;
     a.B = batch; a.T = frames; a.H = hidden;
     PM_HIP_TRY(block(dtype, a, s));
     return PM_OK;
@@ -541,10 +558,7 @@ extern "C" int pm_vocos_gemm_cl(int dtype, int taps, int channels_first,
 extern "C" size_t pm_vocos_head_workspace_bytes(int dtype, int batch,
                                                 int frames) {
     if (!known_dtype(dtype) || batch < 1 || frames < 1) return 0;
-    const size_t rows = (size_t)batch * frames;
-    return packed_bytes(dtype, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1) +
-           pm_align256(rows * PM_VOCOS_HEAD_OUT * 4) +
-           pm_align256(rows * PM_VOCOS_NFFT * 4);
+    return head_layout(dtype, batch, frames, nullptr).total;
 }
 
 extern "C" int pm_vocos_head(int dtype, const float* x, const float* w,
@@ -558,18 +572,13 @@ extern "C" int pm_vocos_head(int dtype, const float* x, const float* w,
         return pm_fail(PM_EINVAL, "dtype must be PM_F32, PM_F16 or PM_BF16");
     if (batch < 1 || frames < 1)
         return pm_fail(PM_EINVAL, "batch and frames must be positive");
-    if (!workspace ||
-        workspace_bytes < pm_vocos_head_workspace_bytes(dtype, batch, frames))
+    const HeadLayout l = head_layout(dtype, batch, frames, workspace);
+    if (!workspace || workspace_bytes < l.total)
         return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const size_t rows = (size_t)batch * frames;
-    char* base = (char*)workspace;
-    char* logits = base + packed_bytes(dtype, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1);
-    char* frames_buf = logits + pm_align256(rows * PM_VOCOS_HEAD_OUT * 4);
-    PM_HIP_TRY(pack(dtype, w, base, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1, s));
-    PM_HIP_TRY(head(dtype, x, base, bias, window, (float*)logits,
-                    (float*)frames_buf, audio, batch, frames,
-                    VocosRagged{nullptr, nullptr}, s));
+    PM_HIP_TRY(pack(dtype, w, l.w, PM_VOCOS_HEAD_OUT, PM_VOCOS_C, 1, s));
+    PM_HIP_TRY(head(dtype, x, l.w, bias, window, l.logits, l.frames, audio,
+                    batch, frames, VocosRagged{nullptr, nullptr}, s));
     return PM_OK;
 }
 
