@@ -263,7 +263,9 @@ int pm_input_conv_cl(int dtype, const float* x_cl, float* out_cl,
                      size_t workspace_bytes, void* stream);
 /* lrelu(optional) -> ConvTranspose1d(c_in, c_out, k = 2 r, stride r,
  * padding r / 2) (hifigan.py:97-106), channels-last: (B, L, c_in_pad) ->
- * (B, L * r, c_out_pad)                                                   */
+ * (B, L * r, c_out_pad). Launched as the engine launches the layer: with
+ * 16-bit operands, an upsampler of r * c_out_pad = 128 rows (c_in 128 -> 64,
+ * r = 2) takes its 256-column variant once batch * ceil(length / 256) >= 1024 */
 int pm_conv_transpose_cl(int dtype, const float* x_cl, float* out_cl,
                          const float* w, const float* bias, int batch,
                          int length, int c_in, int c_out, int rate, int lrelu,
@@ -278,7 +280,9 @@ int pm_conv_transpose_x16_cl(int dtype, const void* x16_cl, float* out_cl,
                              void* workspace, size_t workspace_bytes,
                              void* stream);
 /* LeakyReLU -> Conv1d(C, 1, 7, pad 3, no bias) -> tanh (hifigan.py:55-60):
- * (B, L, c_pad) channels-last -> (B, L)                                   */
+ * (B, L, c_pad) channels-last -> (B, L). Launched as the engine launches
+ * the layer: exactly 32 channels run the 32-channel kernel, any other count
+ * (<= 64) the generic one                                                   */
 int pm_out_conv_tanh(const float* x_cl, const float* w, float* out,
                      int batch, int length, int channels, void* stream);
 /* Debug instrumentation: per-workgroup phase timestamps (s_memtime) of the

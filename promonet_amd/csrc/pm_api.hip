@@ -176,6 +176,21 @@ struct ConvGeom {
     size_t packed_elems() const {
         return weight_elems() + (bias_step ? (size_t)(M / 32) * 512 : 0);
     }
+    // copies of the padded bias (one per phase of a conv-transpose)
+    int bias_rep() const { return mode == 1 ? r : 1; }
+};
+
+// One packed conv: the engine owns w / bias, an op entry points them into the
+// caller's workspace
+struct Layer {
+    ConvGeom geom;
+    void* w = nullptr;        // packed (+ bias steps for MRF convs)
+    float* bias = nullptr;    // padded (tiled per phase for conv-transpose)
+    float* tmp_g = nullptr;   // weight-norm pair awaiting its partner
+    float* tmp_v = nullptr;
+    bool has_w = false, has_b = false;
+    int cfg = 0;
+    int dtype = PM_F16;       // MFMA operand type this layer is packed for
 };
 
 static hipError_t pack_weights(
@@ -231,14 +246,17 @@ static hipError_t pad_bias(
     return hipGetLastError();
 }
 
-// Wide upsampler (conv_upsample_kernel): 16-bit operands, C_in 256 / 512,
-// 256-row M blocks whose tap window is uniform. Sets the single-chunk packing.
-static bool upsample_whole_k(int dtype, ConvGeom& g) {
-    if (esz(dtype) == 4 || g.mode != 1) return false;
-    if (g.cin_pad != 256 && g.cin_pad != 512) return false;
-    if (g.M % 256 || ((g.r / 2) * g.cout_pad) % 64) return false;
-    g.ch = g.cin_pad;
-    return true;
+// Pack torch-layout weights and bias into l.w / l.bias (set_weight / set_bias
+// receive their halves in either order and call the pieces)
+static hipError_t pack_layer(
+    const Layer& l, const float* w, const float* bias, hipStream_t s) {
+    const ConvGeom& g = l.geom;
+    hipError_t e = pack_weights(l.dtype, g, w, l.w, s);
+    if (e == hipSuccess)
+        e = pad_bias(bias, l.bias, g.cout, g.cout_pad, g.bias_rep(), s);
+    if (e == hipSuccess && g.bias_step)
+        e = pack_bias_step(l.dtype, g, l.bias, l.w, s);
+    return e;
 }
 
 static int single_cfg(int M, int ch, int wave64_ok) {
@@ -249,21 +267,126 @@ static int single_cfg(int M, int ch, int wave64_ok) {
 }
 
 // ---------------------------------------------------------------------------
+// The HiFi-GAN layers: the geometry (and kernel configuration) of each kind
+// and its launch, stated once for the engine and the per-kernel entry points
+// ---------------------------------------------------------------------------
+// Input conv: Conv1d(c_in -> c_out, k 7, pad 3)
+static Layer input_layer(int dtype, int c_in, int c_out) {
+    Layer l; l.dtype = dtype;
+    ConvGeom& g = l.geom;
+    g.mode = 0; g.cout = c_out; g.cin = c_in; g.k = g.kt = 7;
+    g.cout_pad = g.M = pm_pad32(c_out); g.cin_pad = pm_pad32(c_in);
+    g.ch = (g.cin_pad % 64 == 0) ? 64 : 32;
+    l.cfg = single_cfg(g.M, g.ch, 1);
+    return l;
+}
+
+// Upsampler: ConvTranspose1d(c_in -> c_out, k 2 r, stride r) as a polyphase
+// GEMM of r phases, two taps each. cfg 4, the wide upsampler
+// (conv_upsample_kernel): 16-bit operands, C_in 256 / 512, 256-row M blocks
+// whose tap window is uniform; its packing is one chunk of the whole K.
+static Layer upsample_layer(int dtype, int c_in, int c_out, int r) {
+    Layer l; l.dtype = dtype;
+    ConvGeom& g = l.geom;
+    g.mode = 1; g.cout = c_out; g.cin = c_in; g.k = 2 * r;
+    g.cout_pad = pm_pad32(c_out); g.cin_pad = pm_pad32(c_in);
+    g.M = r * g.cout_pad; g.kt = 2; g.r = r; g.p = r / 2;
+    g.ch = (g.cin_pad % 64 == 0) ? 64 : 32;
+    const bool uniform = ((r / 2) * g.cout_pad) % 64 == 0;
+    l.cfg = single_cfg(g.M, g.ch, uniform);
+    if (esz(dtype) == 2 && (g.cin_pad == 256 || g.cin_pad == 512) &&
+        g.M % 256 == 0 && uniform) {
+        l.cfg = 4; g.ch = g.cin_pad;
+    }
+    return l;
+}
+
+// One conv of an MRF Block: Conv1d(C -> C, k K), its bias as a packed step
+static Layer mrf_layer(int dtype, int C, int K) {
+    Layer l; l.dtype = dtype;
+    ConvGeom& g = l.geom;
+    g.mode = 0; g.cout = g.cin = C; g.k = g.kt = K;
+    g.cout_pad = g.cin_pad = g.M = pm_pad32(C);
+    g.ch = std::min(g.M, 64);   // (pm_launch.h: one packing)
+    g.bias_step = true;
+    return l;
+}
+
+// Can this upsampler stage a 16-bit copy of its input as it is
+// (SingleArgs::x16)? Only conv_single_kernel does, on 16-bit operands.
+static bool takes_x16(const Layer& up) {
+    return esz(up.dtype) == 2 && up.cfg != 4;
+}
+
+// Speaker conditioning (gbatch, G) as a per-utterance bias (gbatch, pad32(c))
+static hipError_t launch_speaker_bias(
+    const float* global, const float* w, const float* b, float* gbias,
+    int gbatch, int G, int c, hipStream_t s) {
+    const int cp = pm_pad32(c);
+    hipLaunchKernelGGL(pm_speaker_bias_kernel, dim3((cp + 3) / 4, gbatch),
+                       dim3(256), 0, s, global, w, b, gbias, G, c, cp);
+    return hipGetLastError();
+}
+
+static hipError_t launch_input_conv(
+    const Layer& l, const float* x, float* out, const float* gbias, int gbatch,
+    int B, int L, const int* lengths, hipStream_t s) {
+    const ConvGeom& g = l.geom;
+    SingleArgs a = {};
+    a.x = x; a.out = out; a.w = l.w; a.bias = l.bias;
+    a.gbias = gbias; a.gbias_batch = gbatch;
+    a.B = B; a.L = L; a.Lout = L; a.Cin = g.cin_pad; a.M = g.M;
+    a.lrelu = 0; a.pad = 3; a.phase_r = 0; a.phase_c = 1;
+    a.lengths = lengths; a.len_scale = 1;
+    return launch_single(l.dtype, 0, g.ch, l.cfg, a, s);
+}
+
+// x (fp32) or, where takes_x16, x16 (the operand values of lrelu(x)); `rate`
+// input rows per frame of `lengths`
+static hipError_t launch_upsample(
+    const Layer& l, const float* x, const void* x16, float* out, int lrelu,
+    int B, int L, const int* lengths, int rate, hipStream_t s) {
+    const ConvGeom& g = l.geom;
+    SingleArgs a = {};
+    a.x = x; a.x16 = x16; a.out = out; a.w = l.w; a.bias = l.bias;
+    a.gbias = nullptr; a.gbias_batch = 1;
+    a.B = B; a.L = L; a.Lout = L; a.Cin = g.cin_pad; a.M = g.M;
+    a.lrelu = lrelu; a.pad = 1;
+    a.phase_c = g.cout_pad; a.phase_p = g.p; a.phase_r = g.r;
+    a.lengths = lengths; a.len_scale = rate;
+    // (long batches: the 256-column variant of cfg 3)
+    int cfg = l.cfg;
+    if (cfg == 3 && esz(l.dtype) == 2 && g.ch == 64 &&
+        (long long)B * ((L + 255) / 256) >= 4 * 256)
+        cfg = 5;
+    return launch_single(l.dtype, 1, g.ch, cfg, a, s);
+}
+
+// Output layer on x (B, L, pad32(C)), w (1, C, 7): the 32-channel kernel for
+// exactly 32 channels, the generic one otherwise
+static hipError_t launch_out_conv(
+    const float* x, const float* w, float* out, int B, int L, int C,
+    const int* lengths, int rate, hipStream_t s) {
+    constexpr int T32 = 128, TH = 256;   // (T32: 38 KB of LDS, four per CU)
+    const int Cp = pm_pad32(C);
+    if (C == 32)
+        hipLaunchKernelGGL(pm_out_conv32_kernel<T32>,
+                           dim3((L + T32 * 2 - 1) / (T32 * 2), B), dim3(T32),
+                           (size_t)32 * PM_OUT32_RL(T32) * sizeof(float), s, x,
+                           w, out, L, lengths, rate);
+    else
+        hipLaunchKernelGGL(pm_out_conv_kernel<TH>, dim3((L + TH - 1) / TH, B),
+                           dim3(TH),
+                           ((size_t)(TH + 6) * (Cp + 1) + 7 * Cp) * sizeof(float),
+                           s, x, w, out, L, Cp, C, lengths, rate);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // engine
 // ---------------------------------------------------------------------------
-struct Layer {
-    ConvGeom geom;
-    void* w = nullptr;        // packed (+ bias steps for MRF convs)
-    float* bias = nullptr;    // padded (tiled per phase for conv-transpose)
-    float* tmp_g = nullptr;   // weight-norm pair awaiting its partner
-    float* tmp_v = nullptr;
-    bool has_w = false, has_b = false;
-    int cfg = 0;
-    int dtype = PM_F16;       // MFMA operand type this layer is packed for
-};
-
 struct Stage {
-    int cin = 0, cout = 0, cin_pad = 0, cout_pad = 0, r = 0, k = 0;
+    int cin = 0, cout = 0, cout_pad = 0, r = 0, k = 0;
     int dtype = PM_F16;       // operand type of the stage (upsampler + MRF)
     Layer up;
     Layer c1[PM_MAX_RESBLOCKS][PM_MAX_DILATIONS];
@@ -278,7 +401,7 @@ struct pm_hifigan_s {
     float* spk_w = nullptr; float* spk_b = nullptr;
     bool has_spk_w = false, has_spk_b = false;
     float* out_w = nullptr; bool has_out_w = false;
-    int c_last = 0, c_last_pad = 0;
+    int c_last = 0;
     std::vector<Stage> stages;
     bool finalized = false;
     // ---- optional per-launch timing with HIP events (bench.py roofline) ----
@@ -361,10 +484,10 @@ extern "C" int pm_hifigan_create(
     auto* h = new pm_hifigan_s();
     h->cfg = *c;
     h->dtype = c->compute_dtype;
-    h->in_conv.dtype = block_dtype(h->dtype);
     h->cfp = pm_pad32(c->num_features);
     h->c0 = c->initial_channels;
     h->c0p = pm_pad32(h->c0);
+    h->in_conv = input_layer(block_dtype(h->dtype), c->num_features, h->c0);
     h->hop = 1;
     h->stages.resize(c->num_stages);
     for (int i = 0; i < c->num_stages; ++i) {
@@ -374,7 +497,6 @@ extern "C" int pm_hifigan_create(
         const int code = c->stage_compute_dtype[i]
             ? c->stage_compute_dtype[i] - 1 : h->dtype;
         s.dtype = block_dtype(code);
-        s.up.dtype = up_dtype(code);
         if (s.r < 2 || (s.r & 1) || s.k != 2 * s.r) {
             delete h;
             return pm_fail(PM_EINVAL,
@@ -384,7 +506,6 @@ extern "C" int pm_hifigan_create(
         }
         s.cin = h->c0 >> i;
         s.cout = h->c0 >> (i + 1);
-        s.cin_pad = pm_pad32(s.cin);
         s.cout_pad = pm_pad32(s.cout);
         if (s.cout_pad != 32 && s.cout_pad != 64 && s.cout_pad != 128 &&
             s.cout_pad != 256) {
@@ -394,38 +515,14 @@ extern "C" int pm_hifigan_create(
                            "count must be 32, 64, 128 or 256)", i, s.cout);
         }
         h->hop *= s.r;
-        // conv-transpose as a polyphase GEMM
-        ConvGeom& g = s.up.geom;
-        g.mode = 1; g.cout = s.cout; g.cin = s.cin; g.k = s.k;
-        g.cout_pad = s.cout_pad; g.cin_pad = s.cin_pad;
-        g.M = s.r * s.cout_pad; g.kt = 2; g.r = s.r; g.p = s.r / 2;
-        g.ch = (s.cin_pad % 64 == 0) ? 64 : 32;
-        s.up.cfg = upsample_whole_k(s.up.dtype, g)
-            ? 4
-            : single_cfg(g.M, g.ch, ((s.r / 2) * s.cout_pad) % 64 == 0);
+        s.up = upsample_layer(up_dtype(code), s.cin, s.cout, s.r);
         for (int j = 0; j < c->num_resblocks; ++j)
             for (int n = 0; n < c->num_dilations; ++n)
-                for (int which = 0; which < 2; ++which) {
-                    (which ? s.c2 : s.c1)[j][n].dtype = s.dtype;
-                    ConvGeom& q = (which ? s.c2 : s.c1)[j][n].geom;
-                    q.mode = 0; q.cout = q.cin = s.cout;
-                    q.k = c->resblock_kernel_sizes[j];
-                    q.cout_pad = q.cin_pad = q.M = s.cout_pad;
-                    q.kt = q.k;
-                    q.ch = std::min(s.cout_pad, 64);   // (pm_launch.h: one packing)
-                    q.bias_step = true;
-                }
-    }
-    {
-        ConvGeom& g = h->in_conv.geom;
-        g.mode = 0; g.cout = h->c0; g.cin = c->num_features; g.k = 7;
-        g.cout_pad = g.M = h->c0p; g.cin_pad = h->cfp; g.kt = 7;
-        g.ch = (h->cfp % 64 == 0) ? 64 : 32;
-        h->in_conv.cfg = single_cfg(g.M, g.ch, 1);
+                s.c1[j][n] = s.c2[j][n] =
+                    mrf_layer(s.dtype, s.cout, c->resblock_kernel_sizes[j]);
     }
     h->c_last = h->stages.back().cout;
-    h->c_last_pad = h->stages.back().cout_pad;
-    if (h->c_last_pad > 64) {
+    if (pm_pad32(h->c_last) > 64) {
         delete h;
         return pm_fail(PM_EINVAL, "output conv supports <= 64 input channels");
     }
@@ -490,7 +587,7 @@ static int set_bias(
     const ConvGeom& g = l.geom;
     if (ndim != 1 || shape[0] != g.cout)
         return pm_fail(PM_EINVAL, "%s: expected shape (%d)", name, g.cout);
-    const int rep = g.mode == 1 ? g.r : 1;
+    const int rep = g.bias_rep();
     if (!l.bias)
         PM_HIP_TRY(hipMalloc((void**)&l.bias,
                              (size_t)g.cout_pad * rep * sizeof(float)));
@@ -721,24 +818,13 @@ static int forward_impl(
         feat_cl = p.feat;
     }
     // speaker conditioning as a per-utterance bias of the input conv
-    hipLaunchKernelGGL(pm_speaker_bias_kernel, dim3((h->c0p + 3) / 4, gbatch),
-                       dim3(256), 0, s, g, h->spk_w, h->spk_b, p.gbias,
-                       h->cfg.global_channels, h->c0, h->c0p);
-    PM_HIP_TRY(hipGetLastError());
-    {
-        SingleArgs a = {};
-        a.x = feat_cl; a.out = buf[0]; a.w = h->in_conv.w;
-        a.bias = h->in_conv.bias; a.gbias = p.gbias; a.gbias_batch = gbatch;
-        a.B = B; a.L = T; a.Lout = T; a.Cin = h->cfp; a.M = h->c0p;
-        a.lrelu = 0; a.pad = 3; a.phase_r = 0; a.phase_c = 1;
-        a.lengths = lengths; a.len_scale = 1;
-        PROF(h, s, "input_conv",
-             2.0 * h->c0 * h->cfg.num_features * 7 * B * T,
-             (double)B * T * (h->cfg.num_features + h->c0) * 4, {
-            PM_HIP_TRY(launch_single(h->in_conv.dtype, 0, h->in_conv.geom.ch,
-                                  h->in_conv.cfg, a, s));
-        });
-    }
+    PM_HIP_TRY(launch_speaker_bias(g, h->spk_w, h->spk_b, p.gbias, gbatch,
+                                   h->cfg.global_channels, h->c0, s));
+    PROF(h, s, "input_conv", 2.0 * h->c0 * h->cfg.num_features * 7 * B * T,
+         (double)B * T * (h->cfg.num_features + h->c0) * 4, {
+        PM_HIP_TRY(launch_input_conv(h->in_conv, feat_cl, buf[0], p.gbias,
+                                     gbatch, B, T, lengths, s));
+    });
     int xi = 0;        // index of the buffer holding the stage input
     // the stage input once more, as the 16-bit operand values of the next
     // upsampler (written by the previous stage's last Block launch when that
@@ -750,27 +836,14 @@ static int forward_impl(
     for (auto& st : h->stages) {
         const int ui = (xi + 1) & 3, ai = (xi + 2) & 3, bi = (xi + 3) & 3;
         {
-            SingleArgs a = {};
-            a.x = buf[xi]; a.out = buf[ui]; a.w = st.up.w; a.bias = st.up.bias;
-            a.gbias = nullptr; a.gbias_batch = 1;
-            a.B = B; a.L = L; a.Lout = L; a.Cin = st.cin_pad;
-            a.M = st.up.geom.M; a.lrelu = 1; a.pad = 1;
-            a.phase_c = st.cout_pad; a.phase_p = st.r / 2; a.phase_r = st.r;
-            a.lengths = lengths; a.len_scale = rate;
-            a.x16 = x16;
-            x16 = nullptr;
             char label[64];
             snprintf(label, sizeof(label), "convT_c%d_r%d", st.cin, st.r);
             PROF(h, s, label, 2.0 * st.cin * st.cout * st.k * B * L,
                  (double)B * L * (st.cin + (double)st.r * st.cout) * 4, {
-                // (long batches: the 256-column variant of cfg 3)
-                int cfg = st.up.cfg;
-                if (cfg == 3 && esz(st.up.dtype) == 2 && st.up.geom.ch == 64 &&
-                    (long long)B * ((L + 255) / 256) >= 4 * 256)
-                    cfg = 5;
-                PM_HIP_TRY(launch_single(st.up.dtype, 1, st.up.geom.ch, cfg, a,
-                                         s));
+                PM_HIP_TRY(launch_upsample(st.up, buf[xi], x16, buf[ui], 1, B,
+                                           L, lengths, rate, s));
             });
+            x16 = nullptr;
         }
         L *= st.r;
         rate *= st.r;
@@ -797,7 +870,7 @@ static int forward_impl(
         // 16-bit stage.
         const size_t next = &st - &h->stages[0] + 1;
         if (nb > 1 && next < h->stages.size() &&
-            esz(h->stages[next].up.dtype) == 2 && h->stages[next].up.cfg != 4) {
+            takes_x16(h->stages[next].up)) {
             d.act16 = buf[ai];      // (free: no pair iterations)
             d.act16_type = h->stages[next].up.dtype;
         }
@@ -849,29 +922,11 @@ static int forward_impl(
         }
         xi = si;
     }
-    {
-        constexpr int TH = 256;
-        const int C = h->c_last_pad;
-        PROF(h, s, "out_conv_tanh", 2.0 * h->c_last * 7 * B * L,
-             (double)B * L * (h->c_last + 1) * 4, {
-            if (C == 32 && h->c_last == 32) {
-                constexpr int T32 = 128;   // 38 KB of LDS: four per CU
-                const size_t smem = (size_t)32 * PM_OUT32_RL(T32) * sizeof(float);
-                hipLaunchKernelGGL(pm_out_conv32_kernel<T32>,
-                                   dim3((L + T32 * 2 - 1) / (T32 * 2), B),
-                                   dim3(T32), smem, s, buf[xi], h->out_w, out,
-                                   L, lengths, rate);
-            } else {
-                const size_t smem =
-                    ((size_t)(TH + 6) * (C + 1) + 7 * C) * sizeof(float);
-                hipLaunchKernelGGL(pm_out_conv_kernel<TH>,
-                                   dim3((L + TH - 1) / TH, B), dim3(TH), smem,
-                                   s, buf[xi], h->out_w, out, L, C, h->c_last,
-                                   lengths, rate);
-            }
-            PM_HIP_TRY(hipGetLastError());
-        });
-    }
+    PROF(h, s, "out_conv_tanh", 2.0 * h->c_last * 7 * B * L,
+         (double)B * L * (h->c_last + 1) * 4, {
+        PM_HIP_TRY(launch_out_conv(buf[xi], h->out_w, out, B, L, h->c_last,
+                                   lengths, rate, s));
+    });
     return PM_OK;
 }
 
@@ -1069,17 +1124,12 @@ static int pack_iteration(
     int dtype, int C, int K, const float* w1, const float* b1, const float* w2,
     const float* b2, char* base, hipStream_t s, const void** p1,
     const void** p2) {
-    const int Cp = pm_pad32(C);
-    ConvGeom g;
-    g.mode = 0; g.cout = g.cin = C; g.k = K; g.cout_pad = g.cin_pad = g.M = Cp;
-    g.kt = K; g.ch = std::min(Cp, 64); g.bias_step = true;
     const IterationLayout l = iteration_layout(C, C, K, base);
-    PM_HIP_TRY(pack_weights(dtype, g, w1, l.w1, s));
-    PM_HIP_TRY(pack_weights(dtype, g, w2, l.w2, s));
-    PM_HIP_TRY(pad_bias(b1, l.b1, C, Cp, 1, s));
-    PM_HIP_TRY(pad_bias(b2, l.b2, C, Cp, 1, s));
-    PM_HIP_TRY(pack_bias_step(dtype, g, l.b1, l.w1, s));
-    PM_HIP_TRY(pack_bias_step(dtype, g, l.b2, l.w2, s));
+    Layer conv = mrf_layer(dtype, C, K);
+    conv.w = l.w1; conv.bias = l.b1;
+    PM_HIP_TRY(pack_layer(conv, w1, b1, s));
+    conv.w = l.w2; conv.bias = l.b2;
+    PM_HIP_TRY(pack_layer(conv, w2, b2, s));
     *p1 = l.w1; *p2 = l.w2;
     return PM_OK;
 }
@@ -1275,29 +1325,20 @@ extern "C" int pm_input_conv_cl(
         return pm_fail(PM_EINVAL, "null argument");
     if (gbatch != 1 && gbatch != B)
         return pm_fail(PM_EINVAL, "global batch must be 1 or batch");
-    const int cip = pm_pad32(c_in), cop = pm_pad32(c_out);
+    const int cop = pm_pad32(c_out);
     if (cop % 64 && cop != 32)
         return pm_fail(PM_EINVAL, "output channels %d unsupported", c_out);
     const InputConvLayout l = input_conv_layout(c_in, c_out, B, ws);
     if (ws_bytes < l.total)
         return pm_fail(PM_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    ConvGeom g;
-    g.mode = 0; g.cout = c_out; g.cin = c_in; g.k = 7;
-    g.cout_pad = g.M = cop; g.cin_pad = cip; g.kt = 7;
-    g.ch = (cip % 64 == 0) ? 64 : 32;
-    const int cfg = single_cfg(g.M, g.ch, 1);
-    PM_HIP_TRY(pack_weights(dtype, g, w, l.w, s));
-    PM_HIP_TRY(pad_bias(bias, l.bias, c_out, cop, 1, s));
-    hipLaunchKernelGGL(pm_speaker_bias_kernel, dim3((cop + 3) / 4, gbatch),
-                       dim3(256), 0, s, global, ws_w, ws_b, l.gbias, G, c_out,
-                       cop);
-    PM_HIP_TRY(hipGetLastError());
-    SingleArgs a = {};
-    a.x = x; a.out = out; a.w = l.w; a.bias = l.bias; a.gbias = l.gbias;
-    a.gbias_batch = gbatch; a.B = B; a.L = L; a.Lout = L; a.Cin = cip;
-    a.M = cop; a.lrelu = 0; a.pad = 3; a.phase_r = 0; a.phase_c = 1;
-    PM_HIP_TRY(launch_single(dtype, 0, g.ch, cfg, a, s));
+    Layer conv = input_layer(dtype, c_in, c_out);
+    conv.w = l.w; conv.bias = l.bias;
+    PM_HIP_TRY(pack_layer(conv, w, bias, s));
+    PM_HIP_TRY(launch_speaker_bias(global, ws_w, ws_b, l.gbias, gbatch, G,
+                                   c_out, s));
+    PM_HIP_TRY(launch_input_conv(conv, x, out, l.gbias, gbatch, B, L, nullptr,
+                                 s));
     return PM_OK;
 }
 
@@ -1326,28 +1367,13 @@ static int conv_transpose_cl_impl(
     if (l.total > pm_op_workspace_bytes(c_in, c_out, 2 * r))
         return pm_fail(PM_ESTATE, "the layout outgrew its public bound");
     hipStream_t s = (hipStream_t)stream;
-    ConvGeom g;
-    g.mode = 1; g.cout = c_out; g.cin = c_in; g.k = 2 * r;
-    g.cout_pad = pm_pad32(c_out); g.cin_pad = pm_pad32(c_in);
-    g.M = r * g.cout_pad; g.kt = 2; g.r = r; g.p = r / 2;
-    g.ch = (g.cin_pad % 64 == 0) ? 64 : 32;
-    const int cfg = upsample_whole_k(dtype, g)
-        ? 4
-        : single_cfg(g.M, g.ch, ((r / 2) * g.cout_pad) % 64 == 0);
-    PM_HIP_TRY(pack_weights(dtype, g, w, l.w, s));
-    PM_HIP_TRY(pad_bias(bias, l.bias, c_out, g.cout_pad, r, s));
-    SingleArgs a = {};
-    a.x = x; a.out = out; a.w = l.w; a.bias = l.bias; a.gbias = nullptr;
-    a.gbias_batch = 1; a.B = B; a.L = L; a.Lout = L; a.Cin = g.cin_pad;
-    a.M = g.M; a.lrelu = lrelu; a.pad = 1;
-    a.phase_c = g.cout_pad; a.phase_p = r / 2; a.phase_r = r;
-    if (x16) {
-        if (esz(dtype) != 2 || cfg == 4)
-            return pm_fail(PM_EINVAL, "a 16-bit operand input needs a 16-bit "
-                           "operand type and the narrow upsampler kernel");
-        a.x16 = x16;
-    }
-    PM_HIP_TRY(launch_single(dtype, 1, g.ch, cfg, a, s));
+    Layer up = upsample_layer(dtype, c_in, c_out, r);
+    if (x16 && !takes_x16(up))
+        return pm_fail(PM_EINVAL, "a 16-bit operand input needs a 16-bit "
+                       "operand type and the narrow upsampler kernel");
+    up.w = l.w; up.bias = l.bias;
+    PM_HIP_TRY(pack_layer(up, w, bias, s));
+    PM_HIP_TRY(launch_upsample(up, x, x16, out, lrelu, B, L, nullptr, 1, s));
     return PM_OK;
 }
 
@@ -1376,14 +1402,10 @@ extern "C" int pm_out_conv_tanh(
     const float* x, const float* w, float* out, int B, int L, int C,
     void* stream) {
     if (!x || !w || !out) return pm_fail(PM_EINVAL, "null argument");
-    const int Cp = pm_pad32(C);
-    if (Cp > 64) return pm_fail(PM_EINVAL, "channels %d unsupported", C);
-    constexpr int TH = 256;
-    const size_t smem = ((size_t)(TH + 6) * (Cp + 1) + 7 * Cp) * sizeof(float);
-    hipLaunchKernelGGL(pm_out_conv_kernel<TH>, dim3((L + TH - 1) / TH, B),
-                       dim3(TH), smem, (hipStream_t)stream, x, w, out, L, Cp, C,
-                       (const int*)nullptr, 1);
-    PM_HIP_TRY(hipGetLastError());
+    if (pm_pad32(C) > 64)
+        return pm_fail(PM_EINVAL, "channels %d unsupported", C);
+    PM_HIP_TRY(launch_out_conv(x, w, out, B, L, C, nullptr, 1,
+                               (hipStream_t)stream));
     return PM_OK;
 }
 

@@ -477,16 +477,28 @@ def mrf_case(mode, c, niter, run):
 UPSAMPLE_SHAPES = ((512, 256, 8), (256, 128, 8), (128, 64, 2), (64, 32, 2),
                    (64, 32, 8), (32, 16, 2), (16, 8, 4))
 UPSAMPLE_LENGTHS = (1, 5, 130, 300)
+# The c_in 128 r = 2 upsampler with 16-bit operands takes 256 input columns a
+# workgroup, not 128, from batch * ceil(length / 256) >= 1024 on (batch is the
+# cheap axis): one mostly empty tile per utterance; a full and a ragged tile,
+# exactly at the threshold; one utterance fewer, the 128-column side of the
+# rule on the same data (the first 511 utterances of the 512).
+# (batch, length, batch drawn)
+UPSAMPLE_LONG = ((1024, 5, 1024), (512, 300, 512), (511, 300, 512))
 
 
 @functools.lru_cache(maxsize=None)
-def upsample_case(mode, c_in, c_out, rate, length):
+def upsample_case(mode, c_in, c_out, rate, length, batch=BATCH):
     gen = torch.Generator().manual_seed(c_in + 10 * rate + length)
-    x = 10 * _choice(range(-9, 10), (BATCH, c_in, length), gen)
+    x = 10 * _choice(range(-9, 10), (batch, c_in, length), gen)
     w = _choice(range(-3, 4), (c_in, c_out, 2 * rate), gen)
     bias = _choice(range(-999, 1000), (c_out,), gen)
     y, bits = conv_transpose(x, w, bias, mode, rate)
     return dict(x=x, w=w, bias=bias, want=y, bits=bits)
+
+
+@functools.lru_cache(maxsize=1)     # (hundreds of MB: one at a time)
+def upsample_long_case(mode, length, drawn):
+    return upsample_case.__wrapped__(mode, 128, 64, 2, length, drawn)
 
 
 # (f) the f16 operand edge: activations at 65504, on both sides of the last

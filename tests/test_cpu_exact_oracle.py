@@ -119,6 +119,11 @@ def test_other_cases_exact(mode):
             case = E.upsample_case(mode, *shape, length)
             assert case['bits'] <= E.EXACT_BITS
             f16_range(mode, case['x'], case['w'])
+    if mode in ('f16', 'bf16'):
+        for _, length, drawn in E.UPSAMPLE_LONG:
+            case = E.upsample_long_case(mode, length, drawn)
+            assert case['bits'] <= E.EXACT_BITS
+            f16_range(mode, case['x'], case['w'])
     if mode in E.INPUT_MODES:
         for shape in E.INPUT_SHAPES:
             for run in range(len(E.INPUT_RUNS)):

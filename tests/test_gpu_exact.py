@@ -25,6 +25,9 @@ Kernel forms reached (the form is part of a Block test's id):
                                  for them all the same
   test_conv_transpose            conv_single_kernel, conv_upsample_kernel with
                                  1, 2 and all M groups; the 16-bit input path
+  test_conv_transpose_long_batch conv_single_kernel, 256 input columns a
+                                 workgroup (long batches), 128 one utterance
+                                 below the threshold
   test_input_conv                conv_single_kernel with the speaker bias
 """
 import ctypes
@@ -315,6 +318,30 @@ def test_conv_transpose(device, mode, c_in, c_out, rate):
                 assert_equal(from_cl(out, c_out), staged, (length, 'x16'))
     finally:
         restore_hooks()
+
+
+@pytest.mark.parametrize(
+    'mode,batch,length,drawn',
+    [(mode, *run) for mode in HALF for run in E.UPSAMPLE_LONG])
+def test_conv_transpose_long_batch(device, mode, batch, length, drawn):
+    """The 256-column variant of the C_in 128 r = 2 upsampler, and at batch
+    511 the 128-column one on the same data (E.UPSAMPLE_LONG)"""
+    _lib = lib()
+    c_in, c_out, rate = 128, 64, 2
+    case = E.upsample_long_case(mode, length, drawn)
+    assert_exact(case)
+    x_cl = to_cl(case['x'][:batch]).to(device)
+    wd, bd = case['w'].to(device), case['bias'].to(device)
+    size = _lib.lib().pm_op_workspace_bytes(c_in, c_out, 2 * rate)
+    ws = torch.empty(size, dtype=torch.uint8, device=device)
+    out = torch.full((batch, length * rate, c_out), float('nan'),
+                     device=device)
+    _lib.check(_lib.lib().pm_conv_transpose_cl(
+        _lib.DTYPES[mode], _lib.ptr(x_cl), _lib.ptr(out), _lib.ptr(wd),
+        _lib.ptr(bd), batch, length, c_in, c_out, rate, 1, ws.data_ptr(),
+        ws.numel(), _lib.stream()))
+    torch.cuda.synchronize()
+    assert_equal(from_cl(out, c_out), case['want'][:batch], (batch, length))
 
 
 # ---------------------------------------------------------------------------

@@ -414,6 +414,46 @@ def test_out_conv_tanh(device):
         check(max_abs(out[:, None], want), 6e-6, 'out_conv_tanh:fp32', (c, length))
 
 
+def out_conv_exact_case(length):
+    """24 live channels whose sums are exact in fp32 in any order: activations
+    k / 8 in [0, 1] (the LeakyReLU is the identity), weights k / 16 in
+    [-1/4, 1/4] - every partial sum is a multiple of 1 / 128 below
+    168 / 4 = 42 < 2^24 / 128. -> x (2, 24, L), w (1, 24, 7), float64 sums"""
+    gen = torch.Generator().manual_seed(24 + length)
+    x = torch.randint(0, 9, (2, 24, length), generator=gen).float() / 8
+    w = torch.randint(-4, 5, (1, 24, 7), generator=gen).float() / 16
+    return x, w, F.conv1d(x.double(), w.double(), None, padding=3)
+
+
+# (255, 256, 257: the tile edge of the 32-channel kernel, 128 threads x 2)
+@pytest.mark.parametrize('length', [1, 255, 256, 257, 1000])
+def test_out_conv_tanh_both_kernels(device, length):
+    """The same numbers as 24 channels (the generic kernel, padded to 32) and
+    as 32 channels, eight of them zero with zero weights (the 32-channel
+    kernel): both hand the same float to tanhf, so the outputs are equal."""
+    _lib = lib()
+    x, w, acc = out_conv_exact_case(length)
+    assert torch.equal(acc.float().double(), acc)
+    # a saturated tanh would hide a wrong sum
+    assert (acc.abs() < 3).double().mean().item() >= .5
+    x_cl = to_cl(x).to(device)
+    w32 = torch.zeros(1, 32, 7)
+    w32[:, :24] = w
+    outs = []
+    for c, weight in ((24, w), (32, w32)):
+        wd = weight.to(device)
+        out = torch.full((2, length), float('nan'), device=device)
+        _lib.check(_lib.lib().pm_out_conv_tanh(
+            _lib.ptr(x_cl), _lib.ptr(wd), _lib.ptr(out), 2, length, c,
+            _lib.stream()))
+        torch.cuda.synchronize()
+        check(max_abs(out[:, None], torch.tanh(acc)), 6e-6,
+              'out_conv_tanh:fp32', (c, length, 'exact sums'))
+        outs.append(out.cpu())
+    assert torch.equal(outs[0], outs[1]), (
+        length, (outs[0] - outs[1]).abs().max().item())
+
+
 def test_fold_weight_norm(device):
     _lib = lib()
     gen = torch.Generator().manual_seed(2)
