@@ -558,6 +558,57 @@ int pm_resample(const float* x, const int* lengths, const float* bank,
                 int new_rate, int width, int n_out, long long out_stride,
                 void* stream);
 
+/* ---- resampling at any ratio: resampy.resample on the device --------------
+ * Replaces the resampy.resample calls ('kaiser_best') of promonet/data/
+ * augment/{pitch,loudness}.py. Where pm_resample needs one filter per output
+ * phase, this reads ONE long windowed-sinc table with linear interpolation at
+ * a per-output phase, so any pair of rates is served (22 051 -> 22 050, or
+ * int(1.2345 * 44100) -> 44 100).
+ * The table. P = PM_RESAMPLE_INTERP_STEPS = 2^9 steps per zero crossing, 64
+ * zero crossings, N = 64 P; win and delta hold N + 1 =
+ * PM_RESAMPLE_INTERP_TABLE floats. For resampy's filter, in float64,
+ *   win[j] = rolloff sinc(rolloff j / P) kaiser(2 N + 1, beta)[N + j],
+ * multiplied by new / orig when new < orig, delta[j] = win[j + 1] - win[j],
+ * delta[N] = 0, both then rounded to fp32 (promonet_amd/resampy.py). The
+ * entry takes any two tables of that size.
+ * Positions, in integers. For output t of a row with rates (orig, new):
+ *   n = t orig div new, rem = t orig mod new (64 bits), D = max(orig, new),
+ *   left wing:  off  = rem P div D,          eta  = (rem P mod D) / D,
+ *   right wing: off' = (new - rem) P div D,  eta' = ((new - rem) P mod D) / D,
+ *   step = min(orig, new) P div orig,
+ * eta and eta' the fp32 roundings of the exact quotients. (resampy forms the
+ * same quantities in float64 from t (orig / new); they agree wherever float64
+ * does not round across an integer.)
+ * Values. One fp32 accumulator starts at 0; then, ascending,
+ *   i = 0 .. min(n + 1, (N + 1 - off) div step) - 1:
+ *     w = fma(eta, delta[off + i step], win[off + i step])
+ *     acc = fma(w, x[n - i], acc)
+ *   k = 0 .. min(len - n - 1, (N + 1 - off') div step) - 1:
+ *     the same with eta', off' and x[n + k + 1].
+ * A row of length len yields len new div orig outputs; exact zeros follow up
+ * to n_out. A sample's bits depend on its row's samples, its row's rates and
+ * its own index only.
+ * x: `rows` rows of up to n_in samples, x_stride floats apart. lengths, orig,
+ * new_rate: device int32 per row, read on the device only (lengths clamped to
+ * [0, n_in]; NULL: every row has n_in), so one launch carries one ratio per
+ * row and a captured graph replays with other ratios. Asynchronous, no
+ * allocation, no workspace; argument errors are reported before any GPU call.
+ * pm_resample_interp_tile: the outputs one workgroup takes, or PM_EINVAL for
+ * rates the kernel refuses: below 1, 2^21 or more, or a ratio new / orig so
+ * small that the input segment of one tile does not fit the kernel's 6144
+ * floats of LDS (every ratio from 1/5.3 up fits, every upsampling ratio too).
+ * The rates being device data, a row with refused rates is answered on the
+ * device: NaN in all of out[0, n_out) of that row, never a slower walk and
+ * never an access out of bounds.                                            */
+#define PM_RESAMPLE_INTERP_STEPS 512
+#define PM_RESAMPLE_INTERP_TABLE (64 * PM_RESAMPLE_INTERP_STEPS + 1)
+int pm_resample_interp_tile(int orig, int new_rate);
+int pm_resample_interp(const float* x, const int* lengths, const int* orig,
+                       const int* new_rate, const float* win,
+                       const float* delta, float* out, int rows, int n_in,
+                       long long x_stride, int n_out, long long out_stride,
+                       void* stream);
+
 /* ---- Viterbi decoding: torbi.from_probabilities on the device -------------
  * (the decoder of promonet/preprocess/harmonics.py:270-276 and of penn's
  * pitch contour). With A = log transition, B = log observation (batch,

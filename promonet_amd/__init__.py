@@ -14,11 +14,13 @@ from .config import (                                          # noqa: F401
 from . import _lib                                             # noqa: F401
 from . import baseline                                         # noqa: F401
 from . import convert                                          # noqa: F401
+from . import data                                             # noqa: F401
 from . import edit                                             # noqa: F401
 from . import load                                             # noqa: F401
 from . import loss                                             # noqa: F401
 from . import model                                            # noqa: F401
 from . import preprocess                                       # noqa: F401
+from . import resampy                                          # noqa: F401
 from . import synthesize                                       # noqa: F401
 from . import viterbi                                          # noqa: F401
 from . import distributed                                      # noqa: F401

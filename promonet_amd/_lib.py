@@ -121,6 +121,9 @@ SIGNATURES = {
     'pm_resample_tile': (_I, [_I, _I, _I]),
     'pm_resample': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_int64, _I, _I, _I, _I,
                          ctypes.c_int64, _P]),
+    'pm_resample_interp_tile': (_I, [_I, _I]),
+    'pm_resample_interp': (_I, [_P] * 7 + [_I, _I, ctypes.c_int64, _I,
+                                           ctypes.c_int64, _P]),
     'pm_viterbi_workspace': (_S, [_I, _I, _I]),
     'pm_viterbi': (_I, [_P, _P, _P, ctypes.c_int64, _P, _P, _P, _I, _I, _I, _P,
                         _S, _P]),

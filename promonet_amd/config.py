@@ -25,6 +25,9 @@ WINDOW_SIZE = 1024
 # Data / feature parameters (defaults.py:60-135)
 AUGMENT_LOUDNESS = True
 AUGMENT_PITCH = True
+AUGMENTATION_RATIO_MAX = 2.     # defaults.py:81-84; drawn log-uniformly
+AUGMENTATION_RATIO_MIN = .5
+DATASETS = ['daps', 'libritts', 'vctk']
 LOUDNESS_BANDS = 8
 MAX_HARMONICS = 3       # speech harmonics of preprocess.harmonics
 PITCH_EMBEDDING = True
@@ -74,6 +77,7 @@ STEPS = 800000
 ADVERSARIAL_HINGE_LOSS = False      # hinge instead of least-squares GAN terms
 FEATURE_MATCHING_OMIT_FIRST = False  # skip each discriminator's first map
 NUM_WORKERS = 10
+RANDOM_SEED = 1234
 
 # Storage type of the streamed FARGAN weights (math is fp32): 'fp32', 'f16'
 # (6.6e-5 max-abs against the reference on random-init weights, over a 10 s
@@ -126,6 +130,10 @@ COMPUTE_DTYPE = DEFAULT_COMPUTE_DTYPE
 CHECK_DEVICE_SPEAKERS = False
 
 ASSETS_DIR = Path(__file__).parent / 'assets'
+# defaults.py:144-150, static.py:27: where data.augment reads and writes
+ROOT_DIR = Path(__file__).parent.parent
+CACHE_DIR = ROOT_DIR / 'data' / 'cache'
+AUGMENT_DIR = ASSETS_DIR / 'augmentations'
 
 
 def derived():

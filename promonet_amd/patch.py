@@ -15,7 +15,8 @@ def patch(promonet):
     """Monkey-patch the reference package object in place and return it."""
     for name in dir(promonet_amd.config):
         if name.isupper() and hasattr(promonet, name) and name not in (
-                'ASSETS_DIR', 'COMPUTE_DTYPE'):
+                'ASSETS_DIR', 'AUGMENT_DIR', 'CACHE_DIR', 'ROOT_DIR',
+                'COMPUTE_DTYPE'):
             value = getattr(promonet, name)
             if getattr(promonet_amd, name) != value:
                 promonet_amd.configure(**{name: value})
