@@ -136,6 +136,38 @@ int pm_hifigan_forward_ragged(pm_hifigan_t h, const float* features,
                               void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* Streaming by overlap-save (no reference counterpart: the reference
+ * synthesises whole utterances, and its packed_inference, generator.py:
+ * 313-343, treats every chunk as one). The generator is convolutional: the
+ * audio of a frame depends on `left` frames before it and `right` frames
+ * after it, derived from the configuration by interval arithmetic - (13, 13)
+ * at the defaults.                                                         */
+int pm_hifigan_context(pm_hifigan_t h, int* left, int* right);
+/* One streaming step, on `stream`, without allocation or host sync:
+ *   next_window (B, keep + chunk_frames, C_pad) = [the last `keep` frames of
+ *   prev_window (B, prev_frames, C_pad) | chunk], where chunk is (B,
+ *   chunk_frames, C_pad) with chunk_cl != 0 and (B, num_features,
+ *   chunk_frames) otherwise; next_window must alias neither input (the caller
+ *   swaps two buffers). Then, unless emit_frames == 0, the forward of
+ *   pm_hifigan_forward_cl on next_window, and
+ *   out (B, 1, emit_frames * hop) = its audio from frame emit_first on.
+ * The caller's schedule chooses keep <= min(prev_frames, left + right) and
+ * the emitted frames, inside the window, so that every emitted frame has its
+ * context in the window or lies that close to a true end of the utterance;
+ * the concatenated output then equals one forward over the concatenated
+ * chunks bit for bit. chunk_frames == 0 closes a stream: the window is the
+ * history alone. prev_window may be NULL with keep == 0, chunk with
+ * chunk_frames == 0; global_features, out and workspace with emit_frames == 0.
+ * workspace: pm_hifigan_stream_workspace_bytes(h, batch, keep + chunk_frames). */
+int pm_hifigan_stream(pm_hifigan_t h, const float* chunk, int chunk_cl,
+                      int chunk_frames, const float* prev_window,
+                      int prev_frames, int keep, float* next_window,
+                      const float* global_features, int global_batch,
+                      int emit_first, int emit_frames, float* out, int batch,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t pm_hifigan_stream_workspace_bytes(pm_hifigan_t h, int batch,
+                                         int window_frames);
+
 /* Optional per-launch timing (HIP events recorded on `stream` around every
  * kernel the forward launches; no reference counterpart - the reference only
  * has wall-clock torchutil timers, synthesize/core.py:222,250). collect()

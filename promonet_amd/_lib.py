@@ -60,6 +60,10 @@ SIGNATURES = {
     'pm_hifigan_forward': (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _S, _P]),
     'pm_hifigan_forward_cl': (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _S, _P]),
     'pm_hifigan_forward_ragged': (_I, [_P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _S, _P]),
+    'pm_hifigan_context': (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    'pm_hifigan_stream': (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I,
+                               _P, _I, _P, _S, _P]),
+    'pm_hifigan_stream_workspace_bytes': (_S, [_P, _I, _I]),
     'pm_hifigan_profile_enable': (_I, [_P, _I]),
     'pm_hifigan_profile_only': (_I, [_P, ctypes.c_char_p]),
     'pm_hifigan_profile_collect': (_I, [_P]),

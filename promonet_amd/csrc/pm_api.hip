@@ -1011,6 +1011,18 @@ extern "C" int pm_hifigan_forward_ragged(
                         ws, ws_bytes, (hipStream_t)stream, lengths);
 }
 
+// ---- the engine as pm_stream.hip sees it (pm_host.h) -----------------------
+const pm_hifigan_config* pm_hifigan_config_of(pm_hifigan_t h) {
+    return &h->cfg;
+}
+
+int pm_hifigan_forward_window(
+    pm_hifigan_t h, const float* features_cl, const float* g, int gbatch,
+    float* out, int B, int T, void* ws, size_t ws_bytes, hipStream_t s) {
+    return forward_impl(h, features_cl, true, g, gbatch, out, B, T, ws,
+                        ws_bytes, s);
+}
+
 // ---------------------------------------------------------------------------
 // conditioning
 // ---------------------------------------------------------------------------

@@ -81,6 +81,13 @@ hipError_t pm_dft_pack(const float* w, void* out, int cout, int cout_pad,
                        int cin, int k, hipStream_t s);
 hipError_t pm_dft_conv(int epi, const PmDftConv& c, hipStream_t s);
 
+// The HiFi-GAN engine as the streaming entries see it (pm_stream.hip): its
+// configuration, and pm_hifigan_forward_cl with the stream typed.
+const pm_hifigan_config* pm_hifigan_config_of(pm_hifigan_t h);
+int pm_hifigan_forward_window(pm_hifigan_t h, const float* features_cl,
+                              const float* g, int gbatch, float* out, int B,
+                              int T, void* ws, size_t ws_bytes, hipStream_t s);
+
 #ifdef PM_TUNING
 unsigned long long* pm_timeline();   // what pm_debug_timeline set, or null
 #endif

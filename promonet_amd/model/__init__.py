@@ -1,5 +1,5 @@
 from .core import get_padding
 from .fargan import FARGAN, initialize_recurrent_state
 from .generator import Generator, MelGenerator
-from .hifigan import HiFiGAN
+from .hifigan import HiFiGAN, HiFiGANStream, hifigan_context, stream_schedule
 from .vocos import Vocos

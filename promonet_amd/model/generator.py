@@ -324,8 +324,118 @@ class Generator(torch.nn.Module):
         return {'graph': graph, 'input': static, 'output': output,
                 'workspace': private.tensor}
 
+    ###########################################################################
+    # Streaming (HiFi-GAN: overlap-save, hifigan.py::HiFiGANStream)
+    ###########################################################################
+
+    def _streaming_vocoder(self, name):
+        if not isinstance(self.model, HiFiGAN):
+            raise ValueError(
+                f'Generator.{name} streams the HiFi-GAN vocoder; FARGAN '
+                'carries its recurrent state through FARGAN.stream')
+        return self.model
+
+    def open_stream(
+        self, speakers, spectral_balance_ratios, loudness_ratios,
+        lookahead=None, graph=False
+    ):
+        """A stream of `forward`: `push(loudness, pitch, periodicity, ppg)`
+        chunks of frames -> audio, `finish()` the held-back tail; the
+        concatenated audio is bit for bit `forward` over the concatenated
+        chunks (`prepare_features` is per frame). `lookahead`, `graph`:
+        `HiFiGAN.open_stream`."""
+        vocoder = self._streaming_vocoder('open_stream')
+        return GeneratorStream(self, vocoder.open_stream(
+            self.prepare_global_features(
+                speakers, spectral_balance_ratios, loudness_ratios),
+            speakers.shape[0], lookahead, graph))
+
+    def packed_stream(self, lookahead=None, graph=False):
+        """A stream of `packed_inference`: `push(x)` with x (B, 53, c) ->
+        audio, `finish()` the held-back tail - the nn~ interface with chunks
+        that join: the concatenated audio is bit for bit `packed_inference`
+        of the concatenated chunks. The speaker and the two ratios are read
+        at frame 0 of every chunk."""
+        self._streaming_vocoder('packed_stream')
+        return PackedStream(self, lookahead, graph)
+
     def remove_weight_norm(self):
         self.model.remove_weight_norm()
+
+
+class GeneratorStream:
+    """`Generator.open_stream`: feature preparation, chunk by chunk, in front
+    of a `HiFiGANStream`"""
+
+    def __init__(self, generator, stream):
+        self.generator = generator
+        self.stream = stream
+
+    def push(self, loudness, pitch, periodicity, ppg):
+        """(B, 8|513, c), (B, c), (B, c), (B, 40, c) -> (B, 1, 256 emitted)"""
+        if self.stream.closed:
+            raise ValueError('push after finish: reset() starts a new stream')
+        if pitch.shape[-1] == 0:
+            return self.stream._empty()
+        return self.stream.push(
+            self.generator._features(
+                loudness, pitch, periodicity, ppg, channels_last=True),
+            channels_last=True)
+
+    def finish(self):
+        return self.stream.finish()
+
+    def reset(self):
+        self.stream.reset()
+
+
+class PackedStream:
+    """`Generator.packed_stream`: the vocoder stream is opened by the first
+    chunk, which brings the batch size. Unpacking and feature preparation
+    are part of the step: with `graph` they are captured with it, as
+    `packed_inference(graph=True)` captures them."""
+
+    def __init__(self, generator, lookahead, graph):
+        self.generator = generator
+        self.lookahead = lookahead
+        self.graph = graph
+        self.stream = None
+
+    def _prepare(self, x):
+        generator = self.generator
+        unpacked = [t.contiguous() for t in generator.unpack_features(x)]
+        self.stream.set_global_features(
+            generator.prepare_global_features(*unpacked[4:]))
+        return generator._features(*unpacked[:4], channels_last=True)
+
+    def push(self, x):
+        """(B, 53, c) -> (B, 1, 256 emitted) float32"""
+        generator = self.generator
+        _lib.require_gpu(x)
+        if x.ndim != 3 or x.shape[1] != len(generator.labels()):
+            raise ValueError(
+                f'expected a packed (B, {len(generator.labels())}, frames) '
+                f'tensor, got {tuple(x.shape)}')
+        if self.stream is None:
+            if x.shape[-1] == 0:
+                return torch.empty(x.shape[0], 1, 0, device=x.device)
+            self.stream = generator.model.open_stream(
+                generator.prepare_global_features(
+                    *generator.unpack_features(x)[4:]),
+                x.shape[0], self.lookahead, self.graph)
+        if self.stream.batch != x.shape[0]:
+            raise ValueError(
+                f'the stream has {self.stream.batch} rows, got {x.shape[0]}')
+        return self.stream.push(x, prepare=self._prepare)
+
+    def finish(self):
+        if self.stream is None:
+            raise ValueError('finish before the first push')
+        return self.stream.finish()
+
+    def reset(self):
+        if self.stream is not None:
+            self.stream.reset()
 
 
 class MelGenerator(torch.nn.Module):

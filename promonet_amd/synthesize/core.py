@@ -59,7 +59,8 @@ def from_features(
     spectral_balance_ratio: float = 1.,
     loudness_ratio: float = 1.,
     checkpoint: Optional[Union[str, os.PathLike]] = None,
-    gpu: Optional[int] = None
+    gpu: Optional[int] = None,
+    chunk_frames: Optional[int] = None
 ) -> torch.Tensor:
     """Synthesize one utterance from its features (synthesize/core.py:18-59).
 
@@ -68,7 +69,10 @@ def from_features(
     the spectral balance / the loudness), optional generator checkpoint file
     or directory, and the GPU index (required: there is no CPU path).
     Returns (1, 256 T) float32 - utterance 0 of the batch only, as the
-    reference does (core.py:281).
+    reference does (core.py:281). `chunk_frames` (not in the reference; HiFi-GAN)
+    runs the utterance through `Generator.open_stream` that many frames at a
+    time: the same audio bit for bit, in a workspace bounded by the chunk
+    instead of the utterance.
     """
     device = _device(gpu, pitch)
     if loudness.ndim == 2:
@@ -81,7 +85,8 @@ def from_features(
         speaker,
         spectral_balance_ratio,
         loudness_ratio,
-        checkpoint
+        checkpoint,
+        chunk_frames
     ).to(torch.float32)
 
 
@@ -149,7 +154,8 @@ def from_file(
     spectral_balance_ratio: float = 1.,
     loudness_ratio: float = 1.,
     checkpoint: Optional[Union[str, os.PathLike]] = None,
-    gpu: Optional[int] = None
+    gpu: Optional[int] = None,
+    chunk_frames: Optional[int] = None
 ) -> torch.Tensor:
     """`from_features` on features stored as .pt files (core.py:62-111);
     returns (1, samples) float32 on the GPU."""
@@ -159,7 +165,7 @@ def from_file(
             loudness_file, pitch_file, periodicity_file, ppg_file)]
     return from_features(
         *features, speaker, spectral_balance_ratio, loudness_ratio,
-        checkpoint, gpu)
+        checkpoint, gpu, chunk_frames)
 
 
 def from_file_to_file(
@@ -172,12 +178,13 @@ def from_file_to_file(
     spectral_balance_ratio: float = 1.,
     loudness_ratio: float = 1.,
     checkpoint: Optional[Union[str, os.PathLike]] = None,
-    gpu: Optional[int] = None
+    gpu: Optional[int] = None,
+    chunk_frames: Optional[int] = None
 ) -> None:
     """`from_file`, then write a 22.05 kHz wav (core.py:114-155)."""
     audio = from_file(
         loudness_file, pitch_file, periodicity_file, ppg_file, speaker,
-        spectral_balance_ratio, loudness_ratio, checkpoint, gpu)
+        spectral_balance_ratio, loudness_ratio, checkpoint, gpu, chunk_frames)
     target = Path(output_file)
     target.parent.mkdir(exist_ok=True, parents=True)
     save_audio(target, audio.cpu())
@@ -193,7 +200,8 @@ def from_files_to_files(
     spectral_balance_ratio: float = 1.,
     loudness_ratio: float = 1.,
     checkpoint: Optional[Union[str, os.PathLike]] = None,
-    gpu: Optional[int] = None
+    gpu: Optional[int] = None,
+    chunk_frames: Optional[int] = None
 ) -> None:
     """One `from_file_to_file` per utterance, in order - the reference's
     sequential behaviour (core.py:158-201). `from_files_to_files_batched`
@@ -205,7 +213,7 @@ def from_files_to_files(
             loudness_files[index], pitch_files[index],
             periodicity_files[index], ppg_files[index], output_files[index],
             speakers[index], spectral_balance_ratio, loudness_ratio,
-            checkpoint, gpu)
+            checkpoint, gpu, chunk_frames)
 
 
 def from_files_to_files_batched(
@@ -528,7 +536,8 @@ def generate(
     speaker=0,
     spectral_balance_ratio: float = 1.,
     loudness_ratio: float = 1.,
-    checkpoint=None
+    checkpoint=None,
+    chunk_frames=None
 ) -> torch.Tensor:
     """Generate speech from phoneme and prosody features (core.py:209-281)"""
     device = pitch.device
@@ -556,6 +565,10 @@ def generate(
                 spectral_balance_ratio.expand(batch).contiguous()
             loudness_ratio = loudness_ratio.expand(batch).contiguous()
         with torch.inference_mode():
+            if chunk_frames is not None:
+                return _generate_chunked(
+                    model, loudness, pitch, periodicity, ppg, speakers,
+                    spectral_balance_ratio, loudness_ratio, chunk_frames)[0]
             return model(
                 loudness,
                 pitch,
@@ -566,6 +579,26 @@ def generate(
                 loudness_ratio,
                 model.default_previous_samples
             )[0]
+
+
+def _generate_chunked(
+    model, loudness, pitch, periodicity, ppg, speakers,
+    spectral_balance_ratio, loudness_ratio, chunk_frames
+):
+    """`model(...)` through `Generator.open_stream`, `chunk_frames` at a time"""
+    if int(chunk_frames) < 1:
+        raise ValueError('chunk_frames must be at least 1')
+    stream = model.open_stream(
+        speakers, spectral_balance_ratio, loudness_ratio)
+    audio = [
+        stream.push(
+            loudness[..., start:start + chunk_frames],
+            pitch[..., start:start + chunk_frames],
+            periodicity[..., start:start + chunk_frames],
+            ppg[..., start:start + chunk_frames])
+        for start in range(0, pitch.shape[-1], int(chunk_frames))]
+    audio.append(stream.finish())
+    return torch.cat(audio, dim=-1)
 
 
 ###############################################################################
