@@ -779,6 +779,62 @@ int pm_signal_loss_backward(const float* y_true, const float* y_pred,
                             int samples, const void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- discriminator spectrograms: promonet/model/discriminator.py ----------
+ * The transform at the entrance of each spectral discriminator, forward and
+ * backward, on the FFT of the spectral-convergence loss above (the same sizes,
+ * window and twiddle tables). The frames are NOT centred by the transform:
+ * the row is reflect padded by `pad` on both sides (samples > pad) and
+ * frames = 1 + (samples + 2 pad - fft_size) / hop_size >= 1. bins =
+ * fft_size / 2 + 1. win_length (1 .. fft_size) is only checked: the window
+ * (fft_size) arrives zero-padded.
+ *   PM_DISC_SPEC_R    DiscriminatorR.spectrogram (:129-143), pad = (fft_size
+ *                     - hop_size) / 2: out (batch, bins, frames) = |X|
+ *   PM_DISC_SPEC_CMB  DiscriminatorCMB.spectrogram (:175-192), the same pad:
+ *                     out (batch, frames, bins) = |X|, which the caller slices
+ *                     into bands along its last axis
+ *   PM_DISC_SPEC_DB   SpecDiscriminatorBase.spectrogram (:278-299), pad =
+ *                     fft_size / 2: out (batch, bins, frames) = max(d, floor),
+ *                     d = 20 log10 max(|X|, 1e-5), floor = (max of d over the
+ *                     WHOLE batch) - 80; stats (2 device floats) receives
+ *                     (max, floor). The maximum goes through one partial a
+ *                     workgroup in the workspace; nothing syncs with the host.
+ * stats and the workspace may be NULL for R and CMB.
+ * Backward: grad_x (batch, samples) = (or, with accumulate, +=) scale[0] *
+ * (d <upstream, out> / d x); scale is a device scalar, NULL for 1. upstream
+ * has the layout of the mode's out. The transform is computed again from x;
+ * the bin gradient is upstream X / |X| (0 where |X| = 0) for R and CMB. For DB
+ * the caller passes the forward's out and stats back: an element with
+ * saved_out > floor passes upstream (20 / ln 10) X / |X|^2 where |X| >= 1e-5
+ * and nothing below; the others pass their upstream to the floor, and the sum
+ * of those (fixed-order partials in double, one final pass) is shared evenly
+ * among the elements whose saved_out equals max. An element exactly at the
+ * floor before the floor was applied counts as floored (torch gives each side
+ * a half). Then the adjoint of pm_sc_adjoint with the margins of `pad`.
+ * No float atomics: every output is bit-identical from run to run. All
+ * asynchronous, no allocation, capturable. Sizes outside the limits (fft_size
+ * not 2^a or 5 2^a in [64, 2560], hop_size outside [1, fft_size], win_length
+ * outside [1, fft_size], pad outside [0, fft_size], samples <= pad, less than
+ * one frame, an unknown mode) return PM_EINVAL before any device work; the
+ * workspace query returns 0 for them and at least 256 otherwise.            */
+#define PM_DISC_SPEC_R 0
+#define PM_DISC_SPEC_CMB 1
+#define PM_DISC_SPEC_DB 2
+size_t pm_disc_spec_workspace_bytes(int mode, int batch, int samples,
+                                    int fft_size, int hop_size, int win_length,
+                                    int pad, int backward);
+int pm_disc_spec_forward(int mode, const float* x, const float* window,
+                         const float* twiddle, float* out, float* stats,
+                         int batch, int samples, int fft_size, int hop_size,
+                         int win_length, int pad, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int pm_disc_spec_backward(int mode, const float* x, const float* window,
+                          const float* twiddle, const float* upstream,
+                          const float* saved_out, const float* stats,
+                          const float* scale, float* grad_x, int accumulate,
+                          int batch, int samples, int fft_size, int hop_size,
+                          int win_length, int pad, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- adversarial losses: promonet/train/loss.py:11-53 ---------------------
  * feature_matching, discriminator and generator are each a sum of means over
  * a list of tensors of unrelated sizes. pm_multi_mean takes the whole list:

@@ -1,3 +1,4 @@
+from . import discriminator
 from .core import get_padding
 from .fargan import FARGAN, initialize_recurrent_state
 from .generator import Generator, MelGenerator

@@ -5,8 +5,10 @@ After patching, `promonet.synthesize.from_features(..., gpu=N)`,
 `promonet.model.Generator()` and `promonet.preprocess.spectrogram.from_audio`
 / `promonet.preprocess.loudness.from_audio` / `limit` / `scale` / `shift` run on
 libpromonet_hip.so, and,
-where the target has them, `promonet.model.Vocos` / `MelGenerator` and
-`promonet.baseline.mels.*`.
+where the target has them, `promonet.model.Vocos` / `MelGenerator`,
+`promonet.baseline.mels.*` and the `spectrogram` methods of
+`promonet.model.discriminator` (DiscriminatorR, DiscriminatorCMB,
+SpecDiscriminatorBase; a CPU tensor still takes the target's own method).
 """
 import promonet_amd
 
@@ -49,6 +51,11 @@ def patch(promonet):
     for name in ('Vocos', 'MelGenerator'):
         if hasattr(promonet.model, name):
             setattr(promonet.model, name, getattr(promonet_amd.model, name))
+    # the spectrograms of the spectral discriminators, where the target has
+    # them; the conv stacks stay the target's own
+    discriminator = getattr(promonet.model, 'discriminator', None)
+    if discriminator is not None:
+        promonet_amd.model.discriminator.patch_module(discriminator)
     mels = getattr(getattr(promonet, 'baseline', None), 'mels', None)
     if mels is not None:
         for name in (
