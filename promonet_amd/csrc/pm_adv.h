@@ -192,7 +192,7 @@ __device__ __forceinline__ float adv_gradient(float a, float b, float c) {
     return 1.f + a >= 0.f ? c : 0.f;
 }
 
-// Sum over the workgroup in a fixed order (sc_block_sum of pm_loss.h); the
+// Sum over the workgroup in a fixed order (sc_block_sum of pm_stockham.h); the
 // result is valid in thread 0.
 __device__ __forceinline__ float adv_block_sum(float v, float* scratch) {
 #pragma unroll

@@ -1,6 +1,6 @@
 // The spectrograms at the entrance of the spectral discriminators
-// (promonet/model/discriminator.py), forward and backward, on the FFT core of
-// pm_loss.h (sc_stage, sc_fft, sc_bin; the plan, the tables and the split of a
+// (promonet/model/discriminator.py), forward and backward, on the transform of
+// pm_stockham.h (the plan, the loader, the FFT, the tables and the split of a
 // row's frames over workgroups are that file's):
 //   R    DiscriminatorR.spectrogram (:129-143): |X| as (B, bins, frames);
 //   CMB  DiscriminatorCMB.spectrogram (:175-192): |X| as (B, frames, bins),
@@ -12,8 +12,9 @@
 // and frames = 1 + (T + 2 pad - N) / hop.
 //
 // Backward: the transform again from x, the bin gradient G (B, bins, frames, 2)
-// from the upstream gradient, sc_adjoint_frames_kernel (which knows nothing of
-// the padding) and an overlap-add in gather form with `pad` as a parameter.
+// from the upstream gradient, and the adjoint pair of pm_loss.h through
+// pm_sc_adjoint_launch (pm_host.h): the frames, then their overlap-add in
+// gather form with the plan's `pad`.
 // DB reads the forward's output and its (max, floor) instead of a second
 // reduction over a second transform: an element is on the floor where the
 // saved output is <= floor, it holds the maximum where the saved output equals
@@ -26,7 +27,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "pm_loss.h"
+#include "pm_stockham.h"
 
 #define DS_R 0
 #define DS_CMB 1
@@ -47,35 +48,8 @@ struct DsArgs {
     float* out;             // forward: R, DB (B, bins, frames); CMB (B, frames, bins)
     float* G;               // GRAD: (B, bins, frames, 2)
     float* partials;        // forward, DB: one maximum a workgroup
-    ScPlan p;               // (p.frames: the non-centred count)
-    int pad;
+    ScPlan p;
 };
-
-// sc_load with the margin as a parameter: frame f begins at padded sample
-// f hop, which is sample f hop - pad, reflected once where it leaves the row.
-__device__ __forceinline__ void ds_load(float2* __restrict__ dst,
-                                        const float* __restrict__ x,
-                                        const float* __restrict__ window,
-                                        const ScPlan& p, int pad, int f0,
-                                        int count) {
-    const int total = count * p.M;
-    for (int i = threadIdx.x; i < total; i += SC_THREADS) {
-        const int fl = i / p.M, m = i - fl * p.M;
-        const int start = (f0 + fl) * p.hop - pad;
-        float pair[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            int n = start + 2 * m + h;
-            if (n < 0) n = -n;
-            if (n >= p.T) n = 2 * (p.T - 1) - n;
-            // (T > pad: one reflection reaches every sample; the clamp only
-            // keeps a caller's mistake inside the row)
-            n = n < 0 ? 0 : (n >= p.T ? p.T - 1 : n);
-            pair[h] = x[n] * window[2 * m + h];
-        }
-        dst[i] = make_float2(pair[0], pair[1]);
-    }
-}
 
 // Maximum over the workgroup; the result is valid in thread 0.
 __device__ __forceinline__ float ds_block_max(float v, float* scratch) {
@@ -107,7 +81,7 @@ __global__ __launch_bounds__(SC_THREADS) void ds_transform_kernel(DsArgs a) {
     float2* buf0 = ds_lds;
     float2* buf1 = ds_lds + p.fpg * p.M;
     const float2* __restrict__ tw = (const float2*)a.twiddle;
-    ds_load(buf0, a.x + (long long)row * p.T, a.window, p, a.pad, f0, count);
+    sc_load(buf0, a.x + (long long)row * p.T, a.window, p, f0, count);
     const float2* __restrict__ Z = sc_fft(buf0, buf1, tw, p, count);
     const int bins = p.M + 1;
     const long long base = (long long)row * bins * p.frames;
@@ -236,36 +210,4 @@ __global__ __launch_bounds__(SC_THREADS) void ds_share_kernel(
     if (threadIdx.x == 0)
         share[0] = scratch[1][0] > 0. ? (float)(scratch[0][0] / scratch[1][0])
                                       : 0.f;
-}
-
-// Overlap-add in gather form and the adjoint of a reflect margin of `pad`:
-// sample i of a row is padded sample i + pad; samples 1 .. pad also own the
-// left margin's pad - i, samples T-1-pad .. T-2 the right margin's
-// pad + 2 (T - 1) - i. A padded sample sums the frames that cover it in
-// ascending order (sc_padded_sample; a padded sample past the last frame sums
-// nothing); the (up to) three are added centre, left, right.
-// grad_x = (or +=) scale[0] * that; a null scale is 1.
-struct DsOverlapArgs {
-    const float* frames_in;     // (B, frames, N)
-    const float* scale;         // device scalar or NULL
-    float* grad_x;              // (B, T)
-    int N, pad, hop, frames, T, accumulate;
-    long long total;            // B * T
-};
-
-__global__ __launch_bounds__(SC_THREADS) void ds_overlap_kernel(
-    DsOverlapArgs a) {
-    const long long at = (long long)blockIdx.x * SC_THREADS + threadIdx.x;
-    if (at >= a.total) return;
-    const int row = (int)(at / a.T), i = (int)(at - (long long)row * a.T);
-    const float* __restrict__ fr =
-        a.frames_in + (long long)row * a.frames * a.N;
-    float sum = sc_padded_sample(fr, a.N, a.hop, a.frames, i + a.pad);
-    if (i >= 1 && i <= a.pad)
-        sum += sc_padded_sample(fr, a.N, a.hop, a.frames, a.pad - i);
-    if (i <= a.T - 2 && i >= a.T - 1 - a.pad)
-        sum += sc_padded_sample(fr, a.N, a.hop, a.frames,
-                                a.pad + 2 * (a.T - 1) - i);
-    const float v = a.scale ? a.scale[0] * sum : sum;
-    a.grad_x[at] = a.accumulate ? a.grad_x[at] + v : v;
 }

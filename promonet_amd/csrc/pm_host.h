@@ -81,6 +81,17 @@ hipError_t pm_dft_pack(const float* w, void* out, int cout, int cout_pad,
                        int cin, int k, hipStream_t s);
 hipError_t pm_dft_conv(int epi, const PmDftConv& c, hipStream_t s);
 
+// The adjoint of the short-time transform of a plan (pm_stockham.h), whose
+// kernels are compiled with the losses (pm_loss.hip): G (B, bins, frames, 2)
+// to the windowed frames (B, frames, N) in `frames`, then their overlap-add
+// and the adjoint of the reflect margin; grad_x (B, T) = (or +=, `accumulate`)
+// scale[0] * that, a null scale being 1.
+struct ScPlan;
+hipError_t pm_sc_adjoint_launch(const ScPlan& p, int batch, const float* G,
+                                const float* window, const float* twiddle,
+                                const float* scale, float* grad_x,
+                                int accumulate, float* frames, hipStream_t s);
+
 // The HiFi-GAN engine as the streaming entries see it (pm_stream.hip): its
 // configuration, and pm_hifigan_forward_cl with the stream typed.
 const pm_hifigan_config* pm_hifigan_config_of(pm_hifigan_t h);

@@ -2,17 +2,9 @@
 // the spectral-convergence loss (:61-150) as a centred STFT, its bin gradient
 // and the adjoint of the STFT, and the waveform `signal` loss (:158-162).
 //
-// The transform. A frame of N real points (N = 2^a or 5 2^a, 64 <= N <= 2560)
-// is the complex transform of M = N / 2 points z[m] = v[2m] + i v[2m+1] and
-// the split  X[k] = E[k] + W^k O[k],  E = (Z[k] + conj Z[M-k]) / 2,
-// O = -i (Z[k] - conj Z[M-k]) / 2,  W = exp(-2 pi i / N),  0 <= k <= M.
-// The M-point transform is a Stockham autosort FFT between two LDS buffers:
-// one radix-5 stage for the 5 2^a sizes, then radix-4 stages and at most one
-// radix-2 stage (the plan is made on the host, pm_loss.hip). A workgroup
-// carries `fpg` frames of one row at once (and, for the loss, the same frames
-// of the target), and the butterflies of all of them are dealt to the 256
-// threads as one pool: at N = 64 a workgroup holds 32 frames, at N = 2560 one.
-// Twiddles come from one table W^m, m < N, rounded from float64 on the host.
+// The transform, its plan and its loader are pm_stockham.h's, centred:
+// pad = N / 2. The adjoint pair below takes the margin from the plan, so the
+// discriminator spectrograms (pm_disc_spec.hip) launch it too.
 //
 // Nothing here uses a float atomic: sums go through per-workgroup partials and
 // one final pass, overlap-add is in gather form, so every output is the same
@@ -20,16 +12,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#define SC_THREADS 256
-#define SC_MAX_STAGES 8
-#define SC_MAX_POINTS 1280          // complex points of a workgroup's pool
-#define SC_FLOOR 1e-7f              // torch.clamp(magnitude, min=1e-7)
+#include "pm_stockham.h"
 
-struct ScPlan {
-    int N, M, hop, frames, T, fpg, groups;  // groups: workgroups per row
-    int stages;
-    int radix[SC_MAX_STAGES];
-};
+#define SC_FLOOR 1e-7f              // torch.clamp(magnitude, min=1e-7)
 
 struct ScForwardArgs {
     const float* x;         // (B, T)
@@ -43,143 +28,6 @@ struct ScForwardArgs {
     float* partials;        // (workgroups, 2) or NULL
     ScPlan p;
 };
-
-__device__ __forceinline__ float2 sc_mul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-// One Stockham stage of radix R over `slots` transforms of M points that lie
-// back to back in `in`; Ns is the product of the radices already done.
-template <int R>
-__device__ __forceinline__ void sc_stage(const float2* __restrict__ in,
-                                         float2* __restrict__ out,
-                                         const float2* __restrict__ tw,
-                                         int slots, int M, int Ns) {
-    const int per = M / R;                  // butterflies of one transform
-    const int step = M / (Ns * R);          // W_M^(k step) = W_(Ns R)^k
-    const int total = slots * per;
-    for (int i = threadIdx.x; i < total; i += SC_THREADS) {
-        const int slot = i / per, j = i - slot * per;
-        const int k = j % Ns;
-        const float2* __restrict__ src = in + slot * M;
-        float2 v[R];
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            v[q] = src[j + q * per];
-            // (the table has N = 2 M entries: W_M^m is entry 2 m)
-            if (q) v[q] = sc_mul(v[q], tw[2 * (q * k * step)]);
-        }
-        float2 o[R];
-        if (R == 2) {
-            o[0] = make_float2(v[0].x + v[1].x, v[0].y + v[1].y);
-            o[1] = make_float2(v[0].x - v[1].x, v[0].y - v[1].y);
-        } else if (R == 4) {
-            const float2 a0 = make_float2(v[0].x + v[2].x, v[0].y + v[2].y);
-            const float2 a1 = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
-            const float2 a2 = make_float2(v[1].x + v[3].x, v[1].y + v[3].y);
-            // -i (v1 - v3)
-            const float2 a3 = make_float2(v[1].y - v[3].y, v[3].x - v[1].x);
-            o[0] = make_float2(a0.x + a2.x, a0.y + a2.y);
-            o[1] = make_float2(a1.x + a3.x, a1.y + a3.y);
-            o[2] = make_float2(a0.x - a2.x, a0.y - a2.y);
-            o[3] = make_float2(a1.x - a3.x, a1.y - a3.y);
-        } else {
-            const float c1 = 0.30901699437494742f, c2 = -0.80901699437494742f;
-            const float s1 = 0.95105651629515357f, s2 = 0.58778525229247313f;
-            const float2 t1 = make_float2(v[1].x + v[4].x, v[1].y + v[4].y);
-            const float2 t2 = make_float2(v[2].x + v[3].x, v[2].y + v[3].y);
-            const float2 t3 = make_float2(v[1].x - v[4].x, v[1].y - v[4].y);
-            const float2 t4 = make_float2(v[2].x - v[3].x, v[2].y - v[3].y);
-            o[0] = make_float2(v[0].x + t1.x + t2.x, v[0].y + t1.y + t2.y);
-            const float2 m1 = make_float2(v[0].x + c1 * t1.x + c2 * t2.x,
-                                          v[0].y + c1 * t1.y + c2 * t2.y);
-            const float2 m2 = make_float2(v[0].x + c2 * t1.x + c1 * t2.x,
-                                          v[0].y + c2 * t1.y + c1 * t2.y);
-            const float2 n1 = make_float2(s1 * t3.x + s2 * t4.x,
-                                          s1 * t3.y + s2 * t4.y);
-            const float2 n2 = make_float2(s2 * t3.x - s1 * t4.x,
-                                          s2 * t3.y - s1 * t4.y);
-            // X1 = m1 - i n1, X4 = m1 + i n1, X2 = m2 - i n2, X3 = m2 + i n2
-            o[1] = make_float2(m1.x + n1.y, m1.y - n1.x);
-            o[4] = make_float2(m1.x - n1.y, m1.y + n1.x);
-            o[2] = make_float2(m2.x + n2.y, m2.y - n2.x);
-            o[3] = make_float2(m2.x - n2.y, m2.y + n2.x);
-        }
-        float2* __restrict__ dst = out + slot * M + (j / Ns) * Ns * R + k;
-#pragma unroll
-        for (int q = 0; q < R; ++q) dst[q * Ns] = o[q];
-    }
-}
-
-// Every stage of the plan over the pool; returns the buffer the result is in.
-// Every thread of the workgroup must call it (it holds barriers).
-__device__ __forceinline__ float2* sc_fft(float2* a, float2* b,
-                                          const float2* __restrict__ tw,
-                                          const ScPlan& p, int slots) {
-    int Ns = 1;
-    __syncthreads();
-    for (int s = 0; s < p.stages; ++s) {
-        const int r = p.radix[s];
-        if (r == 5) sc_stage<5>(a, b, tw, slots, p.M, Ns);
-        else if (r == 4) sc_stage<4>(a, b, tw, slots, p.M, Ns);
-        else sc_stage<2>(a, b, tw, slots, p.M, Ns);
-        Ns *= r;
-        __syncthreads();
-        float2* t = a; a = b; b = t;
-    }
-    return a;
-}
-
-// Frames [f0, f0 + count) of one row, windowed, reflect padded and packed
-// into `count` transforms of M complex points.
-__device__ __forceinline__ void sc_load(float2* __restrict__ dst,
-                                        const float* __restrict__ x,
-                                        const float* __restrict__ window,
-                                        const ScPlan& p, int f0, int count) {
-    const int total = count * p.M;
-    for (int i = threadIdx.x; i < total; i += SC_THREADS) {
-        const int fl = i / p.M, m = i - fl * p.M;
-        const int start = (f0 + fl) * p.hop - p.M;      // centre: N / 2 = M
-        float pair[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            int n = start + 2 * m + h;
-            if (n < 0) n = -n;
-            if (n >= p.T) n = 2 * (p.T - 1) - n;
-            // (T > N / 2: one reflection reaches every sample; the clamp only
-            // keeps a caller's mistake inside the row)
-            n = n < 0 ? 0 : (n >= p.T ? p.T - 1 : n);
-            pair[h] = x[n] * window[2 * m + h];
-        }
-        dst[i] = make_float2(pair[0], pair[1]);
-    }
-}
-
-// Bin k (0 <= k <= M) of a real frame from its packed transform Z.
-__device__ __forceinline__ float2 sc_bin(const float2* __restrict__ Z,
-                                         const float2* __restrict__ tw,
-                                         int M, int k) {
-    const float2 zk = Z[k == M ? 0 : k];
-    const float2 zc = Z[k == 0 ? 0 : M - k];
-    const float er = .5f * (zk.x + zc.x), ei = .5f * (zk.y - zc.y);
-    const float orr = .5f * (zk.y + zc.y), oi = -.5f * (zk.x - zc.x);
-    float2 w = make_float2(-1.f, 0.f);                  // W^M
-    if (k < M) w = tw[k];
-    return make_float2(er + (orr * w.x - oi * w.y),
-                       ei + (orr * w.y + oi * w.x));
-}
-
-// Sum over the workgroup, in a fixed order; the result is valid in thread 0.
-__device__ __forceinline__ float sc_block_sum(float v, float* scratch) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float total = scratch[0];
-    for (int w = 1; w < SC_THREADS / 64; ++w) total += scratch[w];
-    return total;
-}
 
 // pm_sc_stft (PAIR = false: s of x, or G from an upstream gradient) and
 // pm_sc_forward (PAIR = true: the two sums and G). LDS: two buffers of
@@ -335,17 +183,18 @@ __global__ __launch_bounds__(SC_THREADS) void sc_adjoint_frames_kernel(
     }
 }
 
-// Second half: overlap-add in gather form and the adjoint of the reflect
-// padding. Sample i of a row is padded sample i + M; samples 1 .. M also own
-// the left margin's M - i, samples T-1-M .. T-2 the right margin's
-// M + 2 (T - 1) - i. A padded sample sums the frames that cover it in
-// ascending order; the (up to) three padded samples are added centre, left,
-// right. grad_x = (or +=) scale[0] * that.
+// Second half: overlap-add in gather form and the adjoint of a reflect margin
+// of `pad`. Sample i of a row is padded sample i + pad; samples 1 .. pad also
+// own the left margin's pad - i, samples T-1-pad .. T-2 the right margin's
+// pad + 2 (T - 1) - i. A padded sample sums the frames that cover it in
+// ascending order (one past the last frame sums nothing); the (up to) three
+// padded samples are added centre, left, right.
+// grad_x = (or +=) scale[0] * that; a null scale is 1.
 struct ScOverlapArgs {
     const float* frames_in;     // (B, frames, N)
-    const float* scale;         // device scalar
+    const float* scale;         // device scalar or NULL
     float* grad_x;              // (B, T)
-    int N, M, hop, frames, T, accumulate;
+    int N, pad, hop, frames, T, accumulate;
     long long total;            // B * T
 };
 
@@ -368,13 +217,13 @@ __global__ __launch_bounds__(SC_THREADS) void sc_overlap_kernel(
     const int row = (int)(at / a.T), i = (int)(at - (long long)row * a.T);
     const float* __restrict__ fr =
         a.frames_in + (long long)row * a.frames * a.N;
-    float sum = sc_padded_sample(fr, a.N, a.hop, a.frames, i + a.M);
-    if (i >= 1 && i <= a.M)
-        sum += sc_padded_sample(fr, a.N, a.hop, a.frames, a.M - i);
-    if (i <= a.T - 2 && i >= a.T - 1 - a.M)
+    float sum = sc_padded_sample(fr, a.N, a.hop, a.frames, i + a.pad);
+    if (i >= 1 && i <= a.pad)
+        sum += sc_padded_sample(fr, a.N, a.hop, a.frames, a.pad - i);
+    if (i <= a.T - 2 && i >= a.T - 1 - a.pad)
         sum += sc_padded_sample(fr, a.N, a.hop, a.frames,
-                                a.M + 2 * (a.T - 1) - i);
-    const float v = a.scale[0] * sum;
+                                a.pad + 2 * (a.T - 1) - i);
+    const float v = a.scale ? a.scale[0] * sum : sum;
     a.grad_x[at] = a.accumulate ? a.grad_x[at] + v : v;
 }
 

@@ -59,6 +59,25 @@ TABLE = [
     ('pm_sc_adjoint_workspace_bytes', (2, 8192, 1024, 256), 270336),
     ('pm_signal_loss_workspace_bytes', (0,), 0),
     ('pm_signal_loss_workspace_bytes', (3,), 256),
+    # (mode R, CMB, DB = 0, 1, 2; ...; win_length, pad, backward), recorded
+    # before the transform's plan was stated once (pm_stockham.h): R's and
+    # CMB's forward layouts are empty and answer 256; a refused size (T = pad)
+    # answers 0
+    ('pm_disc_spec_workspace_bytes', (0, 2, 4096, 1024, 120, 600, 452, 0),
+     256),
+    ('pm_disc_spec_workspace_bytes', (0, 2, 4096, 1024, 120, 600, 452, 1),
+     557824),
+    ('pm_disc_spec_workspace_bytes', (1, 2, 4096, 1024, 256, 1024, 384, 0),
+     256),
+    ('pm_disc_spec_workspace_bytes', (1, 2, 4096, 1024, 256, 1024, 384, 1),
+     262400),
+    ('pm_disc_spec_workspace_bytes', (2, 2, 1000, 64, 16, 64, 32, 0), 256),
+    ('pm_disc_spec_workspace_bytes', (2, 2, 1000, 64, 16, 64, 32, 1), 66048),
+    ('pm_disc_spec_workspace_bytes', (2, 40, 1000, 64, 16, 64, 32, 0), 512),
+    ('pm_disc_spec_workspace_bytes', (2, 3, 3000, 2048, 512, 2048, 1024, 1),
+     295680),
+    ('pm_disc_spec_workspace_bytes', (0, 2, 231, 512, 50, 240, 231, 0), 0),
+    ('pm_disc_spec_workspace_bytes', (0, 2, 231, 512, 50, 240, 231, 1), 0),
     ('pm_convnext_block_workspace_bytes', (F16, 512, 1536), 3160064),
     ('pm_convnext_block_workspace_bytes', (BF16, 512, 1024), 2111488),
     ('pm_convnext_block_workspace_bytes', (F32, 512, 1536), 6305792),
