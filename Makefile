@@ -30,6 +30,11 @@ $(OBJ)/pm_limit.o: CXXFLAGS += -ffp-contract=off
 # the multi-tensor mean rounds every product and sum on its own, as the fp32
 # restatement of its tests does; its division stays correctly rounded (pm_adv.h)
 $(OBJ)/pm_adv.o: CXXFLAGS += -ffp-contract=off
+# the optimizer step is bit for bit its restatement (tests/optim_oracle.py):
+# every fp32 and double product and sum rounds on its own, and a NaN gradient
+# is counted: without -fhonor-nans the compiler reads the test of the exponent
+# bits as |g| != inf and lets NaN pass (pm_optim.h)
+$(OBJ)/pm_optim.o: CXXFLAGS += -ffp-contract=off -fhonor-nans
 # the whole-MRF kernels: see pm_conv_bf16_mrf.hip
 MRF_FLAGS ?= -mllvm -amdgpu-sched-strategy=max-ilp
 HDRS = $(wildcard $(SRC)/*.h) include/promonet_hip.h

@@ -888,6 +888,92 @@ int pm_multi_mean_backward(const void* const* a, const void* const* b,
                            void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ---- optimizer step: promonet/train/core.py:335-369 ------------------------
+ * The gradient statistics, the clip, the AdamW update and the update of the
+ * loss scale of a training step, with no host read in between. An entry is
+ * one parameter: param, exp_avg and exp_avg_sq dense fp32, grad numel[k] dense
+ * elements of dtype[k] = PM_F32, PM_F16 or PM_BF16, read as stored. param,
+ * exp_avg, exp_avg_sq, grad, numel and dtype are HOST arrays of `count`
+ * values (device pointers where they are pointers). A tensor is cut into
+ * chunks of pm_optim_chunk() elements, one workgroup a chunk, and a chunk
+ * never spans two tensors; the table of entries travels in the kernel
+ * arguments, pm_optim_entries_per_launch() entries a launch: no host-to-device
+ * copy, any count. No float atomics: every output is bit-identical from run
+ * to run.
+ * pm_optim_grad_stats: over the whole list the maximum and the minimum
+ * gradient, mean = sum / numel, norm = sqrt(sum of squares) (the L2 norm of
+ * the concatenation) and the count of NaN and +-inf elements, which are left
+ * out of the other four. The sums: fp32 inside a chunk in pm_multi_mean's
+ * order, the chunks in ascending order in double, rounded once. They go to
+ * `stats`, PM_OPTIM_STATS device floats indexed by PM_OPTIM_*, with the
+ * step's control block:
+ *   FOUND_INF  1 if the count is not 0, or found_inf (an optional device
+ *              scalar, torch's protocol for fused optimizers) is not 0; else 0
+ *   INV_SCALE  (float)(1.0 / (double)grad_scale[0]) of the optional device
+ *              scalar grad_scale, else 1
+ *   COEF       1; with clip >= 0 (a negative clip is no clip) the reference's
+ *              order: if max(max, |min|) of the gradients as they are (still
+ *              scaled) is above clip,  total = max(max, |min|) INV_SCALE  and
+ *              COEF = min((float)clip / (total + 1e-6f), 1.f)
+ * and, unless FOUND_INF, advance `state` (optional; 3 device doubles {step,
+ * beta1^step, beta2^step}): step += 1 and one multiplication of each power.
+ * pm_optim_adamw_step: nothing when FOUND_INF; else for every element, each
+ * fp32 operation rounded on its own, / and sqrt correctly rounded,
+ *   g = (grad INV_SCALE) COEF
+ *   p = p (float)(1 - lr weight_decay)
+ *   m = m + (float)(1 - beta1) (g - m)
+ *   v = v (float)beta2 + (float)(1 - beta2) (g g)
+ *   d = sqrtf(v) / (float)sqrt(1 - state[2]) + (float)eps
+ *   p = p + (float)(-lr / (1 - state[1])) (m / d)
+ * with the constants formed in double on the device. stats and state MUST be
+ * those that one pm_optim_grad_stats call wrote for the same list just before:
+ * every such call with a state advances the step (unless FOUND_INF), so one
+ * statistics call goes with one update, and a second statistics call without
+ * an update moves the step and the powers on (pass state = NULL for
+ * statistics alone). The hyper-parameters are
+ * kernel arguments: a captured graph keeps the values it was captured with.
+ * pm_optim_scaler_update: torch.amp.GradScaler.update()'s rule on the device
+ * scalars scale (fp32) and growth_tracker (int32): if any of the `count`
+ * (1 .. 8) device scalars found_inf[k] (a HOST array) is not 0, scale *=
+ * backoff and the tracker = 0; else the tracker += 1 and, when it reaches
+ * growth_interval, scale *= growth (unless that is inf) and the tracker = 0.
+ * The products are made in double and rounded once. Then every found_inf[k]
+ * is set to 0.
+ * All three are asynchronous, allocate nothing and capture into a graph. Bad
+ * arguments (count <= 0, a NULL array or pointer, numel <= 0, an unknown
+ * dtype, a clip, lr, beta, eps, weight_decay or factor that is not finite, a
+ * beta outside [0, 1), a negative lr, eps or weight_decay, growth <= 1,
+ * backoff outside (0, 1), growth_interval <= 0, a workspace smaller than
+ * pm_optim_workspace_bytes) return PM_EINVAL before any device work; the
+ * workspace query returns 0 for them. */
+#define PM_OPTIM_MAX 0
+#define PM_OPTIM_MIN 1
+#define PM_OPTIM_MEAN 2
+#define PM_OPTIM_NORM 3
+#define PM_OPTIM_NORM_SQ 4          /* the sum of squares, rounded once */
+#define PM_OPTIM_NONFINITE 5        /* the count, rounded to fp32 */
+#define PM_OPTIM_FOUND_INF 6
+#define PM_OPTIM_INV_SCALE 7
+#define PM_OPTIM_COEF 8
+#define PM_OPTIM_STATS 16
+int pm_optim_chunk(void);
+int pm_optim_entries_per_launch(void);
+size_t pm_optim_workspace_bytes(const long long* numel, int count);
+int pm_optim_grad_stats(const void* const* grad, const long long* numel,
+                        const int* dtype, int count, const float* grad_scale,
+                        const float* found_inf, double clip, double beta1,
+                        double beta2, double* state, float* stats,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int pm_optim_adamw_step(void* const* param, void* const* exp_avg,
+                        void* const* exp_avg_sq, const void* const* grad,
+                        const long long* numel, const int* dtype, int count,
+                        const float* stats, const double* state, double lr,
+                        double beta1, double beta2, double eps,
+                        double weight_decay, void* stream);
+int pm_optim_scaler_update(float* scale, int* growth_tracker,
+                           float* const* found_inf, int count, double growth,
+                           double backoff, int growth_interval, void* stream);
+
 /* ---- Vocos mel vocoder engine: replaces promonet.model.Vocos --------------
  * (promonet/model/vocos.py, config/baselines/vocos.py MODEL = 'vocos').
  * conv_pre (k7) + cond, backbone embed (k7) + LayerNorm, `layers` fused

@@ -25,6 +25,10 @@ DISC_SPEC_R, DISC_SPEC_CMB, DISC_SPEC_DB = range(3)
 # the ops of pm_multi_mean (PM_ADV_*, promonet_hip.h)
 (ADV_ABS_DIFF, ADV_SQ_ONE_MINUS, ADV_SQ, ADV_HINGE_ONE_MINUS,
  ADV_HINGE_ONE_PLUS) = range(5)
+# the floats of pm_optim_grad_stats' block (PM_OPTIM_*, promonet_hip.h)
+(OPTIM_MAX, OPTIM_MIN, OPTIM_MEAN, OPTIM_NORM, OPTIM_NORM_SQ, OPTIM_NONFINITE,
+ OPTIM_FOUND_INF, OPTIM_INV_SCALE, OPTIM_COEF) = range(9)
+OPTIM_STATS = 16
 
 c_float_p = ctypes.c_void_p
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -48,6 +52,7 @@ class HifiganConfig(ctypes.Structure):
 
 # name -> (restype, argtypes); every symbol include/promonet_hip.h declares
 _I, _F, _P, _S = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+_D = ctypes.c_double
 SIGNATURES = {
     'pm_version': (_I, []),
     'pm_last_error': (ctypes.c_char_p, []),
@@ -155,6 +160,13 @@ SIGNATURES = {
     'pm_multi_mean_workspace_bytes': (_S, [_P, _I]),
     'pm_multi_mean': (_I, [_P] * 5 + [_I, _P, _P, _S, _P]),
     'pm_multi_mean_backward': (_I, [_P] * 5 + [_I] + [_P] * 4 + [_S, _P]),
+    'pm_optim_chunk': (_I, []),
+    'pm_optim_entries_per_launch': (_I, []),
+    'pm_optim_workspace_bytes': (_S, [_P, _I]),
+    'pm_optim_grad_stats': (_I, [_P] * 3 + [_I, _P, _P] + [_D] * 3 +
+                            [_P, _P, _P, _S, _P]),
+    'pm_optim_adamw_step': (_I, [_P] * 6 + [_I, _P, _P] + [_D] * 5 + [_P]),
+    'pm_optim_scaler_update': (_I, [_P, _P, _P, _I, _D, _D, _I, _P]),
     'pm_vocos_create': (_I, [_I] * 8 + [ctypes.POINTER(_P)]),
     'pm_vocos_destroy': (_I, [_P]),
     'pm_vocos_load_tensor': (_I, [_P, ctypes.c_char_p, _P, c_int64_p, _I, _P]),
