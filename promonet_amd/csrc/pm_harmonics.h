@@ -173,10 +173,14 @@ __global__ __launch_bounds__(HM_STFT_THREADS) void hm_stft_kernel(
 //   round 0:   log softmax(x[s] + 0.5 (S - s))
 //   masked:    log softmax(x[s]) over lo <= s < hi, -inf elsewhere, with
 //              lo = searchsorted(frequencies, f0 * low), hi = ...(f0 * high)
-// softmax = exp(x - max) / sum in fp32, then logf: what underflows is -inf,
-// as in the reference. A frame whose mask is empty or whose f0 is NaN gets a
-// row of zeros (it contributes nothing to any path) and valid = 0; so does a
-// frame past the row's count. One workgroup a frame.
+// The maximum is exact in fp32; the sum of exp(x - max) and x - max - log(sum)
+// are taken in float64 and rounded once, so an entry is within half an fp32
+// ulp of the exact value (expf, a division and logf composed in fp32 were a
+// whole ulp off at entries near -6, above 4 x the error of the reference's
+// own fp32 pass). Where the reference's fp32 softmax underflows to 0, below
+// 2^-150, the entry is -inf, as its log is. A frame whose mask is empty or
+// whose f0 is NaN gets a row of zeros (it contributes nothing to any path)
+// and valid = 0; so does a frame past the row's count. One workgroup a frame.
 // ---------------------------------------------------------------------------
 #define HM_OBS_THREADS 256
 
@@ -220,9 +224,25 @@ __device__ __forceinline__ float hm_block_reduce(float v, float* scratch,
     return v;
 }
 
+__device__ __forceinline__ double hm_block_sum(double v, double* scratch) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) scratch[wave] = v;
+    __syncthreads();
+    v = scratch[0];
+    for (int w = 1; w < HM_OBS_THREADS / 64; ++w) v += scratch[w];
+    return v;
+}
+
+// log(2^-150): below it exp(x - max) / sum rounds to 0 in fp32
+#define HM_OBS_UNDERFLOW (-103.97207708399179)
+
 __global__ __launch_bounds__(HM_OBS_THREADS) void hm_observation_kernel(
     ObservationArgs a) {
     __shared__ float scratch[HM_OBS_THREADS / 64];
+    __shared__ double wide[HM_OBS_THREADS / 64];
     const int t = threadIdx.x;
     const int f = blockIdx.x % a.T;
     const int row = blockIdx.x / a.T;
@@ -251,17 +271,19 @@ __global__ __launch_bounds__(HM_OBS_THREADS) void hm_observation_kernel(
         top = fmaxf(top, v);
     }
     top = hm_block_reduce(top, scratch, true);
-    float sum = 0.f;
+    double sum = 0.;
     for (int s = lo + t; s < hi; s += HM_OBS_THREADS) {
         const float v = bias ? x[s] + .5f * (float)(S - s) : x[s];
-        sum += expf(v - top);
+        sum += exp((double)v - (double)top);
     }
-    sum = hm_block_reduce(sum, scratch, false);
+    sum = hm_block_sum(sum, wide);
+    const double shift = (double)top + log(sum);
     for (int s = t; s < S; s += HM_OBS_THREADS) {
         float o = ninf;
         if (s >= lo && s < hi) {
             const float v = bias ? x[s] + .5f * (float)(S - s) : x[s];
-            o = logf(expf(v - top) / sum);
+            const double r = (double)v - shift;
+            o = r < HM_OBS_UNDERFLOW ? ninf : (float)r;
         }
         out[s] = o;
     }

@@ -105,7 +105,7 @@ def main():
 
     filtered, t_highpass = wall(
         lambda: oracle.biquad(voice).astype(np.float32))
-    (features, _), t_stft = wall(lambda: oracle.stft(filtered))
+    (features, _, _), t_stft = wall(lambda: oracle.stft(filtered))
     freqs, _ = oracle.frequencies()
     features = features.to(torch.float32)
     (observed, _), t_observation = wall(

@@ -63,29 +63,41 @@ def biquad(x, coefficients=None, dtype=np.float64, clamp=True):
 ###############################################################################
 
 
-def frequencies():
-    """(frequencies above FMIN float32, first bin) (:420-428)"""
+def frequencies(target_rate=SAMPLE_RATE, fmin=FMIN):
+    """(frequencies from fmin up float32, first bin) (:420-428)"""
     result = torch.abs(torch.fft.fftfreq(
-        NUM_FFT, 1 / SAMPLE_RATE)[:NUM_FFT // 2 + 1])
-    minidx = int(torch.searchsorted(result, torch.tensor(FMIN)))
+        NUM_FFT, 1 / target_rate)[:NUM_FFT // 2 + 1])
+    minidx = int(torch.searchsorted(result, torch.tensor(float(fmin))))
     return result[minidx:], minidx
 
 
-def stft(filtered):
-    """float64 magnitudes (frames, states) of high-passed audio (samples,)
-    at SAMPLE_RATE, and per frame sum_n |w_n x_n| (the scale of a
-    transform's rounding error)"""
-    audio = torch.as_tensor(filtered, dtype=torch.float64)[None]
-    frames = audio.shape[-1] // HOPSIZE
-    size = (
-        HOPSIZE * (frames - (audio.shape[-1] // HOPSIZE)) // 2 +
-        (NUM_FFT - HOPSIZE) // 2)
+def stft_geometry(samples, target_rate=SAMPLE_RATE, frames=None):
+    """(hop, reflect padding a side, frames that come out) of `samples`
+    samples at target_rate (:390-396). frames: the reference's `frames`,
+    the frames of the recording at SAMPLE_RATE before it was resampled;
+    default samples // HOPSIZE."""
+    if frames is None:
+        frames = samples // HOPSIZE
+    hop = int(HOPSIZE * target_rate / SAMPLE_RATE)
+    size = hop * (frames - samples // hop) // 2 + (NUM_FFT - HOPSIZE) // 2
+    return hop, size, max(0, 1 + (samples + 2 * size - NUM_FFT) // hop)
+
+
+def stft(filtered, target_rate=SAMPLE_RATE, fmin=FMIN, frames=None,
+         dtype=torch.float64):
+    """Magnitudes (frames, states) in `dtype` of high-passed audio
+    (samples,) at target_rate, per frame sum_n |w_n x_n| (the scale of a
+    direct sum's rounding error) and per frame the L2 norm of w x (the scale
+    of a fast transform's). float64 is the oracle; float32 is the reference's
+    own arithmetic, the yardstick of STFT_GATE."""
+    audio = torch.as_tensor(filtered, dtype=dtype)[None]
+    hop, size, _ = stft_geometry(audio.shape[-1], target_rate, frames)
     audio = torch.nn.functional.pad(audio[None], (size, size), 'reflect')[0]
-    window = torch.hann_window(NUM_FFT, dtype=torch.float64)
+    window = torch.hann_window(NUM_FFT, dtype=dtype)
     result = torch.stft(
         audio,
         NUM_FFT,
-        hop_length=HOPSIZE,
+        hop_length=hop,
         window=window,
         center=False,
         normalized=False,
@@ -93,9 +105,186 @@ def stft(filtered):
         return_complex=True)
     result = torch.view_as_real(result)
     spectrogram = torch.sqrt(result.pow(2).sum(-1) + 1e-6)
-    _, minidx = frequencies()
-    scale = (audio[0].unfold(0, NUM_FFT, HOPSIZE) * window).abs().sum(-1)
-    return spectrogram[0][minidx:].T.contiguous(), scale
+    _, minidx = frequencies(target_rate, fmin)
+    windowed = audio[0].unfold(0, NUM_FFT, hop) * window
+    scale = windowed.abs().sum(-1)
+    return (spectrogram[0][minidx:].T.contiguous(), scale,
+            windowed.pow(2).sum(-1).sqrt())
+
+
+def stft_model(want, l2):
+    """The natural fp32 error of one magnitude: a 4096-point fast transform
+    errs by about 2^-24 log2(4096) ||w x||_2 at every bin, and d sqrt(|X|^2
+    + 1e-6) / d|X| <= 1 passes that on undiminished at most; the result is
+    rounded once more (2^-23 |want| covers the square root and the sum)."""
+    return 2. ** -24 * math.log2(NUM_FFT) * l2[:, None] + 2. ** -23 * want
+
+
+def stft_figure(got, want, l2):
+    """max |got - want| / stft_model: 1 is the natural fp32 error"""
+    got = torch.as_tensor(got).to(torch.float64)
+    return ((got - want).abs() / stft_model(want, l2)).max().item()
+
+
+def _noise(samples, seed, tone=0.):
+    """0.1 randn plus a 0.2 sine of `tone` cycles a sample"""
+    generator = torch.Generator().manual_seed(seed)
+    audio = .1 * torch.randn(samples, generator=generator)
+    return audio + .2 * torch.sin(2 * math.pi * tone * torch.arange(samples))
+
+
+def _ragged(rows):
+    """Rows of different lengths as one batch; 7 where nothing may read"""
+    lengths = [len(row) for row in rows]
+    batch = torch.full((len(rows), max(lengths)), 7.)
+    for row, length, out in zip(rows, lengths, batch):
+        out[:length] = row
+    return batch, lengths
+
+
+_cases = None
+
+
+def stft_cases():
+    """name -> (audio float32 (B, samples), lengths, target_rate, fmin,
+    frame_counts or None): inputs of promonet_amd's `magnitude`, which
+    transforms without the high-pass. Built once and never written to."""
+    global _cases
+    if _cases is not None:
+        return _cases
+    cases = {}
+
+    # an impulse of amplitude a under window value w adds w a at EVERY bin,
+    # with a phase of its own: a wrong twiddle shows at any bin. At both
+    # ends, either side of the padding's mirror and in the middle
+    impulses = torch.zeros(1, 6000)
+    places = [0, 1, 1919, 1920, 1921, 3000, 3001, 5998, 5999]
+    impulses[0, places] = torch.linspace(1 / 8, 3 / 4, len(places))
+    cases['impulses'] = (impulses, [6000], SAMPLE_RATE, FMIN, None)
+
+    # bin0 = 0, 2049 states: DC and Nyquist, and tones on a bin
+    n = torch.arange(5000, dtype=torch.float64)
+    rows = [.5 * torch.cos(2 * math.pi * k0 * n / NUM_FFT)
+            for k0 in (10, 11, 1000, 2047)]
+    rows += [torch.full_like(n, .25), .25 * (-1.) ** n]
+    cases['cosines'] = (
+        torch.stack(rows).to(torch.float32), [5000] * 6, SAMPLE_RATE, 0.,
+        None)
+
+    # the shortest admissible row: a single frame reflects at both ends
+    cases['shortest'] = (
+        _noise(1921, 2)[None], [1921], SAMPLE_RATE, FMIN, None)
+
+    cases['ragged'] = _ragged([
+        _noise(6000, 3, .011), _noise(1921, 4, .03), _noise(4100, 5, .2)
+    ]) + (SAMPLE_RATE, FMIN, None)
+
+    # hop 185, bin0 13, and frame counts that move the padding: +0, -4, +3
+    # frames against len // hop give 1920, 1550 and 2197 a side
+    batch, lengths = _ragged([
+        _noise(6000, 6, .017), _noise(5990, 7, .09), _noise(6011, 8, .31)])
+    counts = [length // 185 + extra
+              for length, extra in zip(lengths, (0, -4, 3))]
+    cases['rate16k'] = (batch, lengths, 16000, FMIN, counts)
+
+    # the high-passed synthetic voice and a shorter, flat one
+    rows = [
+        torch.from_numpy(biquad(synthetic_voice(*args)[0]).astype(np.float32))
+        for args in ((), (9000, 0., 1))]
+    cases['voice'] = _ragged(rows) + (SAMPLE_RATE, FMIN, None)
+
+    _cases = cases
+    return cases
+
+
+def stft_case_rows(name):
+    """Per row of a case: (audio (samples,), target_rate, fmin, frames)"""
+    audio, lengths, target_rate, fmin, counts = stft_cases()[name]
+    hop = int(HOPSIZE * target_rate / SAMPLE_RATE)
+    return [
+        (audio[row, :length], target_rate, fmin,
+         length // hop if counts is None else counts[row])
+        for row, length in enumerate(lengths)]
+
+
+_wanted = {}
+
+
+def stft_case_oracle(name):
+    """Per row of a case: (float64 magnitudes, L1 scale, L2 scale), once"""
+    if name not in _wanted:
+        _wanted[name] = [stft(*row) for row in stft_case_rows(name)]
+    return _wanted[name]
+
+
+def stft_fp32_figure(name):
+    """The stft_figure of the reference's own fp32 arithmetic (torch.stft in
+    float32, float32 window, same padding) on a case"""
+    worst = 0.
+    for row, (want, _, l2) in zip(
+            stft_case_rows(name), stft_case_oracle(name)):
+        got, _, _ = stft(*row, dtype=torch.float32)
+        worst = max(worst, stft_figure(got, want, l2))
+    return worst
+
+
+# (gate, figure): figure is the largest stft_fp32_figure over stft_cases();
+# the gate of every device STFT test is 4 x it. One gate for all cases: a case
+# where fp32 happens to be nearly exact gets no gate that rounding noise trips.
+# torch.stft runs MKL's transform on the CPU, and MKL picks its code by the
+# processor: the same inputs gave 2.29 (AVX-512), 3.47 (AVX2) and 5.03 (the
+# path every x86-64 processor can take). The recorded figure is the last one,
+# the one that MKL_CBWR=COMPATIBLE reproduces on any machine
+# (test_cpu_harmonics.py holds it to these digits in a child process).
+STFT_FP32_FIGURE = 5.03         # the voice's first row
+STFT_GATE = (4 * STFT_FP32_FIGURE, STFT_FP32_FIGURE)
+
+
+###############################################################################
+# The high-pass on a grid: exact in fp32, so held bit for bit
+###############################################################################
+
+
+# (b0, b1, b2, a1, a2): poles on the unit circle, everything stays an integer
+GRID_COEFFICIENTS = ((1, -2, 1, -1, 1), (1, -2, 1, 1, 1))
+GRID_SAMPLES = 6203         # 3 chunks of 2048 and 59 samples: no whole quad
+GRID_LENGTHS = (1, 2, 3, 5, 2047, 2048, 2049, 4095, 4096, 4097, 6150, 0, -3,
+                GRID_SAMPLES + 5)
+GRID_SCALE = 2. ** -12      # |y| stays below 1
+GRID_CLAMPING_SCALE = 2. ** -9
+
+
+def grid_inputs(seed=2):
+    """Integers in [-8, 8], (rows, GRID_SAMPLES) int64: times GRID_SCALE the
+    input of the exact high-pass tests. (The seed is one whose outputs pass
+    512 units under both coefficient sets, so that GRID_CLAMPING_SCALE
+    clamps; test_cpu_harmonics.py asserts it.)"""
+    generator = torch.Generator().manual_seed(seed)
+    return torch.randint(
+        -8, 9, (len(GRID_LENGTHS), GRID_SAMPLES), generator=generator).numpy()
+
+
+def biquad_grid(X, coefficients, scale=GRID_SCALE, clamp=False,
+                return_peak=False):
+    """biquad() of a 1-D array of integers X times `scale` under integer
+    coefficients, in Python integers: exact, and equal to any fp32
+    evaluation whose intermediates stay below 2^24 grid units. float64
+    (len,); with return_peak also the largest sum of the magnitudes of one
+    sample's five terms, in grid units: it bounds every intermediate of
+    every order of summation."""
+    b0, b1, b2, a1, a2 = (int(c) for c in coefficients)
+    Y = []
+    x1 = x2 = y1 = y2 = peak = 0
+    for x0 in (int(item) for item in X):
+        y0 = b0 * x0 + b1 * x1 + b2 * x2 - a1 * y1 - a2 * y2
+        peak = max(peak, abs(b0 * x0) + abs(b1 * x1) + abs(b2 * x2) +
+                   abs(a1 * y1) + abs(a2 * y2))
+        Y.append(y0)
+        x2, x1, y2, y1 = x1, x0, y1, y0
+    y = np.array(Y, dtype=np.float64) * scale
+    if clamp:
+        y = np.clip(y, -1, 1)
+    return (y, peak) if return_peak else y
 
 
 ###############################################################################
@@ -269,7 +458,7 @@ def from_audio(audio, pitch=None, max_harmonics=3):
     the float64 high-pass and STFT rounded to fp32 features, the fp32
     observation and the decode"""
     filtered = biquad(np.asarray(audio, dtype=np.float32)).astype(np.float32)
-    features, _ = stft(filtered)
+    features, _, _ = stft(filtered)
     freqs, _ = frequencies()
     return decode(features.to(torch.float32), freqs, pitch, max_harmonics)
 

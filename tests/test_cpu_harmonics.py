@@ -2,6 +2,11 @@
 promonet_amd.viterbi and the surface of the new modules. No GPU."""
 import ctypes
 import inspect
+import json
+import os
+import subprocess
+import sys
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -150,6 +155,134 @@ def test_oracle_biquad_and_peaks():
         x = generator.randint(0, 4, 50).astype(np.float32)
         assert oracle.find_peaks(x).tolist() == \
             scipy_signal.find_peaks(x)[0].tolist()
+
+
+def test_stft_gate_is_four_times_the_fp32_figure():
+    """MKL chooses its transform by the processor, so the figure is taken in
+    a child process on the code path that every processor has"""
+    script = (
+        'import json, sys\n'
+        f'sys.path.insert(0, {str(Path(__file__).parent)!r})\n'
+        'import harmonics_oracle as oracle\n'
+        'print(json.dumps({name: oracle.stft_fp32_figure(name) '
+        'for name in oracle.stft_cases()}))\n')
+    environment = dict(
+        os.environ, MKL_CBWR='COMPATIBLE', OMP_NUM_THREADS='1',
+        MKL_NUM_THREADS='1')
+    output = subprocess.run(
+        [sys.executable, '-c', script], env=environment, check=True,
+        capture_output=True, text=True).stdout
+    figures = json.loads(output.splitlines()[-1])
+    print('fp32 torch.stft over the natural error model: ' + ', '.join(
+        f'{name} {figure:.2f}' for name, figure in figures.items()))
+    assert list(figures) == [
+        'impulses', 'cosines', 'shortest', 'ragged', 'rate16k', 'voice']
+    assert round(max(figures.values()), 2) == oracle.STFT_GATE[1] == 5.03
+    assert oracle.STFT_GATE[0] == 4 * oracle.STFT_GATE[1]
+    # whatever path this process takes, its figure is within the gate
+    here = max(oracle.stft_fp32_figure(name) for name in figures)
+    print(f'in this process: {here:.2f}')
+    assert 0 < here < oracle.STFT_GATE[0]
+
+
+def test_stft_cases_have_the_geometry_they_are_named_for():
+    cases = oracle.stft_cases()
+    for name, (audio, lengths, target_rate, fmin, counts) in cases.items():
+        assert audio.dtype == torch.float32 and audio.shape[0] == len(lengths)
+        assert audio.shape[1] == max(lengths)
+        for row, length in zip(oracle.stft_case_rows(name), lengths):
+            _, size, count = oracle.stft_geometry(length, row[1], row[3])
+            assert 0 <= size < length and count >= 1
+    assert oracle.frequencies(22050, 0.)[1] == 0
+    assert oracle.stft_case_oracle('cosines')[0][0].shape == (19, 2049)
+    assert oracle.stft_geometry(1921) == (256, 1920, 7)
+    audio, lengths, target_rate, fmin, counts = cases['rate16k']
+    assert oracle.frequencies(16000, fmin)[1] == 13
+    geometry = [oracle.stft_geometry(length, 16000, count)
+                for length, count in zip(lengths, counts)]
+    assert [item[:2] for item in geometry] == [
+        (185, 1920), (185, 1550), (185, 2197)]
+    assert all(item[1] < length for item, length in zip(geometry, lengths))
+    assert [len(want) for want, _, _ in oracle.stft_case_oracle('rate16k')] \
+        == [item[2] for item in geometry]
+    # a tone on bin k0 peaks there at amplitude x sum(w) / 2 = 0.5 x 1024
+    for row, k0 in enumerate((10, 11, 1000, 2047)):
+        want = oracle.stft_case_oracle('cosines')[row][0][9]
+        assert int(want.argmax()) == k0 and abs(want[k0] - 512.) < .01
+    dc, nyquist = (oracle.stft_case_oracle('cosines')[row][0][9]
+                   for row in (4, 5))
+    assert abs(dc[0] - 512.) < .01 and abs(nyquist[2048] - 512.) < .01
+
+
+def test_stft_gate_is_tighter_than_the_direct_sum_bound_at_every_bin():
+    """4 x 5.03 (12 L2 + 2 |X|) against 4098 L1 + 4 |X| (units of 2^-24):
+    L2 <= L1 and |X| <= L1 + 1e-3"""
+    for want, scale, l2 in oracle.stft_case_oracle('voice'):
+        before = (4096 + 2) * 2. ** -24 * scale[:, None] + 2. ** -22 * want
+        now = oracle.STFT_GATE[0] * oracle.stft_model(want, l2)
+        assert (now < before).all()
+        print(f'direct-sum bound over the gated model: median '
+              f'{(before / now).median().item():.0f}')
+
+
+def stft_before(filtered):
+    """oracle.stft as it stood before it took a geometry"""
+    audio = torch.as_tensor(filtered, dtype=torch.float64)[None]
+    frames = audio.shape[-1] // 256
+    size = 256 * (frames - (audio.shape[-1] // 256)) // 2 + (4096 - 256) // 2
+    audio = torch.nn.functional.pad(audio[None], (size, size), 'reflect')[0]
+    window = torch.hann_window(4096, dtype=torch.float64)
+    result = torch.view_as_real(torch.stft(
+        audio, 4096, hop_length=256, window=window, center=False,
+        normalized=False, onesided=True, return_complex=True))
+    spectrogram = torch.sqrt(result.pow(2).sum(-1) + 1e-6)
+    scale = (audio[0].unfold(0, 4096, 256) * window).abs().sum(-1)
+    return spectrogram[0][10:].T.contiguous(), scale
+
+
+def test_stft_defaults_are_unchanged():
+    audio, lengths = oracle.stft_cases()['voice'][:2]
+    for row, length in enumerate(lengths):
+        want, scale, l2 = oracle.stft(audio[row, :length])
+        before, before_scale = stft_before(audio[row, :length])
+        assert torch.equal(want, before) and torch.equal(scale, before_scale)
+        assert want.dtype == torch.float64 and l2.shape == scale.shape
+        assert (l2 <= scale).all() and (l2 > 0).all()
+        assert torch.equal(want, oracle.stft_case_oracle('voice')[row][0])
+
+
+def test_biquad_grid_is_the_float64_recursion_and_fits_fp32():
+    X = oracle.grid_inputs()
+    assert X.shape == (len(oracle.GRID_LENGTHS), oracle.GRID_SAMPLES)
+    assert X.min() == -8 and X.max() == 8
+    for coefficients in oracle.GRID_COEFFICIENTS:
+        above = below_again = total = 0
+        for row, length in zip(X, oracle.GRID_LENGTHS):
+            row = row[:max(0, min(length, oracle.GRID_SAMPLES))]
+            y, peak = oracle.biquad_grid(row, coefficients, return_peak=True)
+            assert peak < 2 ** 24
+            assert np.array_equal(y, oracle.biquad(
+                row * oracle.GRID_SCALE, coefficients, clamp=False))
+            assert np.array_equal(y, oracle.biquad(
+                (row * oracle.GRID_SCALE).astype(np.float32), coefficients,
+                dtype=np.float32, clamp=False))
+            if len(y):
+                assert np.abs(y).max() < 1
+            free = oracle.biquad_grid(
+                row, coefficients, oracle.GRID_CLAMPING_SCALE)
+            clamped = oracle.biquad_grid(
+                row, coefficients, oracle.GRID_CLAMPING_SCALE, clamp=True)
+            assert np.array_equal(clamped, oracle.biquad(
+                row * oracle.GRID_CLAMPING_SCALE, coefficients))
+            assert np.array_equal(clamped, np.clip(free, -1, 1))
+            over = np.abs(free) > 1
+            total += len(free)
+            above += int(over.sum())
+            if over.any():
+                below_again += int((~over[np.argmax(over):]).sum())
+        print(f'{coefficients}: {above} of {total} samples clamp, '
+              f'{below_again} below 1 after the first that does')
+        assert above >= .01 * total and below_again >= .01 * total
 
 
 def test_module_surface():
