@@ -835,6 +835,56 @@ int pm_disc_spec_backward(int mode, const float* x, const float* window,
                           int win_length, int pad, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- FARGAN discriminator conv stacks: promonet/model/discriminator.py ----
+ * One layer of DiscriminatorMagFree (:320-389), forward and backward:
+ *   y = act(conv3x3(cat(x, sin, cos)) + bias)
+ * with stride 1, dilation (dilation, 1) and padding (dilation, 1), the two
+ * channels of FrequencyPositionalEmbedding (:381-389) read from `table`
+ * (bins, 2) = sin, cos of 2 pi f / bins and zero outside the map, as the
+ * conv's own padding makes them. fp32 throughout; the layers with 16 output
+ * channels run on the fp32-input MFMA.
+ * MEMORY ORDER: a map of 16 channels is channels_last, in memory (batch, bins,
+ * frames, 16); a map of one channel is (batch, bins, frames). x has `channels`
+ * (1 or 16) channels, y and upstream `out_channels` (16 or 1; not 1 on both
+ * sides); weight is torch's (out_channels, channels + 2, 3, 3), bias
+ * (out_channels).
+ * Backward: from upstream, the saved y and the saved x, with gz = upstream *
+ * act'(y) (relu: y > 0; sigmoid: y (1 - y)): grad_x in the layout of x (NULL
+ * skips it), grad_weight and grad_bias (both NULL skips them). The two sums
+ * over all pixels go through per-workgroup partials in the workspace, whose
+ * count depends on the sizes alone, added in a fixed order: no float atomics,
+ * the same bits on every run. All asynchronous, no allocation, capturable.
+ * channels not 1 or 16, out_channels not 1 or 16, dilation not 1, 2, 4, 8 or
+ * 16, batch, bins or frames below 1, an unknown activation, too many pixels
+ * for one launch or a workspace that is too small are refused before any
+ * device work; the workspace query returns 0 for such sizes.
+ * pm_fdisc_weight_norm_*: w = g v / |v| with the norm per output channel over
+ * its `fan` = (channels + 2) * 9 values (torch._weight_norm, dim 0), and the
+ * adjoint from grad_w to (grad_g, grad_v).                                  */
+#define PM_FDISC_NONE 0
+#define PM_FDISC_RELU 1
+#define PM_FDISC_SIGMOID 2
+size_t pm_fdisc_workspace_bytes(int batch, int channels, int out_channels,
+                                int bins, int frames);
+int pm_fdisc_conv_forward(const float* x, const float* weight,
+                          const float* bias, const float* table, float* y,
+                          int batch, int channels, int out_channels, int bins,
+                          int frames, int dilation, int activation,
+                          void* stream);
+int pm_fdisc_conv_backward(const float* upstream, const float* y,
+                           const float* x, const float* weight,
+                           const float* table, float* grad_x,
+                           float* grad_weight, float* grad_bias, int batch,
+                           int channels, int out_channels, int bins,
+                           int frames, int dilation, int activation,
+                           void* workspace, size_t workspace_bytes,
+                           void* stream);
+int pm_fdisc_weight_norm_forward(const float* g, const float* v, float* w,
+                                 int out_channels, int fan, void* stream);
+int pm_fdisc_weight_norm_backward(const float* grad_w, const float* g,
+                                  const float* v, float* grad_g, float* grad_v,
+                                  int out_channels, int fan, void* stream);
+
 /* ---- adversarial losses: promonet/train/loss.py:11-53 ---------------------
  * feature_matching, discriminator and generator are each a sum of means over
  * a list of tensors of unrelated sizes. pm_multi_mean takes the whole list:

@@ -22,6 +22,8 @@ MAX_STAGES, MAX_RESBLOCKS, MAX_DILATIONS = 8, 4, 4
 SPARSE_METHODS = {None: 0, 'percentile': 1, 'constant': 2, 'topk': 3}
 # the modes of pm_disc_spec_* (PM_DISC_SPEC_*, promonet_hip.h)
 DISC_SPEC_R, DISC_SPEC_CMB, DISC_SPEC_DB = range(3)
+# the activations of pm_fdisc_conv_* (PM_FDISC_*, promonet_hip.h)
+FDISC_ACTIVATIONS = {'none': 0, 'relu': 1, 'sigmoid': 2}
 # the ops of pm_multi_mean (PM_ADV_*, promonet_hip.h)
 (ADV_ABS_DIFF, ADV_SQ_ONE_MINUS, ADV_SQ, ADV_HINGE_ONE_MINUS,
  ADV_HINGE_ONE_PLUS) = range(5)
@@ -156,6 +158,11 @@ SIGNATURES = {
     'pm_disc_spec_workspace_bytes': (_S, [_I] * 8),
     'pm_disc_spec_forward': (_I, [_I] + [_P] * 5 + [_I] * 6 + [_P, _S, _P]),
     'pm_disc_spec_backward': (_I, [_I] + [_P] * 8 + [_I] * 7 + [_P, _S, _P]),
+    'pm_fdisc_workspace_bytes': (_S, [_I] * 5),
+    'pm_fdisc_conv_forward': (_I, [_P] * 5 + [_I] * 7 + [_P]),
+    'pm_fdisc_conv_backward': (_I, [_P] * 8 + [_I] * 7 + [_P, _S, _P]),
+    'pm_fdisc_weight_norm_forward': (_I, [_P] * 3 + [_I, _I, _P]),
+    'pm_fdisc_weight_norm_backward': (_I, [_P] * 5 + [_I, _I, _P]),
     'pm_multi_mean_chunk': (_I, []),
     'pm_multi_mean_workspace_bytes': (_S, [_P, _I]),
     'pm_multi_mean': (_I, [_P] * 5 + [_I, _P, _P, _S, _P]),

@@ -1,12 +1,18 @@
 """The spectrograms at the entrance of the spectral discriminators on the HIP
-kernels (pm_disc_spec.h), differentiable in the audio.
+kernels (pm_disc_spec.h), differentiable in the audio, and the conv stacks of
+the FARGAN discriminator (pm_fdisc.h), differentiable in the maps and the
+parameters.
 
 API of the three `spectrogram` methods of `promonet.model.discriminator`
 (promonet/model/discriminator.py): DiscriminatorR (:129-143),
-DiscriminatorCMB (:175-192) and SpecDiscriminatorBase (:278-299). The conv
-stacks behind them stay on torch. Neither direction syncs with the host, and
-both capture into a graph on one stream.
+DiscriminatorCMB (:175-192) and SpecDiscriminatorBase (:278-299), and of
+DiscriminatorMagFree (:320-389). The conv stacks of DiscriminatorMagFree are
+in (`frequency_conv`, `weight_norm`, `DiscriminatorMagFree`); those of
+DiscriminatorP / S / R / CMB stay on torch. Neither direction syncs with the
+host, and both capture into a graph on one stream.
 """
+import math
+
 import torch
 
 from promonet_amd import _lib, config
@@ -185,6 +191,341 @@ def spectrogram_decibel(audio, resolution):
 
 
 ###############################################################################
+# The conv stacks of DiscriminatorMagFree
+###############################################################################
+
+DILATIONS = (1, 2, 4, 8, 16)
+RESOLUTIONS = (64, 128, 256, 512, 1024, 2048)
+_TABLES = {}
+
+
+def _embedding_table(device, bins):
+    """(bins, 2) fp32 = sin, cos of FrequencyPositionalEmbedding (:381-389),
+    by its own expression on the device; cached per device and size"""
+    key = (str(device), bins)
+    if key not in _TABLES:
+        args = torch.arange(
+            0, bins, dtype=torch.float32, device=device) * torch.pi * 2 / bins
+        _TABLES[key] = torch.stack(
+            (torch.sin(args), torch.cos(args)), dim=1).contiguous()
+    return _TABLES[key]
+
+
+def _map_order(tensor):
+    """The memory order of the kernels: 16 channels are channels_last, in
+    memory (B, F, T, 16); one channel is (B, F, T) either way"""
+    if tensor.shape[1] == 1:
+        return tensor.contiguous()
+    return tensor.contiguous(memory_format=torch.channels_last)
+
+
+def _empty_map(batch, channels, bins, frames, device):
+    return torch.empty(
+        (batch, channels, bins, frames), device=device, dtype=torch.float32,
+        memory_format=torch.channels_last if channels > 1
+        else torch.contiguous_format)
+
+
+def _layer_sizes(x, weight, bias, dilation, activation):
+    """(B, C, O, F, T, d, act) of a checked call; ValueError otherwise"""
+    for name, tensor in (('x', x), ('weight', weight), ('bias', bias)):
+        if not isinstance(tensor, torch.Tensor) or \
+                not tensor.is_floating_point():
+            raise ValueError(f'{name} must be a float tensor')
+    if x.ndim != 4 or x.shape[1] not in (1, 16) or not x.numel():
+        raise ValueError(
+            f'x {tuple(x.shape)}: must be (B, C, F, T) with C 1 or 16 and no '
+            'empty axis')
+    batch, channels, bins, frames = x.shape
+    if weight.ndim != 4 or weight.shape[0] not in (1, 16) or \
+            tuple(weight.shape[1:]) != (channels + 2, 3, 3):
+        raise ValueError(
+            f'weight {tuple(weight.shape)}: must be (O, {channels + 2}, 3, 3) '
+            'with O 1 or 16')
+    out_channels = weight.shape[0]
+    if channels == 1 and out_channels == 1:
+        raise ValueError('no layer has one channel on both sides')
+    if tuple(bias.shape) != (out_channels,):
+        raise ValueError(
+            f'bias {tuple(bias.shape)}: must be ({out_channels},)')
+    if isinstance(dilation, (tuple, list)):
+        if len(dilation) != 2 or dilation[1] != 1:
+            raise ValueError(f'dilation {dilation!r}: must be (d, 1)')
+        dilation = dilation[0]
+    if dilation not in DILATIONS:
+        raise ValueError(f'dilation {dilation!r}: must be one of {DILATIONS}')
+    if activation not in _lib.FDISC_ACTIVATIONS:
+        raise ValueError(
+            f'activation {activation!r}: must be one of '
+            f'{tuple(_lib.FDISC_ACTIVATIONS)}')
+    return (batch, channels, out_channels, bins, frames, int(dilation),
+            _lib.FDISC_ACTIVATIONS[activation])
+
+
+class _FrequencyConv(torch.autograd.Function):
+    """backward: gx, gW and gb from the upstream gradient, the saved output
+    and the saved input (pm_fdisc_conv_backward)"""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, x, weight, bias, table, sizes):
+        lib = _lib.lib()
+        batch, channels, out_channels, bins, frames = sizes[:5]
+        x, weight, bias = _map_order(x), weight.contiguous(), bias.contiguous()
+        y = _empty_map(batch, out_channels, bins, frames, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.pm_fdisc_conv_forward(
+                x.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
+                _lib.ptr(table), y.data_ptr(), *sizes, _lib.stream()))
+        ctx.save_for_backward(x, weight, table, y)
+        ctx.sizes = sizes
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, grad):
+        lib = _lib.lib()
+        x, weight, table, y = ctx.saved_tensors
+        sizes = ctx.sizes
+        grad = _map_order(grad.to(torch.float32))
+        need_x, need_weight, need_bias = ctx.needs_input_grad[:3]
+        grad_x = torch.empty_like(x) if need_x else None
+        grad_weight = grad_bias = workspace = None
+        with torch.cuda.device(x.device):
+            if need_weight or need_bias:
+                grad_weight = torch.empty_like(weight)
+                grad_bias = torch.empty(sizes[2], device=x.device)
+                workspace = torch.empty(
+                    lib.pm_fdisc_workspace_bytes(*sizes[:5]),
+                    dtype=torch.uint8, device=x.device)
+            _lib.check(lib.pm_fdisc_conv_backward(
+                grad.data_ptr(), y.data_ptr(), x.data_ptr(), _lib.ptr(weight),
+                _lib.ptr(table),
+                None if grad_x is None else grad_x.data_ptr(),
+                _lib.ptr(grad_weight), _lib.ptr(grad_bias), *sizes,
+                None if workspace is None else workspace.data_ptr(),
+                0 if workspace is None else workspace.numel(), _lib.stream()))
+        return (grad_x, grad_weight if need_weight else None,
+                grad_bias if need_bias else None, None, None)
+
+
+def frequency_conv(x, weight, bias, dilation=1, activation='relu', table=None):
+    """One layer of DiscriminatorMagFree (:343-369) without its weight norm:
+    act(conv2d(cat(x, sin, cos), weight, bias, stride 1, dilation (d, 1),
+    padding (d, 1))), sin and cos of 2 pi f / F being the two channels of
+    FrequencyPositionalEmbedding. x (B, C, F, T) on the device with C 1 or 16,
+    weight (O, C + 2, 3, 3) with O 16 or 1, bias (O); activation 'relu',
+    'sigmoid' or 'none'. Returns (B, O, F, T) fp32; with 16 channels it is
+    channels_last in memory, as is the gradient in x. Differentiable in x,
+    weight and bias. Other float dtypes are cast to fp32 and their gradients
+    return in their dtype. `table` (F, 2) replaces sin and cos (the tests'
+    integer embedding)."""
+    sizes = _layer_sizes(x, weight, bias, dilation, activation)
+    if table is not None and tuple(table.shape) != (sizes[3], 2):
+        raise ValueError(f'table {tuple(table.shape)}: must be (F, 2)')
+    _lib.require_gpu(x)
+    if table is None:
+        table = _embedding_table(x.device, sizes[3])
+    return _FrequencyConv.apply(
+        x.to(torch.float32), weight.to(torch.float32),
+        bias.to(torch.float32), table, sizes)
+
+
+class _WeightNorm(torch.autograd.Function):
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, g, v):
+        lib = _lib.lib()
+        g, v = g.contiguous(), v.contiguous()
+        w = torch.empty_like(v)
+        with torch.cuda.device(v.device):
+            _lib.check(lib.pm_fdisc_weight_norm_forward(
+                _lib.ptr(g), _lib.ptr(v), _lib.ptr(w), v.shape[0],
+                v[0].numel(), _lib.stream()))
+        ctx.save_for_backward(g, v)
+        return w
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, grad):
+        lib = _lib.lib()
+        g, v = ctx.saved_tensors
+        grad = grad.to(torch.float32).contiguous()
+        grad_g, grad_v = torch.empty_like(g), torch.empty_like(v)
+        with torch.cuda.device(v.device):
+            _lib.check(lib.pm_fdisc_weight_norm_backward(
+                _lib.ptr(grad), _lib.ptr(g), _lib.ptr(v), _lib.ptr(grad_g),
+                _lib.ptr(grad_v), v.shape[0], v[0].numel(), _lib.stream()))
+        return grad_g, grad_v
+
+
+def weight_norm(g, v):
+    """torch._weight_norm(v, g, 0): w = g v / |v| with the norm of each output
+    channel over its other axes. g (O, 1, ...) or (O), v (O, ...) on the
+    device -> w like v, fp32, differentiable in both."""
+    for name, tensor in (('g', g), ('v', v)):
+        if not isinstance(tensor, torch.Tensor) or \
+                not tensor.is_floating_point():
+            raise ValueError(f'{name} must be a float tensor')
+    if v.ndim < 2 or not v.numel() or g.numel() != v.shape[0] or \
+            g.shape[:1] != v.shape[:1]:
+        raise ValueError(
+            f'g {tuple(g.shape)}, v {tuple(v.shape)}: one g per output '
+            'channel of v')
+    _lib.require_gpu(v)
+    return _WeightNorm.apply(g.to(torch.float32), v.to(torch.float32))
+
+
+def magfree_plan(n_fft):
+    """The six layers of DiscriminatorMagFree at a resolution, as (frequency
+    stride, frequency dilation, channels, out_channels), restating what
+    create_3x3_conv_plan(6, s, s, 0, 0) with s = log2(n_fft / 64) (:397-487,
+    `configs` :302-319) and the channel rule of :342-357 give: the first s
+    layers halve the frequency axis and double the channels (16 at first, 256
+    at most), every other layer has stride 1, no layer is dilated, nothing
+    happens on the time axis, and the last layer has one output channel."""
+    if n_fft not in RESOLUTIONS:
+        raise ValueError(f'n_fft {n_fft!r}: must be one of {RESOLUTIONS}')
+    halvings = int(math.log2(n_fft // 64))
+    layers, channels, out_channels = [], 1, 16
+    for index in range(5):
+        stride = 2 if index < halvings else 1
+        layers.append((stride, 1, channels, out_channels))
+        channels, out_channels = out_channels, min(stride * out_channels, 256)
+    return layers + [(1, 1, channels, 1)]
+
+
+class FrequencyPositionalEmbedding(torch.nn.Identity):
+    """Slot 0 of a layer, as in the reference: no parameters. The kernels
+    add the embedding themselves."""
+
+
+class _NormedConv(torch.nn.Module):
+    """Slot 1 of a layer: the parameters of a weight-normed Conv2d(channels +
+    2, out_channels, 3), under the names torch.nn.utils.weight_norm gives"""
+
+    def __init__(self, channels, out_channels, dilation):
+        super().__init__()
+        conv = torch.nn.Conv2d(channels + 2, out_channels, 3)
+        weight = conv.weight.detach()
+        # (in the order weight_norm leaves them: bias, weight_g, weight_v)
+        self.bias = torch.nn.Parameter(conv.bias.detach().clone())
+        self.weight_g = torch.nn.Parameter(
+            weight.flatten(1).norm(dim=1).reshape(-1, 1, 1, 1))
+        self.weight_v = torch.nn.Parameter(weight.clone())
+        self.dilation = dilation
+
+
+class DiscriminatorMagFree(torch.nn.Module):
+    """promonet.model.discriminator.DiscriminatorMagFree (:320-389) on the
+    device: the decibel spectrogram, then six weight-normed 3x3 convs over
+    (frequency, time) with the frequency embedding, 1 -> 16 -> ... -> 16 -> 1,
+    ReLU after five and a sigmoid after the last. The state_dict has the
+    reference's keys and shapes. `filterbank` is carried for the checkpoint
+    only (the reference's forward never reads it) and starts as zeros.
+
+    Only the resolution whose stack has that form is accepted, n_fft = 64: at
+    128 ... 2048 the reference's layers halve the frequency axis and widen to
+    32 ... 256 channels (magfree_plan), which the kernels do not compute, and
+    a missing kernel is an error, not a reason to run torch's."""
+
+    def __init__(self, resolution):
+        super().__init__()
+        self.resolution = tuple(int(v) for v in resolution)
+        plan = magfree_plan(self.resolution[0])
+        if any(stride != 1 or out_channels > 16
+               for stride, _, _, out_channels in plan):
+            raise ValueError(
+                f'n_fft {self.resolution[0]}: the layers of this resolution '
+                'have a frequency stride of 2 and up to 256 channels, which '
+                'the kernels do not compute (n_fft 64 alone is all stride 1 '
+                'and 16 channels)')
+        layers = []
+        for stride, dilation, channels, out_channels in plan:
+            last = out_channels == 1
+            layers.append(torch.nn.Sequential(
+                FrequencyPositionalEmbedding(),
+                _NormedConv(channels, out_channels, dilation),
+                torch.nn.Sigmoid() if last else torch.nn.ReLU()))
+        self.layers = torch.nn.ModuleList(layers)
+        bins = self.resolution[0] // 2 + 1
+        self.filterbank = torch.nn.Parameter(
+            torch.zeros(bins, bins), requires_grad=False)
+
+    def stack(self, x):
+        """The six layers on x (B, 1, F, T): (logits (B, 1, F, T), [five
+        maps])"""
+        maps = []
+        for layer in self.layers:
+            conv = layer[1]
+            x = frequency_conv(
+                x, weight_norm(conv.weight_g, conv.weight_v), conv.bias,
+                conv.dilation,
+                'sigmoid' if isinstance(layer[2], torch.nn.Sigmoid)
+                else 'relu')
+            maps.append(x)
+        return maps[-1], maps[:-1]
+
+    def forward(self, audio):
+        """audio (B, 1, T) -> (logits flattened to (B, F frames), the five
+        feature maps), as SpecDiscriminatorBase.forward (:259-266)"""
+        logits, maps = self.stack(
+            spectrogram_decibel(audio, self.resolution).unsqueeze(1))
+        return torch.flatten(logits, 1, -1), maps
+
+
+def _stack_layers(self):
+    """[(conv, dilation, activation)] where every layer of a reference-style
+    module has the form the kernels compute, or None"""
+    layers, channels = [], 1
+    for layer in getattr(self, 'layers', ()):
+        if not isinstance(layer, torch.nn.Sequential) or len(layer) != 3:
+            return None
+        embedding, conv, activation = layer
+        if type(embedding).__name__ != 'FrequencyPositionalEmbedding' or \
+                not isinstance(conv, torch.nn.Conv2d) or \
+                not isinstance(getattr(conv, 'weight_g', None), torch.Tensor) \
+                or not isinstance(getattr(conv, 'weight_v', None),
+                                  torch.Tensor) or conv.bias is None:
+            return None
+        if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or \
+                conv.groups != 1 or conv.padding_mode != 'zeros' or \
+                conv.dilation[1] != 1 or conv.dilation[0] not in DILATIONS or \
+                tuple(conv.padding) != (conv.dilation[0], 1) or \
+                conv.in_channels != channels + 2 or \
+                conv.out_channels not in (1, 16) or \
+                (channels == 1 and conv.out_channels == 1):
+            return None
+        if isinstance(activation, torch.nn.ReLU):
+            name = 'relu'
+        elif isinstance(activation, torch.nn.Sigmoid):
+            name = 'sigmoid'
+        else:
+            return None
+        layers.append((conv, conv.dilation[0], name))
+        channels = conv.out_channels
+    return layers or None
+
+
+def _wrap_forward(original):
+    def forward(self, x):
+        layers = _stack_layers(self) if x.is_cuda else None
+        if layers is None:
+            return original(self, x)
+        x = spectrogram_decibel(x, self.resolution).unsqueeze(1)
+        output = []
+        for conv, dilation, activation in layers:
+            x = frequency_conv(
+                x, weight_norm(conv.weight_g, conv.weight_v), conv.bias,
+                dilation, activation)
+            output.append(x)
+        return torch.flatten(output[-1], 1, -1), output[:-1]
+    forward.original = original
+    return forward
+
+
+###############################################################################
 # The wrappers promonet_amd.patch installs
 ###############################################################################
 
@@ -200,8 +541,11 @@ def _wrap(original, on_device):
 
 def patch_module(module):
     """Replace the three spectrogram methods of a `model.discriminator`
-    module, where it has them; a tensor that is not on a GPU goes to the
-    original method."""
+    module, where it has them, and the `forward` of SpecDiscriminatorBase,
+    where it has one; a tensor that is not on a GPU goes to the original
+    method, and so does a module whose layers are not weight-normed 3x3 convs
+    of stride 1 with a frequency dilation of 1 ... 16 under the frequency
+    embedding, each followed by ReLU or Sigmoid."""
     wrappers = {
         'DiscriminatorR': lambda self, x: spectrogram_resolution(
             x, self.resolution),
@@ -214,3 +558,7 @@ def patch_module(module):
         if cls is None or hasattr(cls.spectrogram, 'original'):
             continue
         cls.spectrogram = _wrap(cls.spectrogram, on_device)
+    base = getattr(module, 'SpecDiscriminatorBase', None)
+    forward = getattr(base, 'forward', None)
+    if forward is not None and not hasattr(forward, 'original'):
+        base.forward = _wrap_forward(forward)

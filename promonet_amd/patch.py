@@ -8,7 +8,11 @@ libpromonet_hip.so, and,
 where the target has them, `promonet.model.Vocos` / `MelGenerator`,
 `promonet.baseline.mels.*` and the `spectrogram` methods of
 `promonet.model.discriminator` (DiscriminatorR, DiscriminatorCMB,
-SpecDiscriminatorBase; a CPU tensor still takes the target's own method).
+SpecDiscriminatorBase; a CPU tensor still takes the target's own method) and
+`SpecDiscriminatorBase.forward`, which runs a stack of weight-normed 3x3 convs
+of stride 1 and 16 channels under the frequency embedding on the device
+(DiscriminatorMagFree at n_fft 64) and leaves every other stack to the
+target's own method.
 """
 import promonet_amd
 
@@ -52,7 +56,9 @@ def patch(promonet):
         if hasattr(promonet.model, name):
             setattr(promonet.model, name, getattr(promonet_amd.model, name))
     # the spectrograms of the spectral discriminators, where the target has
-    # them; the conv stacks stay the target's own
+    # them, and SpecDiscriminatorBase.forward for the stacks whose layers the
+    # kernels compute (stride 1, 16 channels: DiscriminatorMagFree at n_fft
+    # 64); every other conv stack stays the target's own
     discriminator = getattr(promonet.model, 'discriminator', None)
     if discriminator is not None:
         promonet_amd.model.discriminator.patch_module(discriminator)
