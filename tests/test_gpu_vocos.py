@@ -3,6 +3,16 @@
 
 Gates are <= 3x the errors measured with PM_RECORD_ERRORS=1 (DESIGN.md
 section 2); the fp32 end-to-end contract (1e-4) is far looser than its gates.
+
+test_istft_against_irfft_and_fold and test_head_exp_clip_and_large_phases
+take one maximum over dense outputs, relative to the peak, against an fp32
+oracle: they hold the head as a whole, at sizes up to 861 frames. What they
+average away is in the care of tests/test_gpu_vocos_head.py: every bin of the
+inverse transform on its own samples against a float64 oracle, the expf, the
+side of the clip and the phase of bins below the clip, the handoff of the
+logits in each operand type with no tolerance, and the index arithmetic of the
+overlap-add (frame range, the clamp at the last frame, the crop, the envelope
+of the frames that exist) bit for bit.
 """
 import math
 
