@@ -303,6 +303,16 @@ int pm_conv_transpose_cl(int dtype, const float* x_cl, float* out_cl,
                          int length, int c_in, int c_out, int rate, int lrelu,
                          void* workspace, size_t workspace_bytes,
                          void* stream);
+/* pm_conv_transpose_cl on a ragged batch, as a forward with `lengths` launches
+ * the layer: lengths (B) int32 on the device, input rows per utterance
+ * (clamped to `length`). Rows of x past lengths[b] read as zero, and the rows
+ * of out_cl past rate * lengths[b] are not written. */
+int pm_conv_transpose_ragged_cl(int dtype, const float* x_cl, float* out_cl,
+                                const float* w, const float* bias,
+                                const int* lengths, int batch, int length,
+                                int c_in, int c_out, int rate, int lrelu,
+                                void* workspace, size_t workspace_bytes,
+                                void* stream);
 /* pm_conv_transpose_cl on an input that already holds the operand values:
  * x16_cl (B, L, c_in_pad) in the operand type `dtype` (PM_F16 | PM_BF16) =
  * cvt(lrelu(x)) as pm_block_act16_cl writes it; narrow (r = 2 ...) upsamplers */

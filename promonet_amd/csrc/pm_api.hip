@@ -1368,8 +1368,8 @@ static TransposeLayout transpose_layout(int c_in, int c_out, int r,
 
 static int conv_transpose_cl_impl(
     int dtype, const float* x, const void* x16, float* out, const float* w,
-    const float* bias, int B, int L, int c_in, int c_out, int r, int lrelu,
-    void* ws, size_t ws_bytes, void* stream) {
+    const float* bias, int B, int L, const int* lengths, int c_in, int c_out,
+    int r, int lrelu, void* ws, size_t ws_bytes, void* stream) {
     if ((!x && !x16) || !out || !w || !bias || !ws)
         return pm_fail(PM_EINVAL, "null argument");
     if (r < 2 || (r & 1)) return pm_fail(PM_EINVAL, "rate %d unsupported", r);
@@ -1385,7 +1385,7 @@ static int conv_transpose_cl_impl(
                        "operand type and the narrow upsampler kernel");
     up.w = l.w; up.bias = l.bias;
     PM_HIP_TRY(pack_layer(up, w, bias, s));
-    PM_HIP_TRY(launch_upsample(up, x, x16, out, lrelu, B, L, nullptr, 1, s));
+    PM_HIP_TRY(launch_upsample(up, x, x16, out, lrelu, B, L, lengths, 1, s));
     return PM_OK;
 }
 
@@ -1394,8 +1394,22 @@ extern "C" int pm_conv_transpose_cl(
     int B, int L, int c_in, int c_out, int r, int lrelu, void* ws,
     size_t ws_bytes, void* stream) {
     if (!x) return pm_fail(PM_EINVAL, "null argument");
-    return conv_transpose_cl_impl(dtype, x, nullptr, out, w, bias, B, L, c_in,
-                                  c_out, r, lrelu, ws, ws_bytes, stream);
+    return conv_transpose_cl_impl(dtype, x, nullptr, out, w, bias, B, L,
+                                  nullptr, c_in, c_out, r, lrelu, ws, ws_bytes,
+                                  stream);
+}
+
+// pm_conv_transpose_cl on a ragged batch, as a forward with `lengths` launches
+// the layer: utterance b has lengths[b] input rows (device int32, clamped to
+// `length`); its output rows past r * lengths[b] are not written.
+extern "C" int pm_conv_transpose_ragged_cl(
+    int dtype, const float* x, float* out, const float* w, const float* bias,
+    const int* lengths, int B, int L, int c_in, int c_out, int r, int lrelu,
+    void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !lengths) return pm_fail(PM_EINVAL, "null argument");
+    return conv_transpose_cl_impl(dtype, x, nullptr, out, w, bias, B, L,
+                                  lengths, c_in, c_out, r, lrelu, ws, ws_bytes,
+                                  stream);
 }
 
 // pm_conv_transpose_cl on an input that already holds the operand values:
@@ -1406,8 +1420,9 @@ extern "C" int pm_conv_transpose_x16_cl(
     int B, int L, int c_in, int c_out, int r, void* ws, size_t ws_bytes,
     void* stream) {
     if (!x16) return pm_fail(PM_EINVAL, "null argument");
-    return conv_transpose_cl_impl(dtype, nullptr, x16, out, w, bias, B, L, c_in,
-                                  c_out, r, 1, ws, ws_bytes, stream);
+    return conv_transpose_cl_impl(dtype, nullptr, x16, out, w, bias, B, L,
+                                  nullptr, c_in, c_out, r, 1, ws, ws_bytes,
+                                  stream);
 }
 
 extern "C" int pm_out_conv_tanh(

@@ -325,6 +325,16 @@ __device__ __forceinline__ void pm_block_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// Orders the lanes' LDS accesses of one wave: code that hands data from lane
+// to lane through LDS without a workgroup barrier (a wave's DS instructions
+// execute in order) must keep the compiler from moving this thread's reads
+// above the other lanes' writes.
+__device__ __forceinline__ void pm_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
+
 // Bijective XCD-aware remap of a linear workgroup id: the dispatcher places
 // block b on XCD b % 8; give each XCD a contiguous run of tiles so that
 // neighbouring time tiles (which share halo rows) hit the same L2.

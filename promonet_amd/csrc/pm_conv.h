@@ -840,6 +840,93 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_pair_kernel(
 // Generic single convolution / polyphase transposed convolution
 // ---------------------------------------------------------------------------
 
+// ---------------------------------------------------------------------------
+// Row stores. The outputs here are (B, L, M) with M floats a column. In the
+// MFMA C/D layout a lane holds one column, so a direct b128 store writes 32
+// pieces of 32 bytes, one per column: 32-byte write requests to the L2.
+// pm_store_rows turns a wave's 32-column tiles round, CP columns at a time,
+// in an LDS buffer of the wave's own (no workgroup barrier: pm_wave_lds_sync)
+// and stores them with RUN / 16 lanes on one column's run of MTW * 32 floats:
+// whole 128-byte lines, half the write requests. Same acc + bias additions,
+// the same bytes. Read by one later launch only, hence non-temporal: such
+// stores do not wait in the L2 to be merged, which whole lines do not need
+// (on the 32-byte pieces of the direct stores nt takes 2.4 times as long).
+// ---------------------------------------------------------------------------
+#ifndef PM_ROWS_AUX
+#define PM_ROWS_AUX 2       // nt
+#endif
+#ifndef PM_SINGLE_ROWS
+#define PM_SINGLE_ROWS 1    // conv_single_kernel's r = 2 upsamplers too
+#endif
+template <int MTW, int CP>
+struct RowStores {
+    static constexpr int RUN = MTW * 32 * 4;   // bytes of one column per wave
+    static constexpr int WAVE = CP * RUN;      // CP columns of a wave's tile
+    static constexpr int LPR = RUN / 16;       // lanes on one run
+    static constexpr int CPI = 64 / LPR;       // columns per store instruction
+    static_assert(MTW == 1 || MTW == 2, "8 or 16 slots of 16 bytes");
+    static_assert(CP == 8 || CP == 16 || CP == 32, "whole 8-lane store groups");
+    // slot (16 bytes) `s` of column `col`: XOR-swizzled so that the 8-lane
+    // groups of ds_write_b128 (8 columns, one slot) and the 16-lane groups of
+    // ds_read_b128 (pieces of two or four columns) each cover every bank once
+    static __device__ __forceinline__ int at(int col, int s) {
+        return col * RUN + ((s ^ (col & 7)) << 4);
+    }
+};
+
+// acc: the wave's tiles, rows m0 ... of M, columns n0 ... of the descriptor
+// `orsrc` (which drops the columns past its end); ebuf: RowStores::WAVE bytes
+template <int MTW, int NTW, int CP>
+__device__ __forceinline__ void pm_store_rows(
+    const floatx16 (&acc)[MTW][NTW], char* ebuf, const float* bias_ptr,
+    const float* gb, __amdgpu_buffer_rsrc_t orsrc, int M, int m0, int n0,
+    int lane) {
+    typedef RowStores<MTW, CP> R;
+    const int ln = lane & 31, lh = lane >> 5;
+    // after the turn: lane = (column % CPI, 4 output channels)
+    const int q = lane % R::LPR, h = lane / R::LPR;
+    const int co = m0 + 4 * q;
+    float4 bias = *reinterpret_cast<const float4*>(bias_ptr + co);
+    if (gb) {
+        const float4 g = *reinterpret_cast<const float4*>(gb + co);
+        bias.x += g.x; bias.y += g.y; bias.z += g.z; bias.w += g.w;
+    }
+#pragma unroll
+    for (int pass = 0; pass < NTW * (32 / CP); ++pass) {
+        const int nt = pass / (32 / CP), sub = pass % (32 / CP);
+        pm_wave_lds_sync();     // the last pass's reads are done
+        if (CP == 32 || ln / CP == sub) {
+#pragma unroll
+            for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4)
+                    *reinterpret_cast<float4*>(
+                        ebuf + R::at(ln % CP, mt * 8 + 2 * g4 + lh)) =
+                        make_float4(acc[mt][nt][4 * g4 + 0],
+                                    acc[mt][nt][4 * g4 + 1],
+                                    acc[mt][nt][4 * g4 + 2],
+                                    acc[mt][nt][4 * g4 + 3]);
+        }
+        pm_wave_lds_sync();
+        const int n = n0 + nt * 32 + sub * CP + h;
+        const unsigned voff = (unsigned)((n * M + co) * 4);
+#pragma unroll
+        for (int k = 0; k < CP / R::CPI; ++k) {
+            const float4 v = *reinterpret_cast<const float4*>(
+                ebuf + R::at(R::CPI * k + h, q));
+            pm_u4 r;
+            r.x = __float_as_uint(v.x + bias.x);
+            r.y = __float_as_uint(v.y + bias.y);
+            r.z = __float_as_uint(v.z + bias.z);
+            r.w = __float_as_uint(v.w + bias.w);
+            // (the column step is part of the range-checked vector offset)
+            __builtin_amdgcn_raw_buffer_store_b128(
+                r, orsrc, voff + (unsigned)(k * R::CPI * M * 4), 0,
+                PM_ROWS_AUX);
+        }
+    }
+}
+
 struct SingleArgs {
     const void* x16;      // (B, L, Cin) operand-type copy of act(x), or null:
                           // staged as it is instead of x (16-bit types only)
@@ -981,6 +1068,20 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_single_kernel(
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
         a.out + ((size_t)b * a.Lout + t0) * M, 0,
         min(Lout - t0, N1) * M * 4, 0x00020000);
+    // the 16-bit r = 2 upsamplers: row stores through the x chunks' LDS, once
+    // every wave is done with them. bf16, batch 32 x 10 s: C_in 128 -> 64
+    // 0.345 -> 0.292 ms, 64 -> 32 0.301 -> 0.232 ms
+    // (profiles/upsample_store/NOTES.md); the input conv (KT 7) and the
+    // 4-byte operand types keep the direct stores, unmeasured
+    constexpr bool ROWS =
+        PM_SINGLE_ROWS && ET::ESZ == 2 && KT == 2 && MTW == 1 &&
+        WM * WN * 32 * 128 <= 2 * XR * SX;
+    if constexpr (ROWS) {
+        pm_block_sync();
+        pm_store_rows<MTW, NTW, 32>(
+            acc, smem + wave * RowStores<MTW, 32>::WAVE, a.bias, gb, orsrc, M,
+            m0, wn * NTW * 32, lane);
+    } else {
 #pragma unroll
     for (int mt = 0; mt < MTW; ++mt) {
         const int co_base = m0 + mt * 32 + 4 * lh;
@@ -1010,6 +1111,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_single_kernel(
                     r, orsrc, voff + g4 * 32, 0, 0);
             }
         }
+    }
     }
     } else if constexpr (EPI == 3) {
     float* ob = a.out + (size_t)b * a.Lout * M;
@@ -1094,8 +1196,11 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_single_kernel(
 // Here the whole x tile ((128 + 2) rows x C_in, 16-bit) is staged ONCE and the
 // workgroup walks its M blocks with no barrier in between - one continuous
 // weight stream (packed as a single chunk, CH = C_in).
+//
+// ROWS > 0: the epilogue of an M block is pm_store_rows, ROWS columns at a
+// time, in LDS behind the x tile; ROWS = 0: direct stores.
 // ---------------------------------------------------------------------------
-template <class ET, int CIN, int WM, int WN, int MTW, int NTW>
+template <class ET, int CIN, int WM, int WN, int MTW, int NTW, int ROWS = 0>
 __global__ __launch_bounds__(WM * WN * 64) void conv_upsample_kernel(
     SingleArgs a) {
     typedef typename ET::afrag_t frag_t;
@@ -1178,6 +1283,11 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_upsample_kernel(
         mma_taps<ET, KT, KC, MTW, NTW, G, S>(
             acc, smem + lane_off, S, w, w_mt_stride, afirst,
             mi + 1 < per_group ? w + (size_t)(MB / 32) * w_mt_stride : nullptr);
+        if constexpr (ROWS) {
+            pm_store_rows<MTW, NTW, ROWS>(
+                acc, smem + XR * S + wave * RowStores<MTW, ROWS>::WAVE, a.bias,
+                gb, orsrc, M, m0, wn * NTW * 32, lane);
+        } else {
 #pragma unroll
         for (int mt = 0; mt < MTW; ++mt) {
             const int co_base = m0 + mt * 32 + 4 * lh;
@@ -1207,6 +1317,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_upsample_kernel(
                         r, orsrc, voff + g4 * 32, 0, 0);
                 }
             }
+        }
         }
     }
 }

@@ -194,16 +194,6 @@ __device__ __forceinline__ void pm_radix8(pm_v2 (&a)[8]) {
     }
 }
 
-// Orders the lanes' LDS accesses of one wave: the exchanges below hand data
-// from lane to lane through LDS without a workgroup barrier (a wave's DS
-// instructions execute in order), so the compiler must not move this thread's
-// reads above the other lanes' writes.
-__device__ __forceinline__ void pm_wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
-
 // EPI 4 keeps the mel filters' non-zero spans (2 x 513 + rounding values for
 // librosa's 80 triangles) in LDS when they fit
 #define PM_FFT_MEL_CAP 2048

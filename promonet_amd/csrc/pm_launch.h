@@ -56,6 +56,12 @@ inline int pm_fusion_level() {
 // LDS a walked or skewed workgroup may take
 #define PM_LDS_BYTES (160 * 1024)
 
+// 1: the wide upsampler stores rows through LDS (launch_upsample_cfg; the
+// r = 2 upsamplers: PM_SINGLE_ROWS, pm_conv.h); 0: direct stores, for A/B builds
+#ifndef PM_UPSAMPLE_ROWS
+#define PM_UPSAMPLE_ROWS 1
+#endif
+
 // ---- fused pair geometry per (operand type, C) ---------------------------
 template <class ET, int C> struct PairCfg;
 // 16-bit operands: every wave owns a 32 (co) x 128 (time) register tile, so
@@ -768,13 +774,40 @@ static hipError_t launch_upsample_cfg(const SingleArgs& a0, hipStream_t stream) 
     if (groups > mblocks) groups = mblocks;
     while (mblocks % groups) groups /= 2;
     a.nmblocks = groups;
+    constexpr int xtile = (N1 + 2) * (CIN * ET::ESZ + 16);
+    const dim3 grid(a.ntiles * a.nmblocks * a.B), block(WM * WN * 64);
+    // Row stores (conv_upsample_kernel, ROWS > 0): every wave turns its
+    // tiles round in LDS behind the x tile, 32 columns at a time (8 KB a
+    // wave) where there is room - C_in = 256: 67 + 64 of 160 KB - and 8
+    // columns (2 KB) at C_in = 512 (132 + 16 KB). A forced group count keeps
+    // the direct stores, so that both stay under test.
+    // Measured, bf16, batch 32 x 10 s (profiles/upsample_store/NOTES.md):
+    // direct stores 0.359 ms (C_in 256) / 0.161 ms (512); row stores 0.298 /
+    // 0.141, with half the write requests from the CUs to the L2; row stores
+    // non-temporal (shipped) 0.276 / 0.137. Staging x for fewer groups at
+    // C_in = 512 (2 instead of 4) measured neutral, 0.142, and is not kept.
+    // Row stores with a workgroup barrier (whole 1 KB runs of a row) were
+    // not built: the 256-byte runs already make every request a whole line.
+    // (-DPM_UPSAMPLE_ROWS=0: the A/B build with direct stores)
+    constexpr int CP =
+        xtile + WM * WN * RowStores<MTW, 32>::WAVE <= PM_LDS_BYTES ? 32 : 8;
+    if constexpr (PM_UPSAMPLE_ROWS &&
+                  xtile + WM * WN * RowStores<MTW, CP>::WAVE <= PM_LDS_BYTES) {
+        if (pm_force().upsample_groups == 0) {
+            auto rows = conv_upsample_kernel<ET, CIN, WM, WN, MTW, NTW, CP>;
+            constexpr int smem = xtile + WM * WN * RowStores<MTW, CP>::WAVE;
+            hipError_t e = pm_ensure_dynamic_lds(
+                reinterpret_cast<const void*>(rows), smem);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(rows, grid, block, smem, stream, a);
+            return hipGetLastError();
+        }
+    }
     auto kern = conv_upsample_kernel<ET, CIN, WM, WN, MTW, NTW>;
-    constexpr int smem = (N1 + 2) * (CIN * ET::ESZ + 16);
     hipError_t e = pm_ensure_dynamic_lds(
-        reinterpret_cast<const void*>(kern), smem);
+        reinterpret_cast<const void*>(kern), xtile);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(a.ntiles * a.nmblocks * a.B),
-                       dim3(WM * WN * 64), smem, stream, a);
+    hipLaunchKernelGGL(kern, grid, block, xtile, stream, a);
     return hipGetLastError();
     }
 }
