@@ -895,6 +895,43 @@ int pm_fdisc_weight_norm_backward(const float* grad_w, const float* g,
                                   const float* v, float* grad_g, float* grad_v,
                                   int out_channels, int fan, void* stream);
 
+/* ---- CMB and resolution discriminator conv stacks --------------------------
+ * One layer of DiscriminatorCMB.band_convs / conv_post
+ * (promonet/model/discriminator.py:146-208) and of DiscriminatorR.convs /
+ * conv_post (:96-127), forward and backward:
+ *   y = leaky(conv2d(x, weight, bias, stride (1, stride),
+ *                    padding (1, (kernel_width - 1) / 2)), slope)
+ * with (channels, out_channels, kernel_width, stride) one of (1, 32, 9, 1),
+ * (32, 32, 9, 2), (32, 32, 3, 1), (32, 1, 3, 1): the whole reference. The
+ * output is (width - 1) / stride + 1 wide and `height` high. slope 1 is no
+ * activation. fp32 throughout; the 32 -> 32 layers run on the fp32-input MFMA.
+ * MEMORY ORDER: a map of 32 channels is channels_last, in memory (batch,
+ * height, width, 32); a map of one channel is (batch, height, width). weight
+ * is torch's (out_channels, channels, 3, kernel_width), bias (out_channels).
+ * Backward: from upstream, the saved y and the saved x, with gz = upstream *
+ * (y > 0 ? 1 : slope): grad_x in the layout of x (NULL skips it), grad_weight
+ * and grad_bias (both NULL skips them). The two sums over all pixels go
+ * through per-workgroup partials in the workspace, whose count depends on the
+ * sizes alone, added in a fixed order in double: no float atomics, the same
+ * bits on every run. All asynchronous, no allocation, capturable.
+ * Another form, batch, height or width below 1, a slope that is not finite or
+ * not in (0, 1], more than 2^31 - 1 input or output pixels, a null pointer or
+ * a workspace that is too small are refused before any device work; the
+ * workspace query returns 0 for such sizes.                                 */
+size_t pm_dconv_workspace_bytes(int batch, int channels, int out_channels,
+                                int height, int width, int kernel_width,
+                                int stride);
+int pm_dconv_forward(const float* x, const float* weight, const float* bias,
+                     float* y, int batch, int channels, int out_channels,
+                     int height, int width, int kernel_width, int stride,
+                     float slope, void* stream);
+int pm_dconv_backward(const float* upstream, const float* y, const float* x,
+                      const float* weight, float* grad_x, float* grad_weight,
+                      float* grad_bias, int batch, int channels,
+                      int out_channels, int height, int width,
+                      int kernel_width, int stride, float slope,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- adversarial losses: promonet/train/loss.py:11-53 ---------------------
  * feature_matching, discriminator and generator are each a sum of means over
  * a list of tensors of unrelated sizes. pm_multi_mean takes the whole list:

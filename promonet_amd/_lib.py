@@ -165,6 +165,9 @@ SIGNATURES = {
     'pm_fdisc_conv_backward': (_I, [_P] * 8 + [_I] * 7 + [_P, _S, _P]),
     'pm_fdisc_weight_norm_forward': (_I, [_P] * 3 + [_I, _I, _P]),
     'pm_fdisc_weight_norm_backward': (_I, [_P] * 5 + [_I, _I, _P]),
+    'pm_dconv_workspace_bytes': (_S, [_I] * 7),
+    'pm_dconv_forward': (_I, [_P] * 4 + [_I] * 7 + [_F, _P]),
+    'pm_dconv_backward': (_I, [_P] * 7 + [_I] * 7 + [_F, _P, _S, _P]),
     'pm_multi_mean_chunk': (_I, []),
     'pm_multi_mean_workspace_bytes': (_S, [_P, _I]),
     'pm_multi_mean': (_I, [_P] * 5 + [_I, _P, _P, _S, _P]),

@@ -7,9 +7,11 @@ API of the three `spectrogram` methods of `promonet.model.discriminator`
 (promonet/model/discriminator.py): DiscriminatorR (:129-143),
 DiscriminatorCMB (:175-192) and SpecDiscriminatorBase (:278-299), and of
 DiscriminatorMagFree (:320-389). The conv stacks of DiscriminatorMagFree are
-in (`frequency_conv`, `weight_norm`, `DiscriminatorMagFree`); those of
-DiscriminatorP / S / R / CMB stay on torch. Neither direction syncs with the
-host, and both capture into a graph on one stream.
+in (`frequency_conv`, `weight_norm`, `DiscriminatorMagFree`), and so are those
+of DiscriminatorCMB (:146-208) and DiscriminatorR (:96-127) on the kernels of
+pm_dconv.h (`band_conv`, `DiscriminatorCMB`, `DiscriminatorR`); those of
+DiscriminatorP / S stay on torch. Neither direction syncs with the host, and
+both capture into a graph on one stream.
 """
 import math
 
@@ -526,6 +528,322 @@ def _wrap_forward(original):
 
 
 ###############################################################################
+# The conv stacks of DiscriminatorCMB and DiscriminatorR
+###############################################################################
+
+# (channels, out_channels, kernel_width, stride): the whole reference
+BAND_FORMS = ((1, 32, 9, 1), (32, 32, 9, 2), (32, 32, 3, 1), (32, 1, 3, 1))
+
+
+def _band_sizes(x, weight, bias, stride, slope):
+    """((B, C, O, H, W, kw, s), slope) of a checked call; ValueError
+    otherwise"""
+    for name, tensor in (('x', x), ('weight', weight), ('bias', bias)):
+        if not isinstance(tensor, torch.Tensor) or \
+                not tensor.is_floating_point():
+            raise ValueError(f'{name} must be a float tensor')
+    if x.ndim != 4 or not x.numel():
+        raise ValueError(
+            f'x {tuple(x.shape)}: must be (B, C, H, W) with no empty axis')
+    batch, channels, height, width = x.shape
+    if isinstance(stride, (tuple, list)):
+        if len(stride) != 2 or stride[0] != 1:
+            raise ValueError(f'stride {stride!r}: must be (1, s)')
+        stride = stride[1]
+    if weight.ndim != 4 or weight.shape[2] != 3 or \
+            (weight.shape[1], weight.shape[0], weight.shape[3], stride) \
+            not in BAND_FORMS:
+        raise ValueError(
+            f'weight {tuple(weight.shape)} at stride {stride!r}: (channels, '
+            f'out_channels, kernel_width, stride) must be one of {BAND_FORMS} '
+            'with a kernel height of 3')
+    if weight.shape[1] != channels:
+        raise ValueError(
+            f'x {tuple(x.shape)}: weight {tuple(weight.shape)} takes '
+            f'{weight.shape[1]} channels')
+    out_channels = weight.shape[0]
+    if tuple(bias.shape) != (out_channels,):
+        raise ValueError(
+            f'bias {tuple(bias.shape)}: must be ({out_channels},)')
+    if isinstance(slope, bool) or not isinstance(slope, (int, float)) or \
+            not math.isfinite(slope) or not 0. < slope <= 1.:
+        raise ValueError(f'slope {slope!r}: must be finite and in (0, 1]')
+    if batch * height * width > 2 ** 31 - 1:
+        raise ValueError(f'x {tuple(x.shape)}: more than 2^31 - 1 pixels')
+    return (batch, channels, out_channels, height, width, weight.shape[3],
+            int(stride)), float(slope)
+
+
+class _BandConv(torch.autograd.Function):
+    """backward: gx, gW and gb from the upstream gradient, the saved output
+    and the saved input (pm_dconv_backward)"""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, x, weight, bias, sizes, slope):
+        lib = _lib.lib()
+        batch, _, out_channels, height, width, _, stride = sizes
+        x, weight, bias = _map_order(x), weight.contiguous(), bias.contiguous()
+        y = _empty_map(
+            batch, out_channels, height, (width - 1) // stride + 1, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.pm_dconv_forward(
+                x.data_ptr(), _lib.ptr(weight), _lib.ptr(bias), y.data_ptr(),
+                *sizes, slope, _lib.stream()))
+        ctx.save_for_backward(x, weight, y)
+        ctx.sizes, ctx.slope = sizes, slope
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, grad):
+        lib = _lib.lib()
+        x, weight, y = ctx.saved_tensors
+        sizes = ctx.sizes
+        grad = _map_order(grad.to(torch.float32))
+        need_x, need_weight, need_bias = ctx.needs_input_grad[:3]
+        grad_x = torch.empty_like(x) if need_x else None
+        grad_weight = grad_bias = workspace = None
+        with torch.cuda.device(x.device):
+            if need_weight or need_bias:
+                grad_weight = torch.empty_like(weight)
+                grad_bias = torch.empty(sizes[2], device=x.device)
+                workspace = torch.empty(
+                    lib.pm_dconv_workspace_bytes(*sizes), dtype=torch.uint8,
+                    device=x.device)
+            _lib.check(lib.pm_dconv_backward(
+                grad.data_ptr(), y.data_ptr(), x.data_ptr(), _lib.ptr(weight),
+                None if grad_x is None else grad_x.data_ptr(),
+                _lib.ptr(grad_weight), _lib.ptr(grad_bias), *sizes, ctx.slope,
+                None if workspace is None else workspace.data_ptr(),
+                0 if workspace is None else workspace.numel(), _lib.stream()))
+        return (grad_x, grad_weight if need_weight else None,
+                grad_bias if need_bias else None, None, None)
+
+
+def band_conv(x, weight, bias, stride=1, slope=1.0):
+    """One layer of DiscriminatorCMB.band_convs / conv_post (:146-208) and of
+    DiscriminatorR.convs / conv_post (:96-127) without its weight norm:
+    leaky_relu(conv2d(x, weight, bias, stride (1, stride), padding (1, (kw -
+    1) / 2)), slope). x (B, C, H, W) on the device, weight (O, C, 3, kw), bias
+    (O), with (C, O, kw, stride) one of BAND_FORMS; slope in (0, 1], 1 being
+    no activation. Returns (B, O, H, (W - 1) // stride + 1) fp32; with 32
+    channels it is channels_last in memory, as is the gradient in x; a
+    one-channel x that is not contiguous (a band of the spectrogram) is copied
+    once. Differentiable in x, weight and bias. Other float dtypes are cast to
+    fp32 and their gradients return in their dtype."""
+    sizes, slope = _band_sizes(x, weight, bias, stride, slope)
+    _lib.require_gpu(x)
+    return _BandConv.apply(
+        x.to(torch.float32), weight.to(torch.float32),
+        bias.to(torch.float32), sizes, slope)
+
+
+class _NormedBandConv(torch.nn.Module):
+    """The parameters of a weight-normed Conv2d(channels, out_channels, (3,
+    kernel_width), (1, stride)), under the names torch.nn.utils.weight_norm
+    gives"""
+
+    def __init__(self, channels, out_channels, kernel_width, stride):
+        super().__init__()
+        conv = torch.nn.Conv2d(channels, out_channels, (3, kernel_width))
+        weight = conv.weight.detach()
+        self.bias = torch.nn.Parameter(conv.bias.detach().clone())
+        self.weight_g = torch.nn.Parameter(
+            weight.flatten(1).norm(dim=1).reshape(-1, 1, 1, 1))
+        self.weight_v = torch.nn.Parameter(weight.clone())
+        self.stride = stride
+
+    def apply_to(self, x, slope):
+        return band_conv(
+            x, weight_norm(self.weight_g, self.weight_v), self.bias,
+            self.stride, slope)
+
+
+class DiscriminatorCMB(torch.nn.Module):
+    """promonet.model.discriminator.DiscriminatorCMB (:146-208) on the device:
+    the magnitude spectrogram in bands, five weight-normed convs a band under
+    LeakyReLU(0.1), the bands' last maps joined on the width axis, and a 32 ->
+    1 conv without activation. The state_dict has the reference's keys and
+    shapes."""
+
+    def __init__(self, bands=DEFAULT_BANDS):
+        super().__init__()
+        self.bands = tuple(tuple(band) for band in bands)
+        self.band_convs = torch.nn.ModuleList([
+            torch.nn.ModuleList([
+                torch.nn.Sequential(
+                    _NormedBandConv(*form), torch.nn.LeakyReLU(0.1))
+                for form in BAND_FORMS[:1] + BAND_FORMS[1:2] * 3 +
+                BAND_FORMS[2:3]])
+            for _ in self.bands])
+        self.conv_post = _NormedBandConv(*BAND_FORMS[3])
+
+    def stack(self, bands_list):
+        """The band tensors (B, 1, frames, bins of the band) -> (logits (B,
+        1, frames, joined width), the 26 maps in the reference's order)"""
+        last, maps = [], []
+        for band, convs in zip(bands_list, self.band_convs):
+            for layer in convs:
+                band = layer[0].apply_to(band, layer[1].negative_slope)
+                maps.append(band)
+            last.append(band)
+        logits = self.conv_post.apply_to(torch.cat(last, dim=-1), 1.)
+        maps.append(logits)
+        return logits, maps
+
+    def forward(self, audio):
+        """audio (B, 1, T) -> (logits flattened, the 26 maps)"""
+        logits, maps = self.stack(spectrogram_multiband(audio, self.bands))
+        return torch.flatten(logits, 1, -1), maps
+
+
+class DiscriminatorR(torch.nn.Module):
+    """promonet.model.discriminator.DiscriminatorR (:96-127) on the device:
+    the magnitude spectrogram (B, 1, bins, frames), five weight-normed convs
+    under leaky_relu(0.2), the maps taken after the activation, and a 32 -> 1
+    conv without activation. The state_dict has the reference's keys and
+    shapes."""
+
+    SLOPE = 0.2
+
+    def __init__(self, resolution):
+        super().__init__()
+        self.resolution = tuple(int(v) for v in resolution)
+        self.convs = torch.nn.ModuleList([
+            _NormedBandConv(*form)
+            for form in BAND_FORMS[:1] + BAND_FORMS[1:2] * 3 +
+            BAND_FORMS[2:3]])
+        self.conv_post = _NormedBandConv(*BAND_FORMS[3])
+
+    def stack(self, x):
+        """x (B, 1, bins, frames) -> (logits (B, 1, bins, width), the six
+        maps)"""
+        maps = []
+        for conv in self.convs:
+            x = conv.apply_to(x, self.SLOPE)
+            maps.append(x)
+        logits = self.conv_post.apply_to(x, 1.)
+        maps.append(logits)
+        return logits, maps
+
+    def forward(self, audio):
+        """audio (B, 1, T) -> (logits flattened, the six maps)"""
+        logits, maps = self.stack(
+            spectrogram_resolution(audio, self.resolution))
+        return torch.flatten(logits, 1, -1), maps
+
+
+def _band_form(conv, channels):
+    """The stride of a weight-normed Conv2d of one of BAND_FORMS that takes
+    `channels` channels, or None"""
+    if not isinstance(conv, torch.nn.Conv2d) or conv.bias is None or \
+            not isinstance(getattr(conv, 'weight_g', None), torch.Tensor) or \
+            not isinstance(getattr(conv, 'weight_v', None), torch.Tensor):
+        return None
+    kernel_width = conv.kernel_size[1]
+    if conv.kernel_size[0] != 3 or conv.stride[0] != 1 or \
+            tuple(conv.dilation) != (1, 1) or conv.groups != 1 or \
+            conv.padding_mode != 'zeros' or conv.in_channels != channels or \
+            tuple(conv.padding) != (1, (kernel_width - 1) // 2) or \
+            (channels, conv.out_channels, kernel_width, conv.stride[1]) \
+            not in BAND_FORMS:
+        return None
+    return conv.stride[1]
+
+
+def _normed(conv):
+    return weight_norm(conv.weight_g, conv.weight_v)
+
+
+def _cmb_layers(self):
+    """([[(conv, stride, slope)] a band], conv_post) where every layer of a
+    reference-style DiscriminatorCMB has a form the kernels compute, or None"""
+    stacks = []
+    try:
+        for convs in self.band_convs:
+            layers, channels = [], 1
+            for layer in convs:
+                if not isinstance(layer, torch.nn.Sequential) or \
+                        len(layer) != 2 or \
+                        not isinstance(layer[1], torch.nn.LeakyReLU) or \
+                        not 0. < layer[1].negative_slope <= 1.:
+                    return None
+                stride = _band_form(layer[0], channels)
+                if stride is None:
+                    return None
+                layers.append((layer[0], stride, layer[1].negative_slope))
+                channels = layer[0].out_channels
+            if not layers or channels != 32:
+                return None
+            stacks.append(layers)
+        if not stacks or _band_form(self.conv_post, 32) is None or \
+                self.conv_post.out_channels != 1:
+            return None
+    except (AttributeError, TypeError):
+        return None
+    return stacks, self.conv_post
+
+
+def _wrap_cmb_forward(original):
+    def forward(self, x):
+        found = _cmb_layers(self) if x.is_cuda else None
+        if found is None:
+            return original(self, x)
+        stacks, post = found
+        last, maps = [], []
+        for band, layers in zip(self.spectrogram(x), stacks):
+            for conv, stride, slope in layers:
+                band = band_conv(band, _normed(conv), conv.bias, stride, slope)
+                maps.append(band)
+            last.append(band)
+        logits = band_conv(
+            torch.cat(last, dim=-1), _normed(post), post.bias, 1, 1.)
+        maps.append(logits)
+        return torch.flatten(logits, 1, -1), maps
+    forward.original = original
+    return forward
+
+
+def _r_layers(self):
+    """([(conv, stride)], conv_post) of a reference-style DiscriminatorR whose
+    layers all have a form the kernels compute, or None"""
+    layers, channels = [], 1
+    try:
+        for conv in self.convs:
+            stride = _band_form(conv, channels)
+            if stride is None:
+                return None
+            layers.append((conv, stride))
+            channels = conv.out_channels
+        if not layers or channels != 32 or \
+                _band_form(self.conv_post, 32) is None or \
+                self.conv_post.out_channels != 1:
+            return None
+    except (AttributeError, TypeError):
+        return None
+    return layers, self.conv_post
+
+
+def _wrap_r_forward(original):
+    def forward(self, audio):
+        found = _r_layers(self) if audio.is_cuda else None
+        if found is None:
+            return original(self, audio)
+        layers, post = found
+        x, maps = self.spectrogram(audio), []
+        for conv, stride in layers:
+            x = band_conv(
+                x, _normed(conv), conv.bias, stride, DiscriminatorR.SLOPE)
+            maps.append(x)
+        logits = band_conv(x, _normed(post), post.bias, 1, 1.)
+        maps.append(logits)
+        return torch.flatten(logits, 1, -1), maps
+    forward.original = original
+    return forward
+
+
+###############################################################################
 # The wrappers promonet_amd.patch installs
 ###############################################################################
 
@@ -545,7 +863,9 @@ def patch_module(module):
     where it has one; a tensor that is not on a GPU goes to the original
     method, and so does a module whose layers are not weight-normed 3x3 convs
     of stride 1 with a frequency dilation of 1 ... 16 under the frequency
-    embedding, each followed by ReLU or Sigmoid."""
+    embedding, each followed by ReLU or Sigmoid. The `forward` of
+    DiscriminatorCMB and of DiscriminatorR is replaced in the same way, where
+    the class has one, for modules whose layers all have one of BAND_FORMS."""
     wrappers = {
         'DiscriminatorR': lambda self, x: spectrogram_resolution(
             x, self.resolution),
@@ -562,3 +882,12 @@ def patch_module(module):
     forward = getattr(base, 'forward', None)
     if forward is not None and not hasattr(forward, 'original'):
         base.forward = _wrap_forward(forward)
+    # DiscriminatorCMB.forward and DiscriminatorR.forward, where the class has
+    # one: on the device when every layer is a weight-normed Conv2d of one of
+    # BAND_FORMS (in CMB inside Sequential(conv, LeakyReLU)), else the original
+    for name, wrap in (('DiscriminatorCMB', _wrap_cmb_forward),
+                       ('DiscriminatorR', _wrap_r_forward)):
+        cls = getattr(module, name, None)
+        forward = getattr(cls, 'forward', None)
+        if forward is not None and not hasattr(forward, 'original'):
+            cls.forward = wrap(forward)
