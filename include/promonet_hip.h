@@ -932,6 +932,62 @@ int pm_dconv_backward(const float* upstream, const float* y, const float* x,
                       int kernel_width, int stride, float slope,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- period discriminator conv stack ---------------------------------------
+ * One layer of DiscriminatorP.convs / conv_post
+ * (promonet/model/discriminator.py:57-93), forward and backward:
+ *   y = leaky(conv2d(x, weight, bias, stride (stride, 1),
+ *                    padding ((kernel - 1) / 2, 0)), slope)
+ * with x (batch, channels, height, period) and (channels, out_channels,
+ * kernel, stride) one of (1, 32, 5, 3), (32, 128, 5, 3), (128, 512, 5, 3),
+ * (512, 1024, 5, 3), (1024, 1024, 5, 1), (1024, 1, 3, 1): the whole
+ * reference. The conv runs along the height alone; the output is (height - 1)
+ * / stride + 1 high and `period` wide. slope 1 is no activation. fp32
+ * throughout; the layers of 32 and more channels on both sides run on the
+ * fp32-input MFMA.
+ * MEMORY ORDER: a map of 32 or more channels is channels_last, in memory
+ * (batch, height, period, channels); a map of one channel is (batch, height,
+ * period). weight is torch's (out_channels, channels, kernel, 1), bias
+ * (out_channels).
+ * THE FOLD: pm_pconv_fold_* are the first layer, (1, 32, 5, 3), on the audio
+ * (batch, samples) itself: the map (batch, (samples + n) / period, period) of
+ * the reference, n = (period - samples mod period) mod period samples
+ * reflected on the right, is read in place (sample t >= samples is sample
+ * 2 (samples - 1) - t) and never written. grad_audio (batch, samples) holds
+ * the adjoint of that reflection, in gather form.
+ * Backward: from upstream, the saved y and the saved x, with gz = upstream *
+ * (y > 0 ? 1 : slope): grad_x in the layout of x (NULL skips it), grad_weight
+ * and grad_bias (both NULL skips them). The sums over all pixels go through
+ * partials in the workspace, whose count depends on the sizes alone, added in
+ * a fixed order in double: no float atomics, the same bits on every run. All
+ * asynchronous, no allocation, capturable.
+ * Another form, batch or height below 1, a period outside 1 ... 64, samples <=
+ * n, a slope that is not finite or not in (0, 1], more than 2^31 - 1 input or
+ * output pixels, a null pointer or a workspace that is too small are refused
+ * before any device work; the workspace queries return 0 for such sizes.    */
+size_t pm_pconv_workspace_bytes(int batch, int channels, int out_channels,
+                                int height, int period, int kernel,
+                                int stride);
+int pm_pconv_forward(const float* x, const float* weight, const float* bias,
+                     float* y, int batch, int channels, int out_channels,
+                     int height, int period, int kernel, int stride,
+                     float slope, void* stream);
+int pm_pconv_backward(const float* upstream, const float* y, const float* x,
+                      const float* weight, float* grad_x, float* grad_weight,
+                      float* grad_bias, int batch, int channels,
+                      int out_channels, int height, int period, int kernel,
+                      int stride, float slope, void* workspace,
+                      size_t workspace_bytes, void* stream);
+size_t pm_pconv_fold_workspace_bytes(int batch, int samples, int period);
+int pm_pconv_fold_forward(const float* audio, const float* weight,
+                          const float* bias, float* y, int batch, int samples,
+                          int period, float slope, void* stream);
+int pm_pconv_fold_backward(const float* upstream, const float* y,
+                           const float* audio, const float* weight,
+                           float* grad_audio, float* grad_weight,
+                           float* grad_bias, int batch, int samples,
+                           int period, float slope, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ---- adversarial losses: promonet/train/loss.py:11-53 ---------------------
  * feature_matching, discriminator and generator are each a sum of means over
  * a list of tensors of unrelated sizes. pm_multi_mean takes the whole list:

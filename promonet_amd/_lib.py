@@ -168,6 +168,12 @@ SIGNATURES = {
     'pm_dconv_workspace_bytes': (_S, [_I] * 7),
     'pm_dconv_forward': (_I, [_P] * 4 + [_I] * 7 + [_F, _P]),
     'pm_dconv_backward': (_I, [_P] * 7 + [_I] * 7 + [_F, _P, _S, _P]),
+    'pm_pconv_workspace_bytes': (_S, [_I] * 7),
+    'pm_pconv_forward': (_I, [_P] * 4 + [_I] * 7 + [_F, _P]),
+    'pm_pconv_backward': (_I, [_P] * 7 + [_I] * 7 + [_F, _P, _S, _P]),
+    'pm_pconv_fold_workspace_bytes': (_S, [_I] * 3),
+    'pm_pconv_fold_forward': (_I, [_P] * 4 + [_I] * 3 + [_F, _P]),
+    'pm_pconv_fold_backward': (_I, [_P] * 7 + [_I] * 3 + [_F, _P, _S, _P]),
     'pm_multi_mean_chunk': (_I, []),
     'pm_multi_mean_workspace_bytes': (_S, [_P, _I]),
     'pm_multi_mean': (_I, [_P] * 5 + [_I, _P, _P, _S, _P]),

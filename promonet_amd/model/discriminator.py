@@ -9,9 +9,11 @@ DiscriminatorCMB (:175-192) and SpecDiscriminatorBase (:278-299), and of
 DiscriminatorMagFree (:320-389). The conv stacks of DiscriminatorMagFree are
 in (`frequency_conv`, `weight_norm`, `DiscriminatorMagFree`), and so are those
 of DiscriminatorCMB (:146-208) and DiscriminatorR (:96-127) on the kernels of
-pm_dconv.h (`band_conv`, `DiscriminatorCMB`, `DiscriminatorR`); those of
-DiscriminatorP / S stay on torch. Neither direction syncs with the host, and
-both capture into a graph on one stream.
+pm_dconv.h (`band_conv`, `DiscriminatorCMB`, `DiscriminatorR`) and that of
+DiscriminatorP (:57-93) on the kernels of pm_pconv.h (`period_conv`,
+`period_fold_conv`, `DiscriminatorP`), under the aggregate `Discriminator`
+(:13-49); the stack of DiscriminatorS stays on torch. Neither direction syncs
+with the host, and both capture into a graph on one stream.
 """
 import math
 
@@ -844,6 +846,373 @@ def _wrap_r_forward(original):
 
 
 ###############################################################################
+# The conv stack of DiscriminatorP, and the aggregate Discriminator
+###############################################################################
+
+# (channels, out_channels, kernel, stride): the whole reference, in the order
+# of the layers, conv_post last
+PERIOD_FORMS = ((1, 32, 5, 3), (32, 128, 5, 3), (128, 512, 5, 3),
+                (512, 1024, 5, 3), (1024, 1024, 5, 1), (1024, 1, 3, 1))
+PERIODS = (2, 3, 5, 7, 11)
+
+
+def _check_slope(slope):
+    if isinstance(slope, bool) or not isinstance(slope, (int, float)) or \
+            not math.isfinite(slope) or not 0. < slope <= 1.:
+        raise ValueError(f'slope {slope!r}: must be finite and in (0, 1]')
+    return float(slope)
+
+
+def _check_period(period):
+    if isinstance(period, bool) or not isinstance(period, int) or \
+            not 1 <= period <= 64:
+        raise ValueError(f'period {period!r}: must be an int in 1 ... 64')
+    return period
+
+
+def _check_parameters(weight, bias, forms, stride):
+    """The form of a checked (weight, bias) at a stride; ValueError
+    otherwise"""
+    for name, tensor in (('weight', weight), ('bias', bias)):
+        if not isinstance(tensor, torch.Tensor) or \
+                not tensor.is_floating_point():
+            raise ValueError(f'{name} must be a float tensor')
+    if isinstance(stride, (tuple, list)):
+        if len(stride) != 2 or stride[1] != 1:
+            raise ValueError(f'stride {stride!r}: must be (s, 1)')
+        stride = stride[0]
+    if weight.ndim != 4 or weight.shape[3] != 1 or \
+            (weight.shape[1], weight.shape[0], weight.shape[2], stride) \
+            not in forms:
+        raise ValueError(
+            f'weight {tuple(weight.shape)} at stride {stride!r}: (channels, '
+            f'out_channels, kernel, stride) must be one of {forms} with a '
+            'kernel width of 1')
+    if tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(
+            f'bias {tuple(bias.shape)}: must be ({weight.shape[0]},)')
+    return weight.shape[1], weight.shape[0], weight.shape[2], int(stride)
+
+
+def _period_sizes(x, weight, bias, stride, slope):
+    """((B, C, O, H, P, k, s), slope) of a checked call; ValueError
+    otherwise"""
+    if not isinstance(x, torch.Tensor) or not x.is_floating_point():
+        raise ValueError('x must be a float tensor')
+    if x.ndim != 4 or not x.numel():
+        raise ValueError(
+            f'x {tuple(x.shape)}: must be (B, C, H, P) with no empty axis')
+    form = _check_parameters(weight, bias, PERIOD_FORMS, stride)
+    batch, channels, height, period = x.shape
+    if form[0] != channels:
+        raise ValueError(
+            f'x {tuple(x.shape)}: weight {tuple(weight.shape)} takes '
+            f'{form[0]} channels')
+    _check_period(period)
+    slope = _check_slope(slope)
+    if batch * height * period > 2 ** 31 - 1:
+        raise ValueError(f'x {tuple(x.shape)}: more than 2^31 - 1 pixels')
+    return (batch, channels, form[1], height, period, form[2], form[3]), slope
+
+
+def _fold_sizes(audio, weight, bias, period, slope):
+    """((B, T, P), slope) of a checked call; ValueError otherwise"""
+    if not isinstance(audio, torch.Tensor) or not audio.is_floating_point():
+        raise ValueError('audio must be a float tensor')
+    if not (audio.ndim == 2 or (audio.ndim == 3 and audio.shape[1] == 1)) or \
+            not audio.numel():
+        raise ValueError(
+            f'audio {tuple(audio.shape)}: must be (B, 1, T) or (B, T) with '
+            'no empty axis')
+    _check_parameters(weight, bias, PERIOD_FORMS[:1], 3)
+    period = _check_period(period)
+    slope = _check_slope(slope)
+    batch, samples = audio.shape[0], audio.shape[-1]
+    pad = (period - samples % period) % period
+    if samples <= pad:
+        raise ValueError(
+            f'{samples} samples: reflect padding needs more than {pad}')
+    if batch * (samples + pad) > 2 ** 31 - 1:
+        raise ValueError(
+            f'audio {tuple(audio.shape)}: more than 2^31 - 1 pixels')
+    return (batch, samples, period), slope
+
+
+def _workspace_of(size, device):
+    return torch.empty(size, dtype=torch.uint8, device=device)
+
+
+class _PeriodConv(torch.autograd.Function):
+    """backward: gx, gW and gb from the upstream gradient, the saved output
+    and the saved input (pm_pconv_backward)"""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, x, weight, bias, sizes, slope):
+        lib = _lib.lib()
+        batch, _, out_channels, height, period, _, stride = sizes
+        x, weight, bias = _map_order(x), weight.contiguous(), bias.contiguous()
+        y = _empty_map(
+            batch, out_channels, (height - 1) // stride + 1, period, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.pm_pconv_forward(
+                x.data_ptr(), _lib.ptr(weight), _lib.ptr(bias), y.data_ptr(),
+                *sizes, slope, _lib.stream()))
+        ctx.save_for_backward(x, weight, y)
+        ctx.sizes, ctx.slope = sizes, slope
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, grad):
+        lib = _lib.lib()
+        x, weight, y = ctx.saved_tensors
+        sizes = ctx.sizes
+        grad = _map_order(grad.to(torch.float32))
+        need_x, need_weight, need_bias = ctx.needs_input_grad[:3]
+        grad_x = torch.empty_like(x) if need_x else None
+        grad_weight = grad_bias = workspace = None
+        with torch.cuda.device(x.device):
+            if need_weight or need_bias:
+                grad_weight = torch.empty_like(weight)
+                grad_bias = torch.empty(sizes[2], device=x.device)
+                workspace = _workspace_of(
+                    lib.pm_pconv_workspace_bytes(*sizes), x.device)
+            _lib.check(lib.pm_pconv_backward(
+                grad.data_ptr(), y.data_ptr(), x.data_ptr(), _lib.ptr(weight),
+                None if grad_x is None else grad_x.data_ptr(),
+                _lib.ptr(grad_weight), _lib.ptr(grad_bias), *sizes, ctx.slope,
+                None if workspace is None else workspace.data_ptr(),
+                0 if workspace is None else workspace.numel(), _lib.stream()))
+        return (grad_x, grad_weight if need_weight else None,
+                grad_bias if need_bias else None, None, None)
+
+
+class _PeriodFoldConv(torch.autograd.Function):
+    """The first layer on the audio (B, T); backward: the gradient in the
+    audio with the adjoint of the reflection, gW and gb
+    (pm_pconv_fold_backward)"""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, audio, weight, bias, sizes, slope):
+        lib = _lib.lib()
+        batch, samples, period = sizes
+        audio, weight, bias = \
+            audio.contiguous(), weight.contiguous(), bias.contiguous()
+        height = -(-samples // period)
+        y = _empty_map(batch, 32, (height - 1) // 3 + 1, period, audio.device)
+        with torch.cuda.device(audio.device):
+            _lib.check(lib.pm_pconv_fold_forward(
+                _lib.ptr(audio), _lib.ptr(weight), _lib.ptr(bias),
+                y.data_ptr(), *sizes, slope, _lib.stream()))
+        ctx.save_for_backward(audio, weight, y)
+        ctx.sizes, ctx.slope = sizes, slope
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, grad):
+        lib = _lib.lib()
+        audio, weight, y = ctx.saved_tensors
+        sizes = ctx.sizes
+        grad = _map_order(grad.to(torch.float32))
+        need_audio, need_weight, need_bias = ctx.needs_input_grad[:3]
+        grad_audio = torch.empty_like(audio) if need_audio else None
+        grad_weight = grad_bias = workspace = None
+        with torch.cuda.device(audio.device):
+            if need_weight or need_bias:
+                grad_weight = torch.empty_like(weight)
+                grad_bias = torch.empty(32, device=audio.device)
+                workspace = _workspace_of(
+                    lib.pm_pconv_fold_workspace_bytes(*sizes), audio.device)
+            _lib.check(lib.pm_pconv_fold_backward(
+                grad.data_ptr(), y.data_ptr(), _lib.ptr(audio),
+                _lib.ptr(weight), _lib.ptr(grad_audio), _lib.ptr(grad_weight),
+                _lib.ptr(grad_bias), *sizes, ctx.slope,
+                None if workspace is None else workspace.data_ptr(),
+                0 if workspace is None else workspace.numel(), _lib.stream()))
+        return (grad_audio, grad_weight if need_weight else None,
+                grad_bias if need_bias else None, None, None)
+
+
+def period_conv(x, weight, bias, stride=1, slope=1.0):
+    """One layer of DiscriminatorP.convs / conv_post (:57-93) without its
+    weight norm: leaky_relu(conv2d(x, weight, bias, stride (stride, 1),
+    padding ((k - 1) / 2, 0)), slope). x (B, C, H, P) on the device, P the
+    period (1 ... 64), weight (O, C, k, 1), bias (O), with (C, O, k, stride)
+    one of PERIOD_FORMS; slope in (0, 1], 1 being no activation. Returns (B,
+    O, (H - 1) // stride + 1, P) fp32; with more than one channel it is
+    channels_last in memory, as is the gradient in x. Differentiable in x,
+    weight and bias. Other float dtypes are cast to fp32 and their gradients
+    return in their dtype."""
+    sizes, slope = _period_sizes(x, weight, bias, stride, slope)
+    _lib.require_gpu(x)
+    return _PeriodConv.apply(
+        x.to(torch.float32), weight.to(torch.float32),
+        bias.to(torch.float32), sizes, slope)
+
+
+def period_fold_conv(audio, weight, bias, period, slope=1.0):
+    """The first layer of DiscriminatorP on the audio itself: the reference's
+    right reflect pad to a multiple of the period, its view as (B, 1, ceil(T
+    / period), period) and period_conv at (1, 32, 5, 3), without the padded
+    copy. audio (B, 1, T) or (B, T) on the device, weight (32, 1, 5, 1), bias
+    (32). Returns (B, 32, Ho, period) fp32, channels_last. Differentiable in
+    the audio (the gradient has the audio's shape and holds the adjoint of the
+    reflection), weight and bias."""
+    sizes, slope = _fold_sizes(audio, weight, bias, period, slope)
+    _lib.require_gpu(audio)
+    out = _PeriodFoldConv.apply(
+        audio.to(torch.float32).reshape(sizes[0], sizes[1]),
+        weight.to(torch.float32), bias.to(torch.float32), sizes, slope)
+    return out
+
+
+class _NormedPeriodConv(torch.nn.Module):
+    """The parameters of a weight-normed Conv2d(channels, out_channels,
+    (kernel, 1), (stride, 1)), under the names torch.nn.utils.weight_norm
+    gives"""
+
+    def __init__(self, channels, out_channels, kernel, stride):
+        super().__init__()
+        conv = torch.nn.Conv2d(channels, out_channels, (kernel, 1))
+        weight = conv.weight.detach()
+        self.bias = torch.nn.Parameter(conv.bias.detach().clone())
+        self.weight_g = torch.nn.Parameter(
+            weight.flatten(1).norm(dim=1).reshape(-1, 1, 1, 1))
+        self.weight_v = torch.nn.Parameter(weight.clone())
+        self.stride = stride
+
+    def weight(self):
+        return weight_norm(self.weight_g, self.weight_v)
+
+
+class DiscriminatorP(torch.nn.Module):
+    """promonet.model.discriminator.DiscriminatorP (:57-93) on the device:
+    the audio folded by the period, five weight-normed convs along the folded
+    axis under leaky_relu(LRELU_SLOPE), the maps taken after the activation, and a
+    1024 -> 1 conv without activation. The state_dict has the reference's
+    keys and shapes."""
+
+    def __init__(self, period):
+        super().__init__()
+        self.period = _check_period(period)
+        self.convs = torch.nn.ModuleList(
+            [_NormedPeriodConv(*form) for form in PERIOD_FORMS[:5]])
+        self.conv_post = _NormedPeriodConv(*PERIOD_FORMS[5])
+
+    def stack(self, audio):
+        """audio (B, 1, T) -> (logits (B, 1, H, period), the six maps)"""
+        first = self.convs[0]
+        # (refused before the weight norm's device work)
+        _fold_sizes(audio, first.weight_v, first.bias, self.period, 1.)
+        x = period_fold_conv(
+            audio, first.weight(), first.bias, self.period, config.LRELU_SLOPE)
+        maps = [x]
+        for conv in self.convs[1:]:
+            x = period_conv(
+                x, conv.weight(), conv.bias, conv.stride, config.LRELU_SLOPE)
+            maps.append(x)
+        logits = period_conv(
+            x, self.conv_post.weight(), self.conv_post.bias, 1, 1.)
+        maps.append(logits)
+        return logits, maps
+
+    def forward(self, audio):
+        """audio (B, 1, T) -> (logits flattened, the six maps)"""
+        logits, maps = self.stack(audio)
+        return torch.flatten(logits, 1, -1), maps
+
+
+class Discriminator(torch.nn.Module):
+    """promonet.model.discriminator.Discriminator (:13-49) over the members
+    that run on the device, in the reference's order: DiscriminatorP at each
+    of `periods`, DiscriminatorR at each of `resolutions`, DiscriminatorCMB.
+    The defaults are the reference's default configuration, whose checkpoint
+    loads with strict=True."""
+
+    def __init__(self, periods=PERIODS, complex_multiband=True,
+                 resolutions=()):
+        super().__init__()
+        members = [DiscriminatorP(period) for period in periods]
+        members += [DiscriminatorR(resolution) for resolution in resolutions]
+        if complex_multiband:
+            members.append(DiscriminatorCMB())
+        self.discriminators = torch.nn.ModuleList(members)
+
+    def forward(self, y, y_hat, **kwargs):
+        """(logits real, logits fake, maps real, maps fake), a list entry a
+        member"""
+        logits_real, logits_fake, maps_real, maps_fake = [], [], [], []
+        for member in self.discriminators:
+            logits, maps = member(y, **kwargs)
+            logits_real.append(logits)
+            maps_real.append(maps)
+            logits, maps = member(y_hat, **kwargs)
+            logits_fake.append(logits)
+            maps_fake.append(maps)
+        return logits_real, logits_fake, maps_real, maps_fake
+
+
+def _period_form(conv, form):
+    """Is `conv` a weight-normed Conv2d of `form`, the stride and the padding
+    on the height?"""
+    channels, out_channels, kernel, stride = form
+    return isinstance(conv, torch.nn.Conv2d) and conv.bias is not None and \
+        isinstance(getattr(conv, 'weight_g', None), torch.Tensor) and \
+        isinstance(getattr(conv, 'weight_v', None), torch.Tensor) and \
+        conv.in_channels == channels and \
+        conv.out_channels == out_channels and \
+        tuple(conv.kernel_size) == (kernel, 1) and \
+        tuple(conv.stride) == (stride, 1) and \
+        tuple(conv.padding) == ((kernel - 1) // 2, 0) and \
+        tuple(conv.dilation) == (1, 1) and conv.groups == 1 and \
+        conv.padding_mode == 'zeros'
+
+
+def _p_layers(self):
+    """(convs, conv_post, period) of a reference-style DiscriminatorP whose
+    layers are the six PERIOD_FORMS, or None"""
+    try:
+        convs = list(self.convs)
+        period = self.period
+        if len(convs) != 5 or isinstance(period, bool) or \
+                not isinstance(period, int) or not 1 <= period <= 64 or \
+                not all(_period_form(conv, form)
+                        for conv, form in zip(convs, PERIOD_FORMS)) or \
+                not _period_form(self.conv_post, PERIOD_FORMS[5]):
+            return None
+    except (AttributeError, TypeError):
+        return None
+    return convs, self.conv_post, period
+
+
+def _wrap_p_forward(original):
+    def forward(self, x):
+        found = _p_layers(self) if x.is_cuda and x.ndim == 3 and \
+            x.shape[1] == 1 else None
+        if found is None:
+            return original(self, x)
+        convs, post, period = found
+        pad = (period - x.shape[-1] % period) % period
+        if x.shape[-1] <= pad:
+            return original(self, x)
+        x = period_fold_conv(
+            x, _normed(convs[0]), convs[0].bias, period, config.LRELU_SLOPE)
+        maps = [x]
+        for conv in convs[1:]:
+            x = period_conv(
+                x, _normed(conv), conv.bias, conv.stride[0], config.LRELU_SLOPE)
+            maps.append(x)
+        logits = period_conv(x, _normed(post), post.bias, 1, 1.)
+        maps.append(logits)
+        return torch.flatten(logits, 1, -1), maps
+    forward.original = original
+    return forward
+
+
+###############################################################################
 # The wrappers promonet_amd.patch installs
 ###############################################################################
 
@@ -865,7 +1234,10 @@ def patch_module(module):
     of stride 1 with a frequency dilation of 1 ... 16 under the frequency
     embedding, each followed by ReLU or Sigmoid. The `forward` of
     DiscriminatorCMB and of DiscriminatorR is replaced in the same way, where
-    the class has one, for modules whose layers all have one of BAND_FORMS."""
+    the class has one, for modules whose layers all have one of BAND_FORMS,
+    and so is the `forward` of DiscriminatorP for modules whose layers are the
+    six PERIOD_FORMS (a stride or a padding on the other axis goes to the
+    original)."""
     wrappers = {
         'DiscriminatorR': lambda self, x: spectrogram_resolution(
             x, self.resolution),
@@ -885,8 +1257,10 @@ def patch_module(module):
     # DiscriminatorCMB.forward and DiscriminatorR.forward, where the class has
     # one: on the device when every layer is a weight-normed Conv2d of one of
     # BAND_FORMS (in CMB inside Sequential(conv, LeakyReLU)), else the original
+    # and DiscriminatorP.forward for the six PERIOD_FORMS
     for name, wrap in (('DiscriminatorCMB', _wrap_cmb_forward),
-                       ('DiscriminatorR', _wrap_r_forward)):
+                       ('DiscriminatorR', _wrap_r_forward),
+                       ('DiscriminatorP', _wrap_p_forward)):
         cls = getattr(module, name, None)
         forward = getattr(cls, 'forward', None)
         if forward is not None and not hasattr(forward, 'original'):

@@ -12,7 +12,9 @@ SpecDiscriminatorBase; a CPU tensor still takes the target's own method) and
 `SpecDiscriminatorBase.forward`, which runs a stack of weight-normed 3x3 convs
 of stride 1 and 16 channels under the frequency embedding on the device
 (DiscriminatorMagFree at n_fft 64) and leaves every other stack to the
-target's own method.
+target's own method, and the `forward` of DiscriminatorCMB, DiscriminatorR
+and DiscriminatorP, which run their conv stacks on the device where every
+layer has one of the reference's forms.
 """
 import promonet_amd
 
@@ -58,7 +60,8 @@ def patch(promonet):
     # the spectrograms of the spectral discriminators, where the target has
     # them, and SpecDiscriminatorBase.forward for the stacks whose layers the
     # kernels compute (stride 1, 16 channels: DiscriminatorMagFree at n_fft
-    # 64); every other conv stack stays the target's own
+    # 64), and the forward of DiscriminatorCMB / R / P for the reference's
+    # layer forms; every other conv stack stays the target's own
     discriminator = getattr(promonet.model, 'discriminator', None)
     if discriminator is not None:
         promonet_amd.model.discriminator.patch_module(discriminator)
