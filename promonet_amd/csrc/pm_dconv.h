@@ -41,7 +41,7 @@
 //            3 kw taps: 27 accumulators, each MFMA of a step independent of
 //            the other 26; gb is one more accumulator against a column of
 //            ones. A workgroup walks `per` consecutive tiles and writes one
-//            partial (O C 3 kw + O floats) to the workspace; dc_reduce_kernel
+//            partial (O C 3 kw + O floats) to the workspace; dl_reduce_kernel
 //            adds the partials in ascending order in double. Their count and
 //            the tiles of each are a function of the sizes alone: no float
 //            atomics, the same bits on every run.
@@ -51,6 +51,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pm_dlayer.h"
+
 #define DC_THREADS 256
 #define DC_ROWS 4               // output rows of a tile: one a wave
 #define DC_COLS 16              // output columns of a tile
@@ -59,8 +61,7 @@
 #define DC_GW_MAX_PARTS 256     // most partials of the 32 -> 32 gW: 28 MB
 #define DC_EDGE_CHUNK 2048      // fewest pixels of an edge gW workgroup
 #define DC_EDGE_MAX_PARTS 768   // most partials of an edge gW
-
-typedef float dc_f4 __attribute__((ext_vector_type(4)));
+static_assert(DC_THREADS == DL_THREADS, "the workgroup of pm_dlayer.h");
 
 struct DcArgs {
     const float* x;         // (B, H, W, C)
@@ -78,30 +79,9 @@ struct DcArgs {
     int span;               // edge gW: pixels of a workgroup, 16 n
 };
 
-__device__ __forceinline__ float dc_leaky(float v, float slope) {
-    return v > 0.f ? v : v * slope;
-}
-// upstream * leaky'(y): y = 0 takes the slope, as torch does
-__device__ __forceinline__ float dc_gate(float g, float y, float slope) {
-    return y > 0.f ? g : g * slope;
-}
-__device__ __forceinline__ float4 dc_gate4(float4 g, float4 y, float slope) {
-    return make_float4(dc_gate(g.x, y.x, slope), dc_gate(g.y, y.y, slope),
-                       dc_gate(g.z, y.z, slope), dc_gate(g.w, y.w, slope));
-}
-
-#define DC_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0)
-// four K steps: the elements of a lane's 16-byte reads of A and B
-#define DC_MFMA4(acc, a4, b4)                                               \
-    do {                                                                    \
-        acc = DC_MFMA((a4).x, (b4).x, acc);                                 \
-        acc = DC_MFMA((a4).y, (b4).y, acc);                                 \
-        acc = DC_MFMA((a4).z, (b4).z, acc);                                 \
-        acc = DC_MFMA((a4).w, (b4).w, acc);                                 \
-    } while (0)
 // six partial sums in a fixed pairwise order
-__device__ __forceinline__ dc_f4 dc_sum6(dc_f4 a, dc_f4 b, dc_f4 c, dc_f4 d,
-                                         dc_f4 e, dc_f4 f) {
+__device__ __forceinline__ dl_f4 dc_sum6(dl_f4 a, dl_f4 b, dl_f4 c, dl_f4 d,
+                                         dl_f4 e, dl_f4 f) {
     return ((a + b) + (c + d)) + (e + f);
 }
 
@@ -212,12 +192,12 @@ __global__ __launch_bounds__(DC_THREADS) void dc_conv32_kernel(DcArgs a) {
         if (h >= a.H) continue;     // (the whole wave; it meets the barriers)
         // [kh][channel half][o tile]: twelve independent chains of 36 MFMAs,
         // added pairwise at the end: more in flight, and a shorter sum each
-        dc_f4 acc[3][2][2];
+        dl_f4 acc[3][2][2];
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                acc[kh][e >> 1][e & 1] = dc_f4{0.f, 0.f, 0.f, 0.f};
+                acc[kh][e >> 1][e & 1] = dl_f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
 #pragma unroll
@@ -231,29 +211,29 @@ __global__ __launch_bounds__(DC_THREADS) void dc_conv32_kernel(DcArgs a) {
                 const float4 a01 = *(const float4*)(wa + 256);
                 const float4 a10 = *(const float4*)(wa + 512);
                 const float4 a11 = *(const float4*)(wa + 768);
-                DC_MFMA4(acc[kh][0][0], a00, b0);
-                DC_MFMA4(acc[kh][0][1], a10, b0);
-                DC_MFMA4(acc[kh][1][0], a01, b1);
-                DC_MFMA4(acc[kh][1][1], a11, b1);
+                DL_MFMA4(acc[kh][0][0], a00, b0);
+                DL_MFMA4(acc[kh][0][1], a10, b0);
+                DL_MFMA4(acc[kh][1][0], a01, b1);
+                DL_MFMA4(acc[kh][1][1], a11, b1);
             }
         }
-        const dc_f4 acc0 = dc_sum6(acc[0][0][0], acc[0][1][0], acc[1][0][0],
+        const dl_f4 acc0 = dc_sum6(acc[0][0][0], acc[0][1][0], acc[1][0][0],
                                    acc[1][1][0], acc[2][0][0], acc[2][1][0]);
-        const dc_f4 acc1 = dc_sum6(acc[0][0][1], acc[0][1][1], acc[1][0][1],
+        const dl_f4 acc1 = dc_sum6(acc[0][0][1], acc[0][1][1], acc[1][0][1],
                                    acc[1][1][1], acc[2][0][1], acc[2][1][1]);
         if (wo < a.Wo) {
             float* out = a.out +
                 ((long long)(tile.b * a.H + h) * a.Wo + wo) * 32 + 4 * k;
             *(float4*)out = make_float4(
-                dc_leaky(acc0[0] + bias[0][0], a.slope),
-                dc_leaky(acc0[1] + bias[0][1], a.slope),
-                dc_leaky(acc0[2] + bias[0][2], a.slope),
-                dc_leaky(acc0[3] + bias[0][3], a.slope));
+                dl_leaky(acc0[0] + bias[0][0], a.slope),
+                dl_leaky(acc0[1] + bias[0][1], a.slope),
+                dl_leaky(acc0[2] + bias[0][2], a.slope),
+                dl_leaky(acc0[3] + bias[0][3], a.slope));
             *(float4*)(out + 16) = make_float4(
-                dc_leaky(acc1[0] + bias[1][0], a.slope),
-                dc_leaky(acc1[1] + bias[1][1], a.slope),
-                dc_leaky(acc1[2] + bias[1][2], a.slope),
-                dc_leaky(acc1[3] + bias[1][3], a.slope));
+                dl_leaky(acc1[0] + bias[1][0], a.slope),
+                dl_leaky(acc1[1] + bias[1][1], a.slope),
+                dl_leaky(acc1[2] + bias[1][2], a.slope),
+                dl_leaky(acc1[3] + bias[1][3], a.slope));
         }
     }
 }
@@ -308,7 +288,7 @@ __global__ __launch_bounds__(DC_THREADS) void dc_gx32_kernel(DcArgs a) {
             const int idx = threadIdx.x + u * DC_THREADS;
             if (idx < D::GV)
                 *(float4*)(zl + (idx >> 3) * DC_PITCH + 4 * (idx & 7)) =
-                    dc_gate4(gr[u], yr[u], a.slope);
+                    dl_gate4(gr[u], yr[u], a.slope);
         }
         __syncthreads();
         dc_load_gz<KW, S>(a, t + gridDim.x, gr, yr);
@@ -316,14 +296,14 @@ __global__ __launch_bounds__(DC_THREADS) void dc_gx32_kernel(DcArgs a) {
         const int h = tile.h0 + wave;
         if (h >= a.H) continue;
         // [parity][kh][channel half][c tile], as in the forward
-        dc_f4 part[S][3][2][2];
+        dl_f4 part[S][3][2][2];
 #pragma unroll
         for (int p = 0; p < S; ++p)
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    part[p][kh][e >> 1][e & 1] = dc_f4{0.f, 0.f, 0.f, 0.f};
+                    part[p][kh][e >> 1][e & 1] = dl_f4{0.f, 0.f, 0.f, 0.f};
         constexpr int STEPS = S == 2 ? 5 : KW;
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
@@ -343,14 +323,14 @@ __global__ __launch_bounds__(DC_THREADS) void dc_gx32_kernel(DcArgs a) {
                     const float4 a01 = *(const float4*)(wa + 256);
                     const float4 a10 = *(const float4*)(wa + 512);
                     const float4 a11 = *(const float4*)(wa + 768);
-                    DC_MFMA4(part[p][kh][0][0], a00, b0);
-                    DC_MFMA4(part[p][kh][0][1], a10, b0);
-                    DC_MFMA4(part[p][kh][1][0], a01, b1);
-                    DC_MFMA4(part[p][kh][1][1], a11, b1);
+                    DL_MFMA4(part[p][kh][0][0], a00, b0);
+                    DL_MFMA4(part[p][kh][0][1], a10, b0);
+                    DL_MFMA4(part[p][kh][1][0], a01, b1);
+                    DL_MFMA4(part[p][kh][1][1], a11, b1);
                 }
             }
         }
-        dc_f4 acc[S][2];
+        dl_f4 acc[S][2];
 #pragma unroll
         for (int p = 0; p < S; ++p)
 #pragma unroll
@@ -409,9 +389,9 @@ __global__ __launch_bounds__(DC_THREADS) void dc_gw32_kernel(DcArgs a) {
     float* zl = dc_lds + (DC_ROWS + 2) * D::NP * DC_PITCH;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, k = lane >> 4, m = wave >> 1, n = wave & 1;
-    dc_f4 acc[TAPS], accb = {0.f, 0.f, 0.f, 0.f};
+    dl_f4 acc[TAPS], accb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) acc[tap] = dc_f4{0.f, 0.f, 0.f, 0.f};
+    for (int tap = 0; tap < TAPS; ++tap) acc[tap] = dl_f4{0.f, 0.f, 0.f, 0.f};
 
     const int first = blockIdx.x * a.per;
     const int last = first + a.per < a.tiles ? first + a.per : a.tiles;
@@ -425,7 +405,7 @@ __global__ __launch_bounds__(DC_THREADS) void dc_gw32_kernel(DcArgs a) {
         for (int u = 0; u < D::ZL; ++u) {
             const int idx = threadIdx.x + u * DC_THREADS;
             *(float4*)(zl + (idx >> 3) * DC_PITCH + 4 * (idx & 7)) =
-                dc_gate4(gr[u], yr[u], a.slope);
+                dl_gate4(gr[u], yr[u], a.slope);
         }
         __syncthreads();
         if (t + 1 < last) {
@@ -441,10 +421,10 @@ __global__ __launch_bounds__(DC_THREADS) void dc_gw32_kernel(DcArgs a) {
             for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
                 for (int kw = 0; kw < KW; ++kw)
-                    acc[kh * KW + kw] = DC_MFMA(
+                    acc[kh * KW + kw] = DL_MFMA(
                         gz, px[(kh * D::NP + kw) * DC_PITCH],
                         acc[kh * KW + kw]);
-            if (n == 0) accb = DC_MFMA(gz, 1.f, accb);
+            if (n == 0) accb = DL_MFMA(gz, 1.f, accb);
         }
     }
     // rows o = 16 m + 4 k + r, column c = 16 n + j: every float of the partial
@@ -462,69 +442,10 @@ __global__ __launch_bounds__(DC_THREADS) void dc_gw32_kernel(DcArgs a) {
             part[TAPS * 1024 + 16 * m + 4 * k + r] = accb[r];
 }
 
-// gW | gb = the partials added in a fixed order, in double: 64 entries a
-// workgroup, each wave a quarter of the partials in ascending order (eight
-// loads in flight), then the four waves in order
-__global__ __launch_bounds__(DC_THREADS) void dc_reduce_kernel(
-    const float* __restrict__ parts, int nparts, int n, int weights,
-    float* __restrict__ grad_weight, float* __restrict__ grad_bias) {
-    __shared__ double lds[DC_THREADS / 64][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + lane;
-    const int per = (nparts + DC_THREADS / 64 - 1) / (DC_THREADS / 64);
-    const int first = wave * per;
-    const int last = first + per < nparts ? first + per : nparts;
-    double sum = 0.;
-    if (e < n) {
-        int i = first;
-        for (; i + 8 <= last; i += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = parts[(long long)(i + u) * n + e];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) sum += (double)v[u];
-        }
-        for (; i < last; ++i) sum += (double)parts[(long long)i * n + e];
-    }
-    lds[wave][lane] = sum;
-    __syncthreads();
-    if (wave != 0 || e >= n) return;
-    for (int w = 1; w < DC_THREADS / 64; ++w) sum += lds[w][lane];
-    if (e < weights) grad_weight[e] = (float)sum;
-    else grad_bias[e - weights] = (float)sum;
-}
-
 // ---------------------------------------------------------------------------
 // The edge layers, stride 1: the output pixel p = (b H + h) W + w is the input
-// pixel, and tap (kh, kw) is the pixel p + (kh - 1) W + (kw - PAD) where its
-// (h, w) lies inside the map. 32-bit pixel arithmetic: the host refuses more
-// than 2^31 - 1 pixels.
+// pixel, and tap (kh, kw) is the tap (kh - 1, kw - PAD) of DlPixel.
 // ---------------------------------------------------------------------------
-struct DcPixel {
-    int h, w;
-    __device__ __forceinline__ DcPixel(long long p, int H, int W) {
-        const unsigned row = (unsigned)p / (unsigned)W;
-        w = (int)((unsigned)p - row * (unsigned)W);
-        h = (int)(row % (unsigned)H);
-    }
-    __device__ __forceinline__ void advance(int n, int H, int W) {
-        w += n;
-        while (w >= W) {
-            w -= W;
-            if (++h == H) h = 0;
-        }
-    }
-    // is the pixel (h + sign (kh - 1), w + sign (kw - pad)) inside?
-    __device__ __forceinline__ bool inside(int kh, int kw, int pad, int H,
-                                           int W, int sign = 1) const {
-        const int hh = h + sign * (kh - 1), ww = w + sign * (kw - pad);
-        return hh >= 0 && hh < H && ww >= 0 && ww < W;
-    }
-};
-__device__ __forceinline__ long long dc_offset(int kh, int kw, int pad, int W) {
-    return (long long)(kh - 1) * W + (kw - pad);
-}
-
 // W (O, C, 3, KW) with O C = 32 to LDS as [tap][32]
 template <int TAPS>
 __device__ __forceinline__ void dc_stage_edge(const float* __restrict__ w,
@@ -542,14 +463,14 @@ __global__ __launch_bounds__(DC_THREADS) void dc_conv_c1_kernel(DcArgs a) {
     if (i >= a.P * 8) return;
     const long long p = i >> 3;
     const int q = (int)(i & 7);
-    const DcPixel px(p, a.H, a.W);
+    const DlPixel px(p, a.H, a.W);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
         for (int kw = 0; kw < 9; ++kw) {
-            if (!px.inside(kh, kw, 4, a.H, a.W)) continue;
-            const float v = a.x[p + dc_offset(kh, kw, 4, a.W)];
+            if (!px.inside(kh - 1, kw - 4, a.H, a.W)) continue;
+            const float v = a.x[p + dl_offset(kh - 1, kw - 4, a.W)];
             const float4 w = *(const float4*)(wl + (kh * 9 + kw) * 32 + 4 * q);
             acc.x = fmaf(w.x, v, acc.x);
             acc.y = fmaf(w.y, v, acc.y);
@@ -558,8 +479,8 @@ __global__ __launch_bounds__(DC_THREADS) void dc_conv_c1_kernel(DcArgs a) {
         }
     const float4 bias = *(const float4*)(a.bias + 4 * q);
     *(float4*)(a.out + p * 32 + 4 * q) = make_float4(
-        dc_leaky(acc.x + bias.x, a.slope), dc_leaky(acc.y + bias.y, a.slope),
-        dc_leaky(acc.z + bias.z, a.slope), dc_leaky(acc.w + bias.w, a.slope));
+        dl_leaky(acc.x + bias.x, a.slope), dl_leaky(acc.y + bias.y, a.slope),
+        dl_leaky(acc.z + bias.z, a.slope), dl_leaky(acc.w + bias.w, a.slope));
 }
 
 // 1 -> 32, input gradient: one pixel a thread
@@ -568,17 +489,17 @@ __global__ __launch_bounds__(DC_THREADS) void dc_gx_c1_kernel(DcArgs a) {
     dc_stage_edge<27>(a.w, wl);
     const long long p = (long long)blockIdx.x * DC_THREADS + threadIdx.x;
     if (p >= a.P) return;
-    const DcPixel px(p, a.H, a.W);
+    const DlPixel px(p, a.H, a.W);
     // (four chains of 216 terms, added pairwise: a shorter sum each)
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int kh = 0; kh < 3; ++kh)
         for (int kw = 0; kw < 9; ++kw) {
-            if (!px.inside(kh, kw, 4, a.H, a.W, -1)) continue;
-            const long long at = (p - dc_offset(kh, kw, 4, a.W)) * 32;
+            if (!px.inside(kh - 1, kw - 4, a.H, a.W, -1)) continue;
+            const long long at = (p - dl_offset(kh - 1, kw - 4, a.W)) * 32;
             const float* w = wl + (kh * 9 + kw) * 32;
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const float4 gz = dc_gate4(*(const float4*)(a.g + at + 4 * q),
+                const float4 gz = dl_gate4(*(const float4*)(a.g + at + 4 * q),
                                            *(const float4*)(a.y + at + 4 * q),
                                            a.slope);
                 const float4 u = *(const float4*)(w + 4 * q);
@@ -597,15 +518,15 @@ __global__ __launch_bounds__(DC_THREADS) void dc_conv_o1_kernel(DcArgs a) {
     dc_stage_edge<9>(a.w, wl);
     const long long p = (long long)blockIdx.x * DC_THREADS + threadIdx.x;
     if (p >= a.P) return;
-    const DcPixel px(p, a.H, a.W);
+    const DlPixel px(p, a.H, a.W);
     // (four chains of 72 terms, added pairwise)
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
-            if (!px.inside(kh, kw, 1, a.H, a.W)) continue;
-            const float* v = a.x + (p + dc_offset(kh, kw, 1, a.W)) * 32;
+            if (!px.inside(kh - 1, kw - 1, a.H, a.W)) continue;
+            const float* v = a.x + (p + dl_offset(kh - 1, kw - 1, a.W)) * 32;
             const float* w = wl + (kh * 3 + kw) * 32;
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
@@ -617,7 +538,7 @@ __global__ __launch_bounds__(DC_THREADS) void dc_conv_o1_kernel(DcArgs a) {
                 acc.w = fmaf(c.w, u.w, acc.w);
             }
         }
-    a.out[p] = dc_leaky(
+    a.out[p] = dl_leaky(
         ((acc.x + acc.y) + (acc.z + acc.w)) + a.bias[0], a.slope);
 }
 
@@ -629,15 +550,15 @@ __global__ __launch_bounds__(DC_THREADS) void dc_gx_o1_kernel(DcArgs a) {
     if (i >= a.P * 8) return;
     const long long p = i >> 3;
     const int q = (int)(i & 7);
-    const DcPixel px(p, a.H, a.W);
+    const DlPixel px(p, a.H, a.W);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
-            if (!px.inside(kh, kw, 1, a.H, a.W, -1)) continue;
-            const long long at = p - dc_offset(kh, kw, 1, a.W);
-            const float gz = dc_gate(a.g[at], a.y[at], a.slope);
+            if (!px.inside(kh - 1, kw - 1, a.H, a.W, -1)) continue;
+            const long long at = p - dl_offset(kh - 1, kw - 1, a.W);
+            const float gz = dl_gate(a.g[at], a.y[at], a.slope);
             const float4 w = *(const float4*)(wl + (kh * 3 + kw) * 32 + 4 * q);
             acc.x = fmaf(w.x, gz, acc.x);
             acc.y = fmaf(w.y, gz, acc.y);
@@ -676,69 +597,47 @@ template <int O>
 __global__ __launch_bounds__(DC_THREADS) void dc_gw_edge_kernel(DcArgs a) {
     typedef DcEdgeGw<O> G;
     constexpr int NM = G::NM, PAD = O == 32 ? 4 : 1, KW = O == 32 ? 9 : 3;
-    __shared__ float lds[DC_THREADS / 64][NM][4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, k = lane >> 4;
-    dc_f4 acc[NM];
+    dl_f4 acc[NM];
 #pragma unroll
-    for (int m = 0; m < NM; ++m) acc[m] = dc_f4{0.f, 0.f, 0.f, 0.f};
-    {
-        const long long begin =
-            (long long)blockIdx.x * a.span + wave * (a.span / 4);
-        const long long left = a.P - begin;
-        const int steps = left <= 0 ? 0
-            : (int)(left < a.span / 4 ? (left + 3) / 4 : a.span / 16);
-        DcPixel px(begin + k < a.P ? begin + k : 0, a.H, a.W);
-        for (int step = 0; step < steps; ++step, px.advance(4, a.H, a.W)) {
-            const long long p = begin + step * 4 + k;
-            const bool live = p < a.P;
-            if (O == 32) {
-                float gz0 = 0.f, gz1 = 0.f;
-                if (live) {
-                    gz0 = dc_gate(a.g[p * 32 + j], a.y[p * 32 + j], a.slope);
-                    gz1 = dc_gate(a.g[p * 32 + 16 + j], a.y[p * 32 + 16 + j],
-                                  a.slope);
-                }
-#pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    const int idx = 16 * n + j;
-                    float v = 0.f;
-                    if (live && idx == 27) v = 1.f;
-                    else if (live && idx < 27 &&
-                             px.inside(idx / 9, idx % 9, PAD, a.H, a.W))
-                        v = a.x[p + dc_offset(idx / 9, idx % 9, PAD, a.W)];
-                    acc[n] = DC_MFMA(gz0, v, acc[n]);
-                    acc[2 + n] = DC_MFMA(gz1, v, acc[2 + n]);
-                }
-            } else {
-                float gz = 0.f;
-                if (live && j < 9 &&
-                    px.inside(j / KW, j % KW, PAD, a.H, a.W, -1)) {
-                    const long long at = p - dc_offset(j / KW, j % KW, PAD, a.W);
-                    gz = dc_gate(a.g[at], a.y[at], a.slope);
-                }
-                const float x0 = live ? a.x[p * 32 + j] : 0.f;
-                const float x1 = live ? a.x[p * 32 + 16 + j] : 0.f;
-                acc[0] = DC_MFMA(x0, gz, acc[0]);
-                acc[1] = DC_MFMA(x1, gz, acc[1]);
-                acc[2] = DC_MFMA(j == 0 ? 1.f : 0.f, gz, acc[2]);
+    for (int m = 0; m < NM; ++m) acc[m] = dl_f4{0.f, 0.f, 0.f, 0.f};
+    const auto [begin, steps] = dl_gw_span(a.P, a.span, wave);
+    DlPixel px(begin + k < a.P ? begin + k : 0, a.H, a.W);
+    for (int step = 0; step < steps; ++step, px.advance(4, a.H, a.W)) {
+        const long long p = begin + step * 4 + k;
+        const bool live = p < a.P;
+        if (O == 32) {
+            float gz0 = 0.f, gz1 = 0.f;
+            if (live) {
+                gz0 = dl_gate(a.g[p * 32 + j], a.y[p * 32 + j], a.slope);
+                gz1 = dl_gate(a.g[p * 32 + 16 + j], a.y[p * 32 + 16 + j],
+                              a.slope);
             }
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                const int idx = 16 * n + j;
+                const int dh = idx / 9 - 1, dw = idx % 9 - PAD;
+                float v = 0.f;
+                if (live && idx == 27) v = 1.f;
+                else if (live && idx < 27 && px.inside(dh, dw, a.H, a.W))
+                    v = a.x[p + dl_offset(dh, dw, a.W)];
+                acc[n] = DL_MFMA(gz0, v, acc[n]);
+                acc[2 + n] = DL_MFMA(gz1, v, acc[2 + n]);
+            }
+        } else {
+            const int dh = j / KW - 1, dw = j % KW - PAD;
+            float gz = 0.f;
+            if (live && j < 9 && px.inside(dh, dw, a.H, a.W, -1)) {
+                const long long at = p - dl_offset(dh, dw, a.W);
+                gz = dl_gate(a.g[at], a.y[at], a.slope);
+            }
+            const float x0 = live ? a.x[p * 32 + j] : 0.f;
+            const float x1 = live ? a.x[p * 32 + 16 + j] : 0.f;
+            acc[0] = DL_MFMA(x0, gz, acc[0]);
+            acc[1] = DL_MFMA(x1, gz, acc[1]);
+            acc[2] = DL_MFMA(j == 0 ? 1.f : 0.f, gz, acc[2]);
         }
     }
-    // the four waves, added in order; every float of the partial is written
-    // by exactly one thread
-#pragma unroll
-    for (int m = 0; m < NM; ++m)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lds[wave][m][r][lane] = acc[m][r];
-    __syncthreads();
-    float* part = a.parts + (long long)blockIdx.x * G::N;
-    for (int e = threadIdx.x; e < NM * 256; e += DC_THREADS) {
-        const int m = e >> 8, r = (e >> 6) & 3, l = e & 63;
-        const int slot = G::slot(m, 4 * (l >> 4) + r, l & 15);
-        if (slot < 0) continue;
-        float sum = lds[0][m][r][l];
-        for (int w = 1; w < DC_THREADS / 64; ++w) sum += lds[w][m][r][l];
-        part[slot] = sum;
-    }
+    dl_gw_store<G>(acc, a.parts);
 }

@@ -4,8 +4,6 @@
 // before the first HIP call, so the checks answer on a machine without a GPU.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-
 #include "pm_dconv.h"
 #include "pm_host.h"
 
@@ -47,26 +45,12 @@ const char* check_layer(int batch, int channels, int out_channels, int height,
     return nullptr;
 }
 
-const char* check_slope(float slope) {
-    // (on the bits, as one integer range: this file is compiled with
-    // -fno-honor-nans, which lets the compiler drop any test that only NaN
-    // fails; the positive floats are ordered as their bits are, 1.f being
-    // 0x3f800000)
-    uint32_t bits;
-    std::memcpy(&bits, &slope, sizeof bits);
-    if (bits - 1u > 0x3f800000u - 1u)
-        return "slope must be finite and in (0, 1]";
-    return nullptr;
-}
-
-int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 // The tiles of the 32 -> 32 kernels over a map `columns` wide
 struct Tiles { int tiles, tiles_h, tiles_w; };
 Tiles tiles_of(const Sizes& z, int columns, int tile_columns) {
     Tiles t;
-    t.tiles_h = ceil_div(z.H, DC_ROWS);
-    t.tiles_w = ceil_div(columns, tile_columns);
+    t.tiles_h = (int)pm_ceil_div(z.H, DC_ROWS);
+    t.tiles_w = (int)pm_ceil_div(columns, tile_columns);
     t.tiles = z.B * t.tiles_h * t.tiles_w;
     return t;
 }
@@ -74,19 +58,15 @@ Tiles tiles_of(const Sizes& z, int columns, int tile_columns) {
 // The partials of gW and gb, one a workgroup, and what each takes: tiles (32
 // -> 32) or pixels, a multiple of 16 (the edges). A function of the sizes
 // alone.
-struct Split { int parts, each; };
-Split split_of(const Sizes& z) {
+PmSplit split_of(const Sizes& z) {
     if (z.wide()) {
         const int tiles = tiles_of(z, z.Wo, DC_COLS).tiles;
-        int want = ceil_div(tiles, DC_GW_MIN_TILES);
+        int want = (int)pm_ceil_div(tiles, DC_GW_MIN_TILES);
         if (want > DC_GW_MAX_PARTS) want = DC_GW_MAX_PARTS;
-        const int each = ceil_div(tiles, want);
-        return {ceil_div(tiles, each), each};
+        const int each = (int)pm_ceil_div(tiles, want);
+        return {(int)pm_ceil_div(tiles, each), each};
     }
-    long long want = (z.out_pixels + DC_EDGE_CHUNK - 1) / DC_EDGE_CHUNK;
-    if (want > DC_EDGE_MAX_PARTS) want = DC_EDGE_MAX_PARTS;
-    const int each = (int)(((z.out_pixels + want - 1) / want + 15) / 16 * 16);
-    return {ceil_div(z.out_pixels, each), each};
+    return pm_pixel_split(z.out_pixels, DC_EDGE_CHUNK, DC_EDGE_MAX_PARTS);
 }
 
 // backward: the partials
@@ -95,10 +75,6 @@ DcLayout backward_layout(const Sizes& z, void* base) {
     PmCarve c(base);
     return {c.take<float>((size_t)split_of(z).parts * z.partial_floats()),
             c.used};
-}
-
-unsigned groups(long long threads) {
-    return (unsigned)((threads + DC_THREADS - 1) / DC_THREADS);
 }
 
 unsigned walked(int tiles) {
@@ -153,7 +129,7 @@ int launch_gw32(DcArgs a, const Sizes& z, hipStream_t s) {
     auto kern = dc_gw32_kernel<KW, S>;
     PM_HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
     set_tiles(a, tiles_of(z, z.Wo, DC_COLS));
-    const Split split = split_of(z);
+    const PmSplit split = split_of(z);
     a.per = split.each;
     hipLaunchKernelGGL(kern, dim3(split.parts), dim3(DC_THREADS), lds, s, a);
     PM_HIP_TRY(hipGetLastError());
@@ -182,7 +158,7 @@ extern "C" int pm_dconv_forward(const float* x, const float* weight,
     if (const char* why = check_layer(batch, channels, out_channels, height,
                                       width, kernel_width, stride, &z))
         return pm_fail(PM_EINVAL, "pm_dconv_forward: %s", why);
-    if (const char* why = check_slope(slope))
+    if (const char* why = pm_check_slope(slope))
         return pm_fail(PM_EINVAL, "pm_dconv_forward: %s", why);
     if (!x || !weight || !bias || !y)
         return pm_fail(PM_EINVAL, "pm_dconv_forward: null argument");
@@ -193,10 +169,12 @@ extern "C" int pm_dconv_forward(const float* x, const float* weight,
         return z.KW == 9 ? launch_conv32<9, 2>(a, z, s)
                          : launch_conv32<3, 1>(a, z, s);
     if (z.O == 1)
-        hipLaunchKernelGGL(dc_conv_o1_kernel, dim3(groups(a.P)),
-                           dim3(DC_THREADS), 0, s, a);
+        hipLaunchKernelGGL(dc_conv_o1_kernel,
+                           dim3(pm_groups(a.P, DC_THREADS)), dim3(DC_THREADS),
+                           0, s, a);
     else
-        hipLaunchKernelGGL(dc_conv_c1_kernel, dim3(groups(a.P * 8)),
+        hipLaunchKernelGGL(dc_conv_c1_kernel,
+                           dim3(pm_groups(a.P * 8, DC_THREADS)),
                            dim3(DC_THREADS), 0, s, a);
     PM_HIP_TRY(hipGetLastError());
     return PM_OK;
@@ -212,15 +190,13 @@ extern "C" int pm_dconv_backward(
     if (const char* why = check_layer(batch, channels, out_channels, height,
                                       width, kernel_width, stride, &z))
         return pm_fail(PM_EINVAL, "pm_dconv_backward: %s", why);
-    if (const char* why = check_slope(slope))
+    if (const char* why = pm_check_slope(slope))
         return pm_fail(PM_EINVAL, "pm_dconv_backward: %s", why);
-    const bool weights = grad_weight || grad_bias;
-    if (!upstream || !y || !x || !weight ||
-        (weights && (!grad_weight || !grad_bias || !workspace)))
-        return pm_fail(PM_EINVAL, "pm_dconv_backward: null argument");
     const DcLayout l = backward_layout(z, workspace);
-    if (weights && workspace_bytes < l.total)
-        return pm_fail(PM_ENOMEM, "pm_dconv_backward: workspace too small");
+    if (const int code = pm_check_backward(
+            "pm_dconv_backward", upstream && y && x && weight, grad_weight,
+            grad_bias, workspace, workspace_bytes, l.total))
+        return code;
     DcArgs a = args_of(z, slope);
     a.x = x; a.w = weight; a.g = upstream; a.y = y;
     hipStream_t s = (hipStream_t)stream;
@@ -233,17 +209,19 @@ extern "C" int pm_dconv_backward(
             if (code != PM_OK) return code;
         } else {
             if (z.O == 1)
-                hipLaunchKernelGGL(dc_gx_o1_kernel, dim3(groups(a.P * 8)),
-                                   block, 0, s, a);
-            else
-                hipLaunchKernelGGL(dc_gx_c1_kernel, dim3(groups(a.P)), block,
+                hipLaunchKernelGGL(dc_gx_o1_kernel,
+                                   dim3(pm_groups(a.P * 8, DC_THREADS)), block,
                                    0, s, a);
+            else
+                hipLaunchKernelGGL(dc_gx_c1_kernel,
+                                   dim3(pm_groups(a.P, DC_THREADS)), block, 0,
+                                   s, a);
             PM_HIP_TRY(hipGetLastError());
         }
     }
-    if (weights) {
+    if (grad_weight) {      // (and grad_bias: pm_check_backward)
         a.parts = l.parts;
-        const Split split = split_of(z);
+        const PmSplit split = split_of(z);
         if (z.wide()) {
             const int code = z.KW == 9 ? launch_gw32<9, 2>(a, z, s)
                                        : launch_gw32<3, 1>(a, z, s);
@@ -258,11 +236,8 @@ extern "C" int pm_dconv_backward(
                                    block, 0, s, a);
             PM_HIP_TRY(hipGetLastError());
         }
-        const int n = z.partial_floats();
-        hipLaunchKernelGGL(dc_reduce_kernel, dim3((n + 63) / 64), block, 0, s,
-                           (const float*)l.parts, split.parts, n, n - z.O,
-                           grad_weight, grad_bias);
-        PM_HIP_TRY(hipGetLastError());
+        PM_HIP_TRY(dl_reduce(l.parts, split.parts, z.partial_floats(), z.O,
+                             grad_weight, grad_bias, s));
     }
     return PM_OK;
 }

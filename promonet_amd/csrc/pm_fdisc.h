@@ -26,11 +26,13 @@
 // with the flipped, transposed weight of the first C channels. gW (O, C + 2,
 // 3, 3) and gb (O) are sums over all pixels: a workgroup accumulates its
 // pixels in MFMA tiles (K = pixels), its four waves are added in order, the
-// partial goes to the workspace, and fd_reduce_kernel adds the partials in a
-// fixed order in double. Their count and the pixels of each are a function of
-// the sizes alone: no float atomics, the same bits on every run.
+// partial goes to the workspace, and dl_reduce_kernel (pm_dlayer.h) adds the
+// partials in a fixed order in double. Their count and the pixels of each are
+// a function of the sizes alone: no float atomics, the same bits on every run.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "pm_dlayer.h"
 
 #define FD_NONE 0
 #define FD_RELU 1
@@ -41,8 +43,7 @@
 #define FD_CONV_PIXELS (FD_THREADS / 64 * FD_WAVE_TILES * 16)   // a workgroup
 #define FD_GW_CHUNK 2048        // fewest pixels of a gW workgroup (but the last)
 #define FD_GW_MAX_PARTS 768     // most partials of gW and gb: three a CU
-
-typedef float fd_f4 __attribute__((ext_vector_type(4)));
+static_assert(FD_THREADS == DL_THREADS, "the workgroup of pm_dlayer.h");
 
 struct FdArgs {
     const float* x;         // (B, F, T, C)
@@ -58,35 +59,19 @@ struct FdArgs {
     int span;               // backward: pixels of a gW workgroup, 16 n
 };
 
-// A pixel of the flattened map, and where its taps fall. 32-bit arithmetic:
-// the host refuses more than 2^31 - 1 pixels (a 64-bit division a pixel cost
-// more than the MFMAs of a gW step).
-struct FdPixel {
-    int f, t;
-    __device__ __forceinline__ FdPixel(long long p, int F, int T) {
-        const unsigned row = (unsigned)p / (unsigned)T;
-        t = (int)((unsigned)p - row * (unsigned)T);
-        f = (int)(row % (unsigned)F);
-    }
-    // the pixel n (< 2^16) further on
-    __device__ __forceinline__ void advance(int n, int F, int T) {
-        t += n;
-        while (t >= T) {
-            t -= T;
-            if (++f == F) f = 0;
-        }
-    }
-    // the frequency of tap `tap` (kf = tap / 3, kt = tap % 3), or -1 outside.
-    // SIGN = -1 mirrors the tap (the input gradient reads gz at p - offset)
-    __device__ __forceinline__ int tap_f(int tap, int d, int F, int T,
-                                         int sign = 1) const {
-        const int ff = f + sign * (tap / 3 - 1) * d;
-        const int tt = t + sign * (tap % 3 - 1);
-        return (ff >= 0 && ff < F && tt >= 0 && tt < T) ? ff : -1;
-    }
-};
+// The taps of a pixel of the flattened map (DlPixel, h the frequency and w the
+// frame): the frequency of tap `tap` (kf = tap / 3, kt = tap % 3), or -1
+// outside, which the embedding table needs. SIGN = -1 mirrors the tap (the
+// input gradient reads gz at p - offset). DlPixel::inside's test with the row
+// kept, in the order that leaves fd_conv16_kernel's machine code as it was.
+__device__ __forceinline__ int fd_tap_f(const DlPixel& px, int tap, int d,
+                                        int F, int T, int sign = 1) {
+    const int ff = px.h + sign * (tap / 3 - 1) * d;
+    const int tt = px.w + sign * (tap % 3 - 1);
+    return (ff >= 0 && ff < F && tt >= 0 && tt < T) ? ff : -1;
+}
 __device__ __forceinline__ long long fd_tap_offset(int tap, int d, int T) {
-    return (long long)(tap / 3 - 1) * d * T + (tap % 3 - 1);
+    return dl_offset((long long)(tap / 3 - 1) * d, tap % 3 - 1, T);
 }
 
 __device__ __forceinline__ float fd_activate(float v, int act) {
@@ -149,12 +134,12 @@ __global__ __launch_bounds__(FD_THREADS) void fd_conv16_kernel(FdArgs a) {
         const long long p = first + tile * 16 + col;
         if (first + tile * 16 >= a.P) break;        // (the whole wave leaves)
         const bool live = p < a.P;
-        const FdPixel px(live ? p : 0, a.F, a.T);
-        fd_f4 acc = {0.f, 0.f, 0.f, 0.f};
+        const DlPixel px(live ? p : 0, a.F, a.T);
+        dl_f4 acc = {0.f, 0.f, 0.f, 0.f};
         if (C == 16) {
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
-                const int ff = px.tap_f(tap, a.d, a.F, a.T);
+                const int ff = fd_tap_f(px, tap, a.d, a.F, a.T);
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (live && ff >= 0) {
                     const long long at =
@@ -185,7 +170,7 @@ __global__ __launch_bounds__(FD_THREADS) void fd_conv16_kernel(FdArgs a) {
                 for (int s = 0; s < 5; ++s) {
                     const int tap = 2 * s + (k >> 1);
                     const int ff =
-                        tap < 9 ? px.tap_f(tap, a.d, a.F, a.T) : -1;
+                        tap < 9 ? fd_tap_f(px, tap, a.d, a.F, a.T) : -1;
                     const float v = (live && ff >= 0)
                         ? a.table[2 * ff + (k & 1)] : 0.f;
                     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(
@@ -195,7 +180,7 @@ __global__ __launch_bounds__(FD_THREADS) void fd_conv16_kernel(FdArgs a) {
         } else {
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
-                const int ff = px.tap_f(tap, a.d, a.F, a.T);
+                const int ff = fd_tap_f(px, tap, a.d, a.F, a.T);
                 float v = 0.f;
                 if (live && ff >= 0 && k < 3)
                     v = k == 0 ? a.x[p + fd_tap_offset(tap, a.d, a.T)]
@@ -225,11 +210,11 @@ __global__ __launch_bounds__(FD_THREADS) void fd_conv16_kernel(FdArgs a) {
 __global__ __launch_bounds__(FD_THREADS) void fd_conv_o1_kernel(FdArgs a) {
     const long long p = (long long)blockIdx.x * FD_THREADS + threadIdx.x;
     if (p >= a.P) return;
-    const FdPixel px(p, a.F, a.T);
+    const DlPixel px(p, a.F, a.T);
     float acc = 0.f;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
-        const int ff = px.tap_f(tap, a.d, a.F, a.T);
+        const int ff = fd_tap_f(px, tap, a.d, a.F, a.T);
         if (ff < 0) continue;
         const float4* v =
             (const float4*)(a.x + (p + fd_tap_offset(tap, a.d, a.T)) * 16);
@@ -253,11 +238,11 @@ __global__ __launch_bounds__(FD_THREADS) void fd_gx_o1_kernel(FdArgs a) {
     if (i >= a.P * 4) return;
     const long long p = i >> 2;
     const int q = (int)(i & 3);
-    const FdPixel px(p, a.F, a.T);
+    const DlPixel px(p, a.F, a.T);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
-        if (px.tap_f(tap, a.d, a.F, a.T, -1) < 0) continue;
+        if (fd_tap_f(px, tap, a.d, a.F, a.T, -1) < 0) continue;
         const long long at = p - fd_tap_offset(tap, a.d, a.T);
         const float gz = fd_gate(a.g[at], a.y[at], a.act);
         acc.x = fmaf(a.w[(4 * q + 0) * 9 + tap], gz, acc.x);
@@ -272,11 +257,11 @@ __global__ __launch_bounds__(FD_THREADS) void fd_gx_o1_kernel(FdArgs a) {
 __global__ __launch_bounds__(FD_THREADS) void fd_gx_c1_kernel(FdArgs a) {
     const long long p = (long long)blockIdx.x * FD_THREADS + threadIdx.x;
     if (p >= a.P) return;
-    const FdPixel px(p, a.F, a.T);
+    const DlPixel px(p, a.F, a.T);
     float acc = 0.f;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
-        if (px.tap_f(tap, a.d, a.F, a.T, -1) < 0) continue;
+        if (fd_tap_f(px, tap, a.d, a.F, a.T, -1) < 0) continue;
         const long long at = (p - fd_tap_offset(tap, a.d, a.T)) * 16;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -329,126 +314,69 @@ template <int C, int O>
 __global__ __launch_bounds__(FD_THREADS) void fd_gw_kernel(FdArgs a) {
     typedef FdGw<C, O> G;
     constexpr int NM = G::NM;
-    __shared__ float lds[FD_THREADS / 64][NM][4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, k = lane >> 4;
-    fd_f4 acc[NM];
+    dl_f4 acc[NM];
 #pragma unroll
-    for (int m = 0; m < NM; ++m) acc[m] = fd_f4{0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < NM; ++m) acc[m] = dl_f4{0.f, 0.f, 0.f, 0.f};
 
-    // pixels blockIdx.x * span ... + span; a wave takes a quarter
-    {
-        const long long begin =
-            (long long)blockIdx.x * a.span + wave * (a.span / 4);
-        // steps of four pixels, the same for every lane of the wave; a lane
-        // beyond the last pixel stays beyond it
-        const long long left = a.P - begin;
-        const int steps = left <= 0 ? 0
-            : (int)(left < a.span / 4 ? (left + 3) / 4 : a.span / 16);
-        FdPixel px(begin + k < a.P ? begin + k : 0, a.F, a.T);
-        for (int step = 0; step < steps; ++step, px.advance(4, a.F, a.T)) {
-            const long long p = begin + step * 4 + k;
-            const bool live = p < a.P;
-            if (O == 16) {
-                float gz = 0.f;
-                if (live) gz = fd_gate(a.g[p * 16 + j], a.y[p * 16 + j], a.act);
+    const auto [begin, steps] = dl_gw_span(a.P, a.span, wave);
+    DlPixel px(begin + k < a.P ? begin + k : 0, a.F, a.T);
+    for (int step = 0; step < steps; ++step, px.advance(4, a.F, a.T)) {
+        const long long p = begin + step * 4 + k;
+        const bool live = p < a.P;
+        if (O == 16) {
+            float gz = 0.f;
+            if (live) gz = fd_gate(a.g[p * 16 + j], a.y[p * 16 + j], a.act);
 #pragma unroll
-                for (int m = 0; m < NM; ++m) {
-                    float v = 0.f;
-                    if (C == 16 && m < 9) {
-                        if (live && px.tap_f(m, a.d, a.F, a.T) >= 0)
-                            v = a.x[(p + fd_tap_offset(m, a.d, a.T)) * 16 + j];
+            for (int m = 0; m < NM; ++m) {
+                float v = 0.f;
+                if (C == 16 && m < 9) {
+                    if (live && fd_tap_f(px, m, a.d, a.F, a.T) >= 0)
+                        v = a.x[(p + fd_tap_offset(m, a.d, a.T)) * 16 + j];
+                } else {
+                    // (tap, which) of this column: which 0 = x (C = 1),
+                    // 1 = sin, 2 = cos; 3 = one; -1 = nothing
+                    int tap = 0, which = -1;
+                    if (C == 16) {
+                        const int e = 16 * m + j - 144;
+                        tap = e >> 1;
+                        which = e < 18 ? 1 + (e & 1) : (e == 18 ? 3 : -1);
                     } else {
-                        // (tap, which) of this column: which 0 = x (C = 1),
-                        // 1 = sin, 2 = cos; 3 = one; -1 = nothing
-                        int tap = 0, which = -1;
-                        if (C == 16) {
-                            const int e = 16 * m + j - 144;
-                            tap = e >> 1;
-                            which = e < 18 ? 1 + (e & 1) : (e == 18 ? 3 : -1);
-                        } else {
-                            const int idx = 16 * m + j;
-                            tap = idx / 3;
-                            which = idx < 27 ? idx % 3 : (idx == 27 ? 3 : -1);
-                        }
-                        if (live && which == 3) {
-                            v = 1.f;
-                        } else if (live && which >= 0) {
-                            const int ff = px.tap_f(tap, a.d, a.F, a.T);
-                            if (ff >= 0)
-                                v = which == 0
-                                    ? a.x[p + fd_tap_offset(tap, a.d, a.T)]
-                                    : a.table[2 * ff + which - 1];
-                        }
+                        const int idx = 16 * m + j;
+                        tap = idx / 3;
+                        which = idx < 27 ? idx % 3 : (idx == 27 ? 3 : -1);
                     }
-                    acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                        gz, v, acc[m], 0, 0, 0);
+                    if (live && which == 3) {
+                        v = 1.f;
+                    } else if (live && which >= 0) {
+                        const int ff = fd_tap_f(px, tap, a.d, a.F, a.T);
+                        if (ff >= 0)
+                            v = which == 0
+                                ? a.x[p + fd_tap_offset(tap, a.d, a.T)]
+                                : a.table[2 * ff + which - 1];
+                    }
                 }
-            } else {
-                float gz = 0.f;
-                if (live && j < 9 && px.tap_f(j, a.d, a.F, a.T, -1) >= 0) {
-                    const long long at = p - fd_tap_offset(j, a.d, a.T);
-                    gz = fd_gate(a.g[at], a.y[at], a.act);
-                }
-                const float xv = live ? a.x[p * 16 + j] : 0.f;
-                float ev = 0.f;
-                if (live && j < 3)
-                    ev = j == 2 ? 1.f : a.table[2 * px.f + j];
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    xv, gz, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ev, gz, acc[1], 0, 0, 0);
+                acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                    gz, v, acc[m], 0, 0, 0);
             }
+        } else {
+            float gz = 0.f;
+            if (live && j < 9 && fd_tap_f(px, j, a.d, a.F, a.T, -1) >= 0) {
+                const long long at = p - fd_tap_offset(j, a.d, a.T);
+                gz = fd_gate(a.g[at], a.y[at], a.act);
+            }
+            const float xv = live ? a.x[p * 16 + j] : 0.f;
+            float ev = 0.f;
+            if (live && j < 3)
+                ev = j == 2 ? 1.f : a.table[2 * px.h + j];
+            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                xv, gz, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                ev, gz, acc[1], 0, 0, 0);
         }
     }
-    // the four waves, added in order; every element of the partial is written
-    // by exactly one thread (the slots of a partial are distinct)
-#pragma unroll
-    for (int m = 0; m < NM; ++m)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lds[wave][m][r][lane] = acc[m][r];
-    __syncthreads();
-    float* part = a.parts + (long long)blockIdx.x * G::N;
-    for (int e = threadIdx.x; e < NM * 256; e += FD_THREADS) {
-        const int m = e >> 8, r = (e >> 6) & 3, l = e & 63;
-        const int slot = G::slot(m, 4 * (l >> 4) + r, l & 15);
-        if (slot < 0) continue;
-        float sum = lds[0][m][r][l];
-        for (int w = 1; w < FD_THREADS / 64; ++w) sum += lds[w][m][r][l];
-        part[slot] = sum;
-    }
-}
-
-// gW | gb = the partials added in a fixed order, in double: 64 entries a
-// workgroup, each wave a quarter of the partials in ascending order (eight
-// loads in flight), then the four waves in order
-__global__ __launch_bounds__(FD_THREADS) void fd_reduce_kernel(
-    const float* __restrict__ parts, int nparts, int n, int weights,
-    float* __restrict__ grad_weight, float* __restrict__ grad_bias) {
-    __shared__ double lds[FD_THREADS / 64][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + lane;
-    const int per = (nparts + FD_THREADS / 64 - 1) / (FD_THREADS / 64);
-    const int first = wave * per;
-    const int last = first + per < nparts ? first + per : nparts;
-    double sum = 0.;
-    if (e < n) {
-        int i = first;
-        for (; i + 8 <= last; i += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = parts[(long long)(i + u) * n + e];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) sum += (double)v[u];
-        }
-        for (; i < last; ++i) sum += (double)parts[(long long)i * n + e];
-    }
-    lds[wave][lane] = sum;
-    __syncthreads();
-    if (wave != 0 || e >= n) return;
-    for (int w = 1; w < FD_THREADS / 64; ++w) sum += lds[w][lane];
-    if (e < weights) grad_weight[e] = (float)sum;
-    else grad_bias[e - weights] = (float)sum;
+    dl_gw_store<G>(acc, a.parts);
 }
 
 // ---------------------------------------------------------------------------

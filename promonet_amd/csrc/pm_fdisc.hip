@@ -34,17 +34,9 @@ const char* check_layer(int batch, int channels, int out_channels, int bins,
     return nullptr;
 }
 
-// The pixels of a gW workgroup (a multiple of 16, so that its four waves take
-// whole steps of four) and the partials of gW and gb, one a workgroup: a
-// function of the sizes alone.
-int span_of(long long pixels) {
-    long long want = (pixels + FD_GW_CHUNK - 1) / FD_GW_CHUNK;
-    if (want > FD_GW_MAX_PARTS) want = FD_GW_MAX_PARTS;
-    return (int)(((pixels + want - 1) / want + 15) / 16 * 16);
-}
-int parts_of(long long pixels) {
-    const int span = span_of(pixels);
-    return (int)((pixels + span - 1) / span);
+// The partials of gW and gb and the pixels of each
+PmSplit split_of(long long pixels) {
+    return pm_pixel_split(pixels, FD_GW_CHUNK, FD_GW_MAX_PARTS);
 }
 
 int partial_floats(int channels, int out_channels) {
@@ -56,13 +48,9 @@ struct FdLayout { float* parts; size_t total; };
 FdLayout backward_layout(long long pixels, int channels, int out_channels,
                          void* base) {
     PmCarve c(base);
-    return {c.take<float>((size_t)parts_of(pixels) *
+    return {c.take<float>((size_t)split_of(pixels).parts *
                           partial_floats(channels, out_channels)),
             c.used};
-}
-
-unsigned groups(long long threads) {
-    return (unsigned)((threads + FD_THREADS - 1) / FD_THREADS);
 }
 
 const char* check_norm(int out_channels, int fan) {
@@ -101,10 +89,10 @@ extern "C" int pm_fdisc_conv_forward(const float* x, const float* weight,
     a.P = (long long)batch * bins * frames;
     hipStream_t s = (hipStream_t)stream;
     const dim3 block(FD_THREADS);
-    const dim3 tiles((unsigned)((a.P + FD_CONV_PIXELS - 1) / FD_CONV_PIXELS));
+    const dim3 tiles(pm_groups(a.P, FD_CONV_PIXELS));
     if (out_channels == 1)
-        hipLaunchKernelGGL(fd_conv_o1_kernel, dim3(groups(a.P)), block, 0, s,
-                           a);
+        hipLaunchKernelGGL(fd_conv_o1_kernel,
+                           dim3(pm_groups(a.P, FD_THREADS)), block, 0, s, a);
     else if (channels == 16)
         hipLaunchKernelGGL((fd_conv16_kernel<16, false>), tiles, block, 0, s,
                            a);
@@ -124,40 +112,40 @@ extern "C" int pm_fdisc_conv_backward(
     if (const char* why = check_layer(batch, channels, out_channels, bins,
                                       frames, dilation, activation))
         return pm_fail(PM_EINVAL, "pm_fdisc_conv_backward: %s", why);
-    const bool weights = grad_weight || grad_bias;
-    if (!upstream || !y || !x || !weight || !table ||
-        (weights && (!grad_weight || !grad_bias || !workspace)))
-        return pm_fail(PM_EINVAL, "pm_fdisc_conv_backward: null argument");
+    const long long pixels = (long long)batch * bins * frames;
+    const FdLayout l =
+        backward_layout(pixels, channels, out_channels, workspace);
+    if (const int code = pm_check_backward(
+            "pm_fdisc_conv_backward", upstream && y && x && weight && table,
+            grad_weight, grad_bias, workspace, workspace_bytes, l.total))
+        return code;
     FdArgs a = {};
     a.x = x; a.w = weight; a.table = table; a.g = upstream; a.y = y;
     a.B = batch; a.F = bins; a.T = frames; a.d = dilation; a.act = activation;
-    a.P = (long long)batch * bins * frames;
-    const FdLayout l = backward_layout(a.P, channels, out_channels, workspace);
-    if (weights && workspace_bytes < l.total)
-        return pm_fail(PM_ENOMEM,
-                       "pm_fdisc_conv_backward: workspace too small");
+    a.P = pixels;
     hipStream_t s = (hipStream_t)stream;
     const dim3 block(FD_THREADS);
     if (grad_x) {
         a.out = grad_x;
         if (out_channels == 1)
-            hipLaunchKernelGGL(fd_gx_o1_kernel, dim3(groups(a.P * 4)), block,
-                               0, s, a);
-        else if (channels == 1)
-            hipLaunchKernelGGL(fd_gx_c1_kernel, dim3(groups(a.P)), block, 0,
+            hipLaunchKernelGGL(fd_gx_o1_kernel,
+                               dim3(pm_groups(a.P * 4, FD_THREADS)), block, 0,
                                s, a);
+        else if (channels == 1)
+            hipLaunchKernelGGL(fd_gx_c1_kernel,
+                               dim3(pm_groups(a.P, FD_THREADS)), block, 0, s,
+                               a);
         else
-            hipLaunchKernelGGL(
-                (fd_conv16_kernel<16, true>),
-                dim3((unsigned)((a.P + FD_CONV_PIXELS - 1) / FD_CONV_PIXELS)),
-                block, 0, s, a);
+            hipLaunchKernelGGL((fd_conv16_kernel<16, true>),
+                               dim3(pm_groups(a.P, FD_CONV_PIXELS)), block, 0,
+                               s, a);
         PM_HIP_TRY(hipGetLastError());
     }
-    if (weights) {
+    if (grad_weight) {      // (and grad_bias: pm_check_backward)
+        const PmSplit split = split_of(a.P);
         a.parts = l.parts;
-        a.span = span_of(a.P);
-        const int nparts = parts_of(a.P);
-        const dim3 grid(nparts);
+        a.span = split.each;
+        const dim3 grid(split.parts);
         if (out_channels == 1)
             hipLaunchKernelGGL((fd_gw_kernel<16, 1>), grid, block, 0, s, a);
         else if (channels == 16)
@@ -165,11 +153,9 @@ extern "C" int pm_fdisc_conv_backward(
         else
             hipLaunchKernelGGL((fd_gw_kernel<1, 16>), grid, block, 0, s, a);
         PM_HIP_TRY(hipGetLastError());
-        const int n = partial_floats(channels, out_channels);
-        hipLaunchKernelGGL(fd_reduce_kernel, dim3((n + 63) / 64), block, 0, s,
-                           (const float*)l.parts, nparts, n,
-                           n - out_channels, grad_weight, grad_bias);
-        PM_HIP_TRY(hipGetLastError());
+        PM_HIP_TRY(dl_reduce(l.parts, split.parts,
+                             partial_floats(channels, out_channels),
+                             out_channels, grad_weight, grad_bias, s));
     }
     return PM_OK;
 }

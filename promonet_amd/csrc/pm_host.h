@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #include "promonet_hip.h"
 
@@ -28,6 +29,56 @@ static inline int pm_pad32(int c) { return (c + 31) / 32 * 32; }
 static inline size_t pm_align256(size_t v) { return (v + 255) / 256 * 256; }
 static inline bool pm_aligned16(const void* p) {
     return ((uintptr_t)p & 15) == 0;
+}
+
+static inline long long pm_ceil_div(long long a, long long b) {
+    return (a + b - 1) / b;
+}
+// the workgroups of `block` threads that hold `threads`
+static inline unsigned pm_groups(long long threads, int block) {
+    return (unsigned)pm_ceil_div(threads, block);
+}
+
+// Returns NULL, or what is wrong with the slope of a leaky layer.
+static inline const char* pm_check_slope(float slope) {
+    // (on the bits, as one integer range: the files that call this are
+    // compiled with -fno-honor-nans, which lets the compiler drop any test
+    // that only NaN fails; the positive floats are ordered as their bits are,
+    // 1.f being 0x3f800000)
+    uint32_t bits;
+    std::memcpy(&bits, &slope, sizeof bits);
+    if (bits - 1u > 0x3f800000u - 1u)
+        return "slope must be finite and in (0, 1]";
+    return nullptr;
+}
+
+// The partials of a gW kernel over `pixels` flattened pixels, one a workgroup,
+// and the pixels of each, a multiple of 16 (so that its four waves take whole
+// steps of four): ceil(pixels / chunk) of them, `max_parts` at the most. A
+// function of the sizes alone.
+struct PmSplit { int parts, each; };
+static inline PmSplit pm_pixel_split(long long pixels, int chunk,
+                                     int max_parts) {
+    long long want = pm_ceil_div(pixels, chunk);
+    if (want > max_parts) want = max_parts;
+    const int each = (int)((pm_ceil_div(pixels, want) + 15) / 16 * 16);
+    return {(int)pm_ceil_div(pixels, each), each};
+}
+
+// The checks of a conv layer's backward after its sizes: the pointers, then
+// the workspace of `needed` bytes, which only the weight gradients use.
+// `inputs`: no tensor that the entry reads is null.
+static inline int pm_check_backward(const char* entry, bool inputs,
+                                    const float* grad_weight,
+                                    const float* grad_bias,
+                                    const void* workspace,
+                                    size_t workspace_bytes, size_t needed) {
+    const bool weights = grad_weight || grad_bias;
+    if (!inputs || (weights && (!grad_weight || !grad_bias || !workspace)))
+        return pm_fail(PM_EINVAL, "%s: null argument", entry);
+    if (weights && workspace_bytes < needed)
+        return pm_fail(PM_ENOMEM, "%s: workspace too small", entry);
+    return PM_OK;
 }
 
 // A caller-provided workspace is laid out by one function that carves its

@@ -43,7 +43,7 @@
 //            accumulator against a column of ones in the tiles of the first
 //            input channels. The chunks are split over `parts` workgroups a
 //            tile, each writing one partial (O C 5 + O floats) to the
-//            workspace; pc_reduce_kernel adds the partials in ascending order
+//            workspace; dl_reduce_kernel adds the partials in ascending order
 //            in double. Their count is a function of the sizes alone: no
 //            float atomics, the same bits on every run.
 // THE EDGE LAYERS are plain VALU kernels. The first layer (1 -> 32) reads the
@@ -55,6 +55,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pm_dlayer.h"
+
 #define PC_THREADS 256
 #define PC_NT 64                // pixels of a tile of the forward and of gx
 #define PC_KC 32                // contracted channels of a K chunk
@@ -65,8 +67,7 @@
 #define PC_FOLD_CHUNK 256       // fewest output pixels of a first-layer partial
 #define PC_POST_CHUNK 16        // fewest pixels of a last-layer partial
 #define PC_EDGE_MAX_PARTS 1024  // most partials of an edge layer
-
-typedef float pc_f4 __attribute__((ext_vector_type(4)));
+static_assert(PC_THREADS == DL_THREADS, "the workgroup of pm_dlayer.h");
 
 struct PcArgs {
     const float* x;         // (B, H, P, C); the first layer: the audio (B, T)
@@ -84,28 +85,6 @@ struct PcArgs {
     long long pixels;       // edge kernels: B Ho P output pixels
     int span;               // edge gW: pixels of a workgroup
 };
-
-__device__ __forceinline__ float pc_leaky(float v, float slope) {
-    return v > 0.f ? v : v * slope;
-}
-// upstream * leaky'(y): y = 0 takes the slope, as torch does
-__device__ __forceinline__ float pc_gate(float g, float y, float slope) {
-    return y > 0.f ? g : g * slope;
-}
-__device__ __forceinline__ float4 pc_gate4(float4 g, float4 y, float slope) {
-    return make_float4(pc_gate(g.x, y.x, slope), pc_gate(g.y, y.y, slope),
-                       pc_gate(g.z, y.z, slope), pc_gate(g.w, y.w, slope));
-}
-
-#define PC_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0)
-// four K steps: the elements of a lane's 16-byte reads of A and B
-#define PC_MFMA4(acc, a4, b4)                                               \
-    do {                                                                    \
-        acc = PC_MFMA((a4).x, (b4).x, acc);                                 \
-        acc = PC_MFMA((a4).y, (b4).y, acc);                                 \
-        acc = PC_MFMA((a4).z, (b4).z, acc);                                 \
-        acc = PC_MFMA((a4).w, (b4).w, acc);                                 \
-    } while (0)
 
 // ---------------------------------------------------------------------------
 // The general forward (GX false) and input gradient (GX true): D[row][pixel].
@@ -224,21 +203,21 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
         for (int u = 0; u < BV; ++u) {
             const int idx = threadIdx.x + u * PC_THREADS;
             float4 v = br[u];
-            if constexpr (GX) v = pc_gate4(br[u], yr[u], a.slope);
+            if constexpr (GX) v = dl_gate4(br[u], yr[u], a.slope);
             *(float4*)(xl + (idx >> 3) * PC_PITCH + 4 * (idx & 7)) = v;
         }
     };
 
     // [chunk parity][row tile][channel half]
-    pc_f4 acc[2][MM][2];
+    dl_f4 acc[2][MM][2];
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int m = 0; m < MM; ++m)
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                acc[p][m][h] = pc_f4{0.f, 0.f, 0.f, 0.f};
-    auto mma = [&](pc_f4 (&to)[MM][2]) {
+                acc[p][m][h] = dl_f4{0.f, 0.f, 0.f, 0.f};
+    auto mma = [&](dl_f4 (&to)[MM][2]) {
 #pragma unroll
         for (int slot = 0; slot < SLOTS; ++slot) {
             if (slot >= slots) break;
@@ -252,8 +231,8 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
                     wl + (slot * MT + 16 * m + col) * PC_PITCH + 4 * k;
                 const float4 a0 = *(const float4*)wa;
                 const float4 a1 = *(const float4*)(wa + 16);
-                PC_MFMA4(to[m][0], a0, b0);
-                PC_MFMA4(to[m][1], a1, b1);
+                DL_MFMA4(to[m][0], a0, b0);
+                DL_MFMA4(to[m][1], a1, b1);
             }
         }
     };
@@ -280,7 +259,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
     float* out = a.out + pixel * M + m0 + 4 * k;
 #pragma unroll
     for (int m = 0; m < MM; ++m) {
-        const pc_f4 sum =
+        const dl_f4 sum =
             (acc[0][m][0] + acc[0][m][1]) + (acc[1][m][0] + acc[1][m][1]);
         if (GX) {
             *(float4*)(out + 16 * m) =
@@ -288,10 +267,10 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
         } else {
             const float4 bias = *(const float4*)(a.bias + m0 + 16 * m + 4 * k);
             *(float4*)(out + 16 * m) = make_float4(
-                pc_leaky(sum[0] + bias.x, a.slope),
-                pc_leaky(sum[1] + bias.y, a.slope),
-                pc_leaky(sum[2] + bias.z, a.slope),
-                pc_leaky(sum[3] + bias.w, a.slope));
+                dl_leaky(sum[0] + bias.x, a.slope),
+                dl_leaky(sum[1] + bias.y, a.slope),
+                dl_leaky(sum[2] + bias.z, a.slope),
+                dl_leaky(sum[3] + bias.w, a.slope));
         }
     }
 }
@@ -319,11 +298,11 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gw_kernel(PcArgs a) {
     const bool with_bias = c0 == 0;
     const unsigned plane = (unsigned)a.Ho * (unsigned)a.P;
 
-    pc_f4 acc[5][NN], accb = {0.f, 0.f, 0.f, 0.f};
+    dl_f4 acc[5][NN], accb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < 5; ++t)
 #pragma unroll
-        for (int n = 0; n < NN; ++n) acc[t][n] = pc_f4{0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < NN; ++n) acc[t][n] = dl_f4{0.f, 0.f, 0.f, 0.f};
 
     float4 gr[ZV], yr[ZV], xr[XV];
     auto load = [&](int chunk) {
@@ -369,7 +348,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gw_kernel(PcArgs a) {
         for (int u = 0; u < ZV; ++u) {
             const int idx = threadIdx.x + u * PC_THREADS;
             *(float4*)(zl + (idx >> 4) * ZP + 4 * (idx & 15)) =
-                pc_gate4(gr[u], yr[u], a.slope);
+                dl_gate4(gr[u], yr[u], a.slope);
         }
 #pragma unroll
         for (int u = 0; u < XV; ++u) {
@@ -386,10 +365,10 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gw_kernel(PcArgs a) {
             for (int t = 0; t < 5; ++t)
 #pragma unroll
                 for (int n = 0; n < NN; ++n)
-                    acc[t][n] = PC_MFMA(
+                    acc[t][n] = DL_MFMA(
                         gz, xl[(t * PC_GW_PIX + 4 * step + k) * XP + 16 * n + i],
                         acc[t][n]);
-            if (with_bias) accb = PC_MFMA(gz, 1.f, accb);
+            if (with_bias) accb = DL_MFMA(gz, 1.f, accb);
         }
     }
     // rows o = o0 + 16 wave + 4 k + r, column c = c0 + 16 n + i: every float
@@ -410,44 +389,12 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gw_kernel(PcArgs a) {
                 accb[r];
 }
 
-// gW | gb = the partials added in a fixed order, in double: 64 entries a
-// workgroup, each wave a quarter of the partials in ascending order (eight
-// loads in flight), then the four waves in order
-__global__ __launch_bounds__(PC_THREADS) void pc_reduce_kernel(
-    const float* __restrict__ parts, int nparts, long long n,
-    long long weights, float* __restrict__ grad_weight,
-    float* __restrict__ grad_bias) {
-    __shared__ double lds[PC_THREADS / 64][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long e = (long long)blockIdx.x * 64 + lane;
-    const int per = (nparts + PC_THREADS / 64 - 1) / (PC_THREADS / 64);
-    const int first = wave * per;
-    const int last = first + per < nparts ? first + per : nparts;
-    double sum = 0.;
-    if (e < n) {
-        int p = first;
-        for (; p + 8 <= last; p += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = parts[(long long)(p + u) * n + e];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) sum += (double)v[u];
-        }
-        for (; p < last; ++p) sum += (double)parts[(long long)p * n + e];
-    }
-    lds[wave][lane] = sum;
-    __syncthreads();
-    if (wave != 0 || e >= n) return;
-    for (int w = 1; w < PC_THREADS / 64; ++w) sum += lds[w][lane];
-    if (e < weights) grad_weight[e] = (float)sum;
-    else grad_bias[e - weights] = (float)sum;
-}
-
 // ---------------------------------------------------------------------------
 // The first layer, 1 -> 32 at k 5, s 3, on the audio (B, T). The folded map
 // is (B, H, P) with H = (T + pad) / P; its pixel (h, w) is the sample h P + w,
 // reflected about T - 1 past the end. 32-bit pixel arithmetic: the host
-// refuses more than 2^31 - 1 pixels.
+// refuses more than 2^31 - 1 pixels. (DlPixel with the batch row, which finds
+// the audio: the kernels of the last layer read h alone, and none walks.)
 // ---------------------------------------------------------------------------
 struct PcPixel {
     int b, h, w;
@@ -498,8 +445,8 @@ __global__ __launch_bounds__(PC_THREADS) void pc_fold_conv_kernel(PcArgs a) {
     }
     const float4 bias = *(const float4*)(a.bias + 4 * q);
     *(float4*)(a.out + p * 32 + 4 * q) = make_float4(
-        pc_leaky(acc.x + bias.x, a.slope), pc_leaky(acc.y + bias.y, a.slope),
-        pc_leaky(acc.z + bias.z, a.slope), pc_leaky(acc.w + bias.w, a.slope));
+        dl_leaky(acc.x + bias.x, a.slope), dl_leaky(acc.y + bias.y, a.slope),
+        dl_leaky(acc.z + bias.z, a.slope), dl_leaky(acc.w + bias.w, a.slope));
 }
 
 // The gradient of the folded map at the position pos = h P + w of a batch
@@ -517,7 +464,7 @@ __device__ __forceinline__ float pc_fold_gather(const PcArgs& a,
             (((long long)b * a.Ho + num / 3) * a.P + w) * 32;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            const float4 gz = pc_gate4(*(const float4*)(a.g + at + 4 * q),
+            const float4 gz = dl_gate4(*(const float4*)(a.g + at + 4 * q),
                                        *(const float4*)(a.y + at + 4 * q),
                                        a.slope);
             const float4 u = *(const float4*)(wl + t * 32 + 4 * q);
@@ -558,7 +505,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_fold_gw_kernel(PcArgs a) {
     for (long long p = begin + slice; p < end; p += 8) {
         const PcPixel px(p, a.Ho, a.P);
         const float* audio = a.x + (long long)px.b * a.T;
-        const float gz = pc_gate(a.g[p * 32 + o], a.y[p * 32 + o], a.slope);
+        const float gz = dl_gate(a.g[p * 32 + o], a.y[p * 32 + o], a.slope);
 #pragma unroll
         for (int t = 0; t < 5; ++t)
             acc[t] = fmaf(gz, pc_folded(audio, 3 * px.h - 2 + t, px.w, a),
@@ -614,7 +561,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_post_conv_kernel(PcArgs a) {
     float sum = (acc.x + acc.y) + (acc.z + acc.w);
 #pragma unroll
     for (int step = 32; step > 0; step >>= 1) sum += __shfl_xor(sum, step, 64);
-    if (lane == 0) a.out[p] = pc_leaky(sum + a.bias[0], a.slope);
+    if (lane == 0) a.out[p] = dl_leaky(sum + a.bias[0], a.slope);
 }
 
 // input gradient: four input channels of a pixel a thread
@@ -637,7 +584,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_post_gx_kernel(PcArgs a) {
         const int h = px.h + 1 - t;
         if (h < 0 || h >= a.H) continue;
         const long long at = p + (long long)(1 - t) * a.P;
-        const float gz = pc_gate(a.g[at], a.y[at], a.slope);
+        const float gz = dl_gate(a.g[at], a.y[at], a.slope);
         acc.x = fmaf(wv[t], gz, acc.x);
         acc.y = fmaf(wv[3 + t], gz, acc.y);
         acc.z = fmaf(wv[6 + t], gz, acc.z);
@@ -664,7 +611,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_post_gw_kernel(PcArgs a) {
             const int h = px.h + 1 - t;
             if (h < 0 || h >= a.H) continue;
             const long long at = p + (long long)(1 - t) * a.P;
-            const float gz = pc_gate(a.g[at], a.y[at], a.slope);
+            const float gz = dl_gate(a.g[at], a.y[at], a.slope);
             acc[0][t] = fmaf(gz, v.x, acc[0][t]);
             acc[1][t] = fmaf(gz, v.y, acc[1][t]);
             acc[2][t] = fmaf(gz, v.z, acc[2][t]);

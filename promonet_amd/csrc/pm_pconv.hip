@@ -4,8 +4,6 @@
 // the first HIP call, so the checks answer on a machine without a GPU.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-
 #include "pm_host.h"
 #include "pm_pconv.h"
 
@@ -72,39 +70,25 @@ const char* check_fold(int batch, int samples, int period, Sizes* z) {
     return nullptr;
 }
 
-const char* check_slope(float slope) {
-    // (on the bits, as one integer range: this file is compiled with
-    // -fno-honor-nans, which lets the compiler drop any test that only NaN
-    // fails; the positive floats are ordered as their bits are, 1.f being
-    // 0x3f800000)
-    uint32_t bits;
-    std::memcpy(&bits, &slope, sizeof bits);
-    if (bits - 1u > 0x3f800000u - 1u)
-        return "slope must be finite and in (0, 1]";
-    return nullptr;
-}
-
-long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
-
 // The partials of gW and gb and what each takes: K chunks of a tile (the
 // general layers) or pixels (the edges). A function of the sizes alone.
 struct Split { int parts, each, chunks; };
 Split split_of(const Sizes& z) {
     if (z.first() || z.post()) {
         const long long pixels = z.first() ? z.out_pixels : z.in_pixels;
-        long long each = ceil_div(pixels, PC_EDGE_MAX_PARTS);
+        long long each = pm_ceil_div(pixels, PC_EDGE_MAX_PARTS);
         const int least = z.first() ? PC_FOLD_CHUNK : PC_POST_CHUNK;
         if (each < least) each = least;
-        return {(int)ceil_div(pixels, each), (int)each, 0};
+        return {(int)pm_ceil_div(pixels, each), (int)each, 0};
     }
-    const int chunks = (int)ceil_div(z.out_pixels, PC_GW_PIX);
+    const int chunks = (int)pm_ceil_div(z.out_pixels, PC_GW_PIX);
     const int tiles = (z.O / 64) * (z.C / (z.C < 64 ? 32 : 64));
-    long long want = ceil_div(chunks, PC_GW_MIN_CHUNKS);
+    long long want = pm_ceil_div(chunks, PC_GW_MIN_CHUNKS);
     const long long room = PC_GW_WORKGROUPS / tiles > 1
         ? PC_GW_WORKGROUPS / tiles : 1;
     if (want > room) want = room;
-    const int each = (int)ceil_div(chunks, want);
-    return {(int)ceil_div(chunks, each), each, chunks};
+    const int each = (int)pm_ceil_div(chunks, want);
+    return {(int)pm_ceil_div(chunks, each), each, chunks};
 }
 
 // backward: the partials
@@ -114,10 +98,6 @@ PcLayout backward_layout(const Sizes& z, void* base) {
     return {c.take<float>((size_t)split_of(z).parts *
                           (size_t)z.partial_floats()),
             c.used};
-}
-
-unsigned groups(long long threads) {
-    return (unsigned)((threads + PC_THREADS - 1) / PC_THREADS);
 }
 
 PcArgs args_of(const Sizes& z, float slope) {
@@ -139,11 +119,11 @@ int launch_gemm(PcArgs a, const Sizes& z, hipStream_t s) {
         ntiles = 0;
         for (int r = 0; r < 3; ++r) {
             const long long rows = z.H > r ? (z.H - 1 - r) / 3 + 1 : 0;
-            a.classes[r] = (int)ceil_div((long long)z.B * rows * z.P, PC_NT);
+            a.classes[r] = (int)pm_ceil_div((long long)z.B * rows * z.P, PC_NT);
             ntiles += a.classes[r];
         }
     } else {
-        ntiles = ceil_div(GX ? z.in_pixels : z.out_pixels, PC_NT);
+        ntiles = pm_ceil_div(GX ? z.in_pixels : z.out_pixels, PC_NT);
     }
     const long long grid = ntiles * ((GX ? z.C : z.O) / MT);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PC_THREADS), lds, s, a);
@@ -168,7 +148,7 @@ int launch_gw(PcArgs a, const Sizes& z, const Split& split, hipStream_t s) {
 int forward(const char* entry, const Sizes& z, const float* x,
             const float* weight, const float* bias, float* y, float slope,
             void* stream) {
-    if (const char* why = check_slope(slope))
+    if (const char* why = pm_check_slope(slope))
         return pm_fail(PM_EINVAL, "%s: %s", entry, why);
     if (!x || !weight || !bias || !y)
         return pm_fail(PM_EINVAL, "%s: null argument", entry);
@@ -176,11 +156,12 @@ int forward(const char* entry, const Sizes& z, const float* x,
     a.x = x; a.w = weight; a.bias = bias; a.out = y;
     hipStream_t s = (hipStream_t)stream;
     if (z.first())
-        hipLaunchKernelGGL(pc_fold_conv_kernel, dim3(groups(a.pixels * 8)),
+        hipLaunchKernelGGL(pc_fold_conv_kernel,
+                           dim3(pm_groups(a.pixels * 8, PC_THREADS)),
                            dim3(PC_THREADS), 0, s, a);
     else if (z.post())
         hipLaunchKernelGGL(pc_post_conv_kernel,
-                           dim3((unsigned)ceil_div(a.pixels, 4)),
+                           dim3((unsigned)pm_ceil_div(a.pixels, 4)),
                            dim3(PC_THREADS), 0, s, a);
     else
         return z.S == 3 ? launch_gemm<false, 3, 64>(a, z, s)
@@ -193,15 +174,13 @@ int backward(const char* entry, const Sizes& z, const float* upstream,
              const float* y, const float* x, const float* weight,
              float* grad_x, float* grad_weight, float* grad_bias, float slope,
              void* workspace, size_t workspace_bytes, void* stream) {
-    if (const char* why = check_slope(slope))
+    if (const char* why = pm_check_slope(slope))
         return pm_fail(PM_EINVAL, "%s: %s", entry, why);
-    const bool weights = grad_weight || grad_bias;
-    if (!upstream || !y || !x || !weight ||
-        (weights && (!grad_weight || !grad_bias || !workspace)))
-        return pm_fail(PM_EINVAL, "%s: null argument", entry);
     const PcLayout l = backward_layout(z, workspace);
-    if (weights && workspace_bytes < l.total)
-        return pm_fail(PM_ENOMEM, "%s: workspace too small", entry);
+    if (const int code = pm_check_backward(
+            entry, upstream && y && x && weight, grad_weight, grad_bias,
+            workspace, workspace_bytes, l.total))
+        return code;
     PcArgs a = args_of(z, slope);
     a.x = x; a.w = weight; a.g = upstream; a.y = y;
     hipStream_t s = (hipStream_t)stream;
@@ -209,12 +188,14 @@ int backward(const char* entry, const Sizes& z, const float* upstream,
     if (grad_x) {
         a.out = grad_x;
         if (z.first()) {
+            const long long samples = (long long)z.B * z.T;
             hipLaunchKernelGGL(pc_fold_gx_kernel,
-                               dim3(groups((long long)z.B * z.T)), block, 0, s,
-                               a);
+                               dim3(pm_groups(samples, PC_THREADS)), block, 0,
+                               s, a);
             PM_HIP_TRY(hipGetLastError());
         } else if (z.post()) {
-            hipLaunchKernelGGL(pc_post_gx_kernel, dim3(groups(a.pixels * 256)),
+            hipLaunchKernelGGL(pc_post_gx_kernel,
+                               dim3(pm_groups(a.pixels * 256, PC_THREADS)),
                                block, 0, s, a);
             PM_HIP_TRY(hipGetLastError());
         } else {
@@ -225,7 +206,7 @@ int backward(const char* entry, const Sizes& z, const float* upstream,
             if (code != PM_OK) return code;
         }
     }
-    if (weights) {
+    if (grad_weight) {      // (and grad_bias: pm_check_backward)
         a.parts = l.parts;
         const Split split = split_of(z);
         if (z.first() || z.post()) {
@@ -244,11 +225,8 @@ int backward(const char* entry, const Sizes& z, const float* upstream,
                             : launch_gw<3, 64>(a, z, split, s);
             if (code != PM_OK) return code;
         }
-        const long long n = z.partial_floats();
-        hipLaunchKernelGGL(pc_reduce_kernel, dim3((unsigned)ceil_div(n, 64)),
-                           block, 0, s, (const float*)l.parts, split.parts, n,
-                           n - z.O, grad_weight, grad_bias);
-        PM_HIP_TRY(hipGetLastError());
+        PM_HIP_TRY(dl_reduce(l.parts, split.parts, z.partial_floats(), z.O,
+                             grad_weight, grad_bias, s));
     }
     return PM_OK;
 }

@@ -74,10 +74,13 @@ def _tables(device, sizes):
             _twiddle(device, fft_size))
 
 
+def _workspace_of(size, device):
+    return torch.empty(size, dtype=torch.uint8, device=device)
+
+
 def _workspace(lib, sizes, flat, backward):
-    size = lib.pm_disc_spec_workspace_bytes(
-        sizes[0], *flat.shape, *sizes[1:], int(backward))
-    return torch.empty(size, dtype=torch.uint8, device=flat.device)
+    return _workspace_of(lib.pm_disc_spec_workspace_bytes(
+        sizes[0], *flat.shape, *sizes[1:], int(backward)), flat.device)
 
 
 def _forward_call(flat, window, twiddle, sizes):
@@ -195,102 +198,82 @@ def spectrogram_decibel(audio, resolution):
 
 
 ###############################################################################
-# The conv stacks of DiscriminatorMagFree
+# What the conv stacks share
 ###############################################################################
 
-DILATIONS = (1, 2, 4, 8, 16)
-RESOLUTIONS = (64, 128, 256, 512, 1024, 2048)
-_TABLES = {}
+
+def _require_float(**tensors):
+    for name, tensor in tensors.items():
+        if not isinstance(tensor, torch.Tensor) or \
+                not tensor.is_floating_point():
+            raise ValueError(f'{name} must be a float tensor')
 
 
-def _embedding_table(device, bins):
-    """(bins, 2) fp32 = sin, cos of FrequencyPositionalEmbedding (:381-389),
-    by its own expression on the device; cached per device and size"""
-    key = (str(device), bins)
-    if key not in _TABLES:
-        args = torch.arange(
-            0, bins, dtype=torch.float32, device=device) * torch.pi * 2 / bins
-        _TABLES[key] = torch.stack(
-            (torch.sin(args), torch.cos(args)), dim=1).contiguous()
-    return _TABLES[key]
+def _check_slope(slope):
+    if isinstance(slope, bool) or not isinstance(slope, (int, float)) or \
+            not math.isfinite(slope) or not 0. < slope <= 1.:
+        raise ValueError(f'slope {slope!r}: must be finite and in (0, 1]')
+    return float(slope)
+
+
+def _check_pixels(name, tensor, pixels):
+    """(the kernels count pixels in 32 bits)"""
+    if pixels > 2 ** 31 - 1:
+        raise ValueError(
+            f'{name} {tuple(tensor.shape)}: more than 2^31 - 1 pixels')
 
 
 def _map_order(tensor):
-    """The memory order of the kernels: 16 channels are channels_last, in
-    memory (B, F, T, 16); one channel is (B, F, T) either way"""
-    if tensor.shape[1] == 1:
+    """The memory order of the kernels: a map of several channels is
+    channels_last, in memory (B, H, W, C); one channel is (B, H, W) either
+    way, and the audio is (B, T)"""
+    if tensor.ndim != 4 or tensor.shape[1] == 1:
         return tensor.contiguous()
     return tensor.contiguous(memory_format=torch.channels_last)
 
 
-def _empty_map(batch, channels, bins, frames, device):
+def _empty_map(shape, device):
     return torch.empty(
-        (batch, channels, bins, frames), device=device, dtype=torch.float32,
-        memory_format=torch.channels_last if channels > 1
+        shape, device=device, dtype=torch.float32,
+        memory_format=torch.channels_last if shape[1] > 1
         else torch.contiguous_format)
 
 
-def _layer_sizes(x, weight, bias, dilation, activation):
-    """(B, C, O, F, T, d, act) of a checked call; ValueError otherwise"""
-    for name, tensor in (('x', x), ('weight', weight), ('bias', bias)):
-        if not isinstance(tensor, torch.Tensor) or \
-                not tensor.is_floating_point():
-            raise ValueError(f'{name} must be a float tensor')
-    if x.ndim != 4 or x.shape[1] not in (1, 16) or not x.numel():
-        raise ValueError(
-            f'x {tuple(x.shape)}: must be (B, C, F, T) with C 1 or 16 and no '
-            'empty axis')
-    batch, channels, bins, frames = x.shape
-    if weight.ndim != 4 or weight.shape[0] not in (1, 16) or \
-            tuple(weight.shape[1:]) != (channels + 2, 3, 3):
-        raise ValueError(
-            f'weight {tuple(weight.shape)}: must be (O, {channels + 2}, 3, 3) '
-            'with O 1 or 16')
-    out_channels = weight.shape[0]
-    if channels == 1 and out_channels == 1:
-        raise ValueError('no layer has one channel on both sides')
-    if tuple(bias.shape) != (out_channels,):
-        raise ValueError(
-            f'bias {tuple(bias.shape)}: must be ({out_channels},)')
-    if isinstance(dilation, (tuple, list)):
-        if len(dilation) != 2 or dilation[1] != 1:
-            raise ValueError(f'dilation {dilation!r}: must be (d, 1)')
-        dilation = dilation[0]
-    if dilation not in DILATIONS:
-        raise ValueError(f'dilation {dilation!r}: must be one of {DILATIONS}')
-    if activation not in _lib.FDISC_ACTIVATIONS:
-        raise ValueError(
-            f'activation {activation!r}: must be one of '
-            f'{tuple(_lib.FDISC_ACTIVATIONS)}')
-    return (batch, channels, out_channels, bins, frames, int(dilation),
-            _lib.FDISC_ACTIVATIONS[activation])
+def _address(tensor):
+    """Of a map in the kernels' memory order (_lib.ptr takes plain contiguous
+    tensors alone), or None"""
+    return None if tensor is None else tensor.data_ptr()
 
 
-class _FrequencyConv(torch.autograd.Function):
-    """backward: gx, gW and gb from the upstream gradient, the saved output
-    and the saved input (pm_fdisc_conv_backward)"""
+class _ConvLayer(torch.autograd.Function):
+    """One conv layer of a stack on its three C entries. `entries` = (forward,
+    backward, workspace_bytes of _lib, the shape of the output from `sizes`);
+    `sizes` are the ints of the workspace query, `scalars` what the two calls
+    take after them (the dilation and the activation, or the slope), `tables`
+    the tensors they take after the weight and the bias (the frequency
+    embedding). backward: gx, gW and gb from the upstream gradient, the saved
+    output and the saved input."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, x, weight, bias, table, sizes):
+    def forward(ctx, x, weight, bias, entries, sizes, scalars, *tables):
         lib = _lib.lib()
-        batch, channels, out_channels, bins, frames = sizes[:5]
         x, weight, bias = _map_order(x), weight.contiguous(), bias.contiguous()
-        y = _empty_map(batch, out_channels, bins, frames, x.device)
+        y = _empty_map(entries[3](*sizes), x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.pm_fdisc_conv_forward(
-                x.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
-                _lib.ptr(table), y.data_ptr(), *sizes, _lib.stream()))
-        ctx.save_for_backward(x, weight, table, y)
-        ctx.sizes = sizes
+            _lib.check(getattr(lib, entries[0])(
+                _address(x), _lib.ptr(weight), _lib.ptr(bias),
+                *map(_lib.ptr, tables), _address(y), *sizes, *scalars,
+                _lib.stream()))
+        ctx.save_for_backward(x, weight, y, *tables)
+        ctx.entries, ctx.sizes, ctx.scalars = entries, sizes, scalars
         return y
 
     @staticmethod
     @torch.amp.custom_bwd(device_type='cuda')
     def backward(ctx, grad):
         lib = _lib.lib()
-        x, weight, table, y = ctx.saved_tensors
-        sizes = ctx.sizes
+        x, weight, y, *tables = ctx.saved_tensors
         grad = _map_order(grad.to(torch.float32))
         need_x, need_weight, need_bias = ctx.needs_input_grad[:3]
         grad_x = torch.empty_like(x) if need_x else None
@@ -298,41 +281,18 @@ class _FrequencyConv(torch.autograd.Function):
         with torch.cuda.device(x.device):
             if need_weight or need_bias:
                 grad_weight = torch.empty_like(weight)
-                grad_bias = torch.empty(sizes[2], device=x.device)
-                workspace = torch.empty(
-                    lib.pm_fdisc_workspace_bytes(*sizes[:5]),
-                    dtype=torch.uint8, device=x.device)
-            _lib.check(lib.pm_fdisc_conv_backward(
-                grad.data_ptr(), y.data_ptr(), x.data_ptr(), _lib.ptr(weight),
-                _lib.ptr(table),
-                None if grad_x is None else grad_x.data_ptr(),
-                _lib.ptr(grad_weight), _lib.ptr(grad_bias), *sizes,
-                None if workspace is None else workspace.data_ptr(),
+                grad_bias = torch.empty(weight.shape[0], device=x.device)
+                workspace = _workspace_of(
+                    getattr(lib, ctx.entries[2])(*ctx.sizes), x.device)
+            _lib.check(getattr(lib, ctx.entries[1])(
+                _address(grad), _address(y), _address(x), _lib.ptr(weight),
+                *map(_lib.ptr, tables), _address(grad_x),
+                _lib.ptr(grad_weight), _lib.ptr(grad_bias), *ctx.sizes,
+                *ctx.scalars, _address(workspace),
                 0 if workspace is None else workspace.numel(), _lib.stream()))
         return (grad_x, grad_weight if need_weight else None,
-                grad_bias if need_bias else None, None, None)
-
-
-def frequency_conv(x, weight, bias, dilation=1, activation='relu', table=None):
-    """One layer of DiscriminatorMagFree (:343-369) without its weight norm:
-    act(conv2d(cat(x, sin, cos), weight, bias, stride 1, dilation (d, 1),
-    padding (d, 1))), sin and cos of 2 pi f / F being the two channels of
-    FrequencyPositionalEmbedding. x (B, C, F, T) on the device with C 1 or 16,
-    weight (O, C + 2, 3, 3) with O 16 or 1, bias (O); activation 'relu',
-    'sigmoid' or 'none'. Returns (B, O, F, T) fp32; with 16 channels it is
-    channels_last in memory, as is the gradient in x. Differentiable in x,
-    weight and bias. Other float dtypes are cast to fp32 and their gradients
-    return in their dtype. `table` (F, 2) replaces sin and cos (the tests'
-    integer embedding)."""
-    sizes = _layer_sizes(x, weight, bias, dilation, activation)
-    if table is not None and tuple(table.shape) != (sizes[3], 2):
-        raise ValueError(f'table {tuple(table.shape)}: must be (F, 2)')
-    _lib.require_gpu(x)
-    if table is None:
-        table = _embedding_table(x.device, sizes[3])
-    return _FrequencyConv.apply(
-        x.to(torch.float32), weight.to(torch.float32),
-        bias.to(torch.float32), table, sizes)
+                grad_bias if need_bias else None, None, None, None,
+                *(None for _ in tables))
 
 
 class _WeightNorm(torch.autograd.Function):
@@ -368,10 +328,7 @@ def weight_norm(g, v):
     """torch._weight_norm(v, g, 0): w = g v / |v| with the norm of each output
     channel over its other axes. g (O, 1, ...) or (O), v (O, ...) on the
     device -> w like v, fp32, differentiable in both."""
-    for name, tensor in (('g', g), ('v', v)):
-        if not isinstance(tensor, torch.Tensor) or \
-                not tensor.is_floating_point():
-            raise ValueError(f'{name} must be a float tensor')
+    _require_float(g=g, v=v)
     if v.ndim < 2 or not v.numel() or g.numel() != v.shape[0] or \
             g.shape[:1] != v.shape[:1]:
         raise ValueError(
@@ -379,6 +336,119 @@ def weight_norm(g, v):
             'channel of v')
     _lib.require_gpu(v)
     return _WeightNorm.apply(g.to(torch.float32), v.to(torch.float32))
+
+
+class _NormedConv2d(torch.nn.Module):
+    """The parameters of a weight-normed Conv2d(channels, out_channels,
+    kernel_size), under the names torch.nn.utils.weight_norm gives; its
+    stride or dilation is an attribute that its stack sets"""
+
+    def __init__(self, channels, out_channels, kernel_size):
+        super().__init__()
+        conv = torch.nn.Conv2d(channels, out_channels, kernel_size)
+        weight = conv.weight.detach()
+        # (in the order weight_norm leaves them: bias, weight_g, weight_v)
+        self.bias = torch.nn.Parameter(conv.bias.detach().clone())
+        self.weight_g = torch.nn.Parameter(
+            weight.flatten(1).norm(dim=1).reshape(-1, 1, 1, 1))
+        self.weight_v = torch.nn.Parameter(weight.clone())
+
+    def weight(self):
+        return weight_norm(self.weight_g, self.weight_v)
+
+
+def _is_normed_conv(conv):
+    """Is `conv` a weight-normed Conv2d with a bias, as the reference's are?"""
+    return isinstance(conv, torch.nn.Conv2d) and conv.bias is not None and \
+        isinstance(getattr(conv, 'weight_g', None), torch.Tensor) and \
+        isinstance(getattr(conv, 'weight_v', None), torch.Tensor)
+
+
+def _normed(conv):
+    return weight_norm(conv.weight_g, conv.weight_v)
+
+
+###############################################################################
+# The conv stacks of DiscriminatorMagFree
+###############################################################################
+
+DILATIONS = (1, 2, 4, 8, 16)
+RESOLUTIONS = (64, 128, 256, 512, 1024, 2048)
+_TABLES = {}
+
+
+def _embedding_table(device, bins):
+    """(bins, 2) fp32 = sin, cos of FrequencyPositionalEmbedding (:381-389),
+    by its own expression on the device; cached per device and size"""
+    key = (str(device), bins)
+    if key not in _TABLES:
+        args = torch.arange(
+            0, bins, dtype=torch.float32, device=device) * torch.pi * 2 / bins
+        _TABLES[key] = torch.stack(
+            (torch.sin(args), torch.cos(args)), dim=1).contiguous()
+    return _TABLES[key]
+
+
+def _layer_sizes(x, weight, bias, dilation, activation):
+    """((B, C, O, F, T), (d, act)) of a checked call; ValueError otherwise"""
+    _require_float(x=x, weight=weight, bias=bias)
+    if x.ndim != 4 or x.shape[1] not in (1, 16) or not x.numel():
+        raise ValueError(
+            f'x {tuple(x.shape)}: must be (B, C, F, T) with C 1 or 16 and no '
+            'empty axis')
+    batch, channels, bins, frames = x.shape
+    if weight.ndim != 4 or weight.shape[0] not in (1, 16) or \
+            tuple(weight.shape[1:]) != (channels + 2, 3, 3):
+        raise ValueError(
+            f'weight {tuple(weight.shape)}: must be (O, {channels + 2}, 3, 3) '
+            'with O 1 or 16')
+    out_channels = weight.shape[0]
+    if channels == 1 and out_channels == 1:
+        raise ValueError('no layer has one channel on both sides')
+    if tuple(bias.shape) != (out_channels,):
+        raise ValueError(
+            f'bias {tuple(bias.shape)}: must be ({out_channels},)')
+    if isinstance(dilation, (tuple, list)):
+        if len(dilation) != 2 or dilation[1] != 1:
+            raise ValueError(f'dilation {dilation!r}: must be (d, 1)')
+        dilation = dilation[0]
+    if dilation not in DILATIONS:
+        raise ValueError(f'dilation {dilation!r}: must be one of {DILATIONS}')
+    if activation not in _lib.FDISC_ACTIVATIONS:
+        raise ValueError(
+            f'activation {activation!r}: must be one of '
+            f'{tuple(_lib.FDISC_ACTIVATIONS)}')
+    return (batch, channels, out_channels, bins, frames), \
+        (int(dilation), _lib.FDISC_ACTIVATIONS[activation])
+
+
+_FREQUENCY_ENTRIES = (
+    'pm_fdisc_conv_forward', 'pm_fdisc_conv_backward',
+    'pm_fdisc_workspace_bytes',
+    lambda batch, channels, out_channels, bins, frames:
+        (batch, out_channels, bins, frames))
+
+
+def frequency_conv(x, weight, bias, dilation=1, activation='relu', table=None):
+    """One layer of DiscriminatorMagFree (:343-369) without its weight norm:
+    act(conv2d(cat(x, sin, cos), weight, bias, stride 1, dilation (d, 1),
+    padding (d, 1))), sin and cos of 2 pi f / F being the two channels of
+    FrequencyPositionalEmbedding. x (B, C, F, T) on the device with C 1 or 16,
+    weight (O, C + 2, 3, 3) with O 16 or 1, bias (O); activation 'relu',
+    'sigmoid' or 'none'. Returns (B, O, F, T) fp32; with 16 channels it is
+    channels_last in memory, as is the gradient in x. Differentiable in x,
+    weight and bias. Other float dtypes are cast to fp32 and their gradients
+    return in their dtype. `table` (F, 2) replaces sin and cos (the tests'
+    integer embedding)."""
+    sizes, scalars = _layer_sizes(x, weight, bias, dilation, activation)
+    if table is not None and tuple(table.shape) != (sizes[3], 2):
+        raise ValueError(f'table {tuple(table.shape)}: must be (F, 2)')
+    _lib.require_gpu(x)
+    if table is None:
+        table = _embedding_table(x.device, sizes[3])
+    return _ConvLayer.apply(
+        x.to(torch.float32), weight.to(torch.float32),
+        bias.to(torch.float32), _FREQUENCY_ENTRIES, sizes, scalars, table)
 
 
 def magfree_plan(n_fft):
@@ -405,20 +475,12 @@ class FrequencyPositionalEmbedding(torch.nn.Identity):
     add the embedding themselves."""
 
 
-class _NormedConv(torch.nn.Module):
-    """Slot 1 of a layer: the parameters of a weight-normed Conv2d(channels +
-    2, out_channels, 3), under the names torch.nn.utils.weight_norm gives"""
-
-    def __init__(self, channels, out_channels, dilation):
-        super().__init__()
-        conv = torch.nn.Conv2d(channels + 2, out_channels, 3)
-        weight = conv.weight.detach()
-        # (in the order weight_norm leaves them: bias, weight_g, weight_v)
-        self.bias = torch.nn.Parameter(conv.bias.detach().clone())
-        self.weight_g = torch.nn.Parameter(
-            weight.flatten(1).norm(dim=1).reshape(-1, 1, 1, 1))
-        self.weight_v = torch.nn.Parameter(weight.clone())
-        self.dilation = dilation
+def _frequency_module(channels, out_channels, dilation):
+    """Slot 1 of a layer: the parameters of its conv over the map and the two
+    channels of the embedding"""
+    conv = _NormedConv2d(channels + 2, out_channels, 3)
+    conv.dilation = dilation
+    return conv
 
 
 class DiscriminatorMagFree(torch.nn.Module):
@@ -450,7 +512,7 @@ class DiscriminatorMagFree(torch.nn.Module):
             last = out_channels == 1
             layers.append(torch.nn.Sequential(
                 FrequencyPositionalEmbedding(),
-                _NormedConv(channels, out_channels, dilation),
+                _frequency_module(channels, out_channels, dilation),
                 torch.nn.Sigmoid() if last else torch.nn.ReLU()))
         self.layers = torch.nn.ModuleList(layers)
         bins = self.resolution[0] // 2 + 1
@@ -464,8 +526,7 @@ class DiscriminatorMagFree(torch.nn.Module):
         for layer in self.layers:
             conv = layer[1]
             x = frequency_conv(
-                x, weight_norm(conv.weight_g, conv.weight_v), conv.bias,
-                conv.dilation,
+                x, conv.weight(), conv.bias, conv.dilation,
                 'sigmoid' if isinstance(layer[2], torch.nn.Sigmoid)
                 else 'relu')
             maps.append(x)
@@ -488,10 +549,7 @@ def _stack_layers(self):
             return None
         embedding, conv, activation = layer
         if type(embedding).__name__ != 'FrequencyPositionalEmbedding' or \
-                not isinstance(conv, torch.nn.Conv2d) or \
-                not isinstance(getattr(conv, 'weight_g', None), torch.Tensor) \
-                or not isinstance(getattr(conv, 'weight_v', None),
-                                  torch.Tensor) or conv.bias is None:
+                not _is_normed_conv(conv):
             return None
         if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or \
                 conv.groups != 1 or conv.padding_mode != 'zeros' or \
@@ -521,8 +579,7 @@ def _wrap_forward(original):
         output = []
         for conv, dilation, activation in layers:
             x = frequency_conv(
-                x, weight_norm(conv.weight_g, conv.weight_v), conv.bias,
-                dilation, activation)
+                x, _normed(conv), conv.bias, dilation, activation)
             output.append(x)
         return torch.flatten(output[-1], 1, -1), output[:-1]
     forward.original = original
@@ -538,12 +595,9 @@ BAND_FORMS = ((1, 32, 9, 1), (32, 32, 9, 2), (32, 32, 3, 1), (32, 1, 3, 1))
 
 
 def _band_sizes(x, weight, bias, stride, slope):
-    """((B, C, O, H, W, kw, s), slope) of a checked call; ValueError
+    """((B, C, O, H, W, kw, s), (slope,)) of a checked call; ValueError
     otherwise"""
-    for name, tensor in (('x', x), ('weight', weight), ('bias', bias)):
-        if not isinstance(tensor, torch.Tensor) or \
-                not tensor.is_floating_point():
-            raise ValueError(f'{name} must be a float tensor')
+    _require_float(x=x, weight=weight, bias=bias)
     if x.ndim != 4 or not x.numel():
         raise ValueError(
             f'x {tuple(x.shape)}: must be (B, C, H, W) with no empty axis')
@@ -567,60 +621,16 @@ def _band_sizes(x, weight, bias, stride, slope):
     if tuple(bias.shape) != (out_channels,):
         raise ValueError(
             f'bias {tuple(bias.shape)}: must be ({out_channels},)')
-    if isinstance(slope, bool) or not isinstance(slope, (int, float)) or \
-            not math.isfinite(slope) or not 0. < slope <= 1.:
-        raise ValueError(f'slope {slope!r}: must be finite and in (0, 1]')
-    if batch * height * width > 2 ** 31 - 1:
-        raise ValueError(f'x {tuple(x.shape)}: more than 2^31 - 1 pixels')
+    slope = _check_slope(slope)
+    _check_pixels('x', x, batch * height * width)
     return (batch, channels, out_channels, height, width, weight.shape[3],
-            int(stride)), float(slope)
+            int(stride)), (slope,)
 
 
-class _BandConv(torch.autograd.Function):
-    """backward: gx, gW and gb from the upstream gradient, the saved output
-    and the saved input (pm_dconv_backward)"""
-
-    @staticmethod
-    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, x, weight, bias, sizes, slope):
-        lib = _lib.lib()
-        batch, _, out_channels, height, width, _, stride = sizes
-        x, weight, bias = _map_order(x), weight.contiguous(), bias.contiguous()
-        y = _empty_map(
-            batch, out_channels, height, (width - 1) // stride + 1, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.pm_dconv_forward(
-                x.data_ptr(), _lib.ptr(weight), _lib.ptr(bias), y.data_ptr(),
-                *sizes, slope, _lib.stream()))
-        ctx.save_for_backward(x, weight, y)
-        ctx.sizes, ctx.slope = sizes, slope
-        return y
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type='cuda')
-    def backward(ctx, grad):
-        lib = _lib.lib()
-        x, weight, y = ctx.saved_tensors
-        sizes = ctx.sizes
-        grad = _map_order(grad.to(torch.float32))
-        need_x, need_weight, need_bias = ctx.needs_input_grad[:3]
-        grad_x = torch.empty_like(x) if need_x else None
-        grad_weight = grad_bias = workspace = None
-        with torch.cuda.device(x.device):
-            if need_weight or need_bias:
-                grad_weight = torch.empty_like(weight)
-                grad_bias = torch.empty(sizes[2], device=x.device)
-                workspace = torch.empty(
-                    lib.pm_dconv_workspace_bytes(*sizes), dtype=torch.uint8,
-                    device=x.device)
-            _lib.check(lib.pm_dconv_backward(
-                grad.data_ptr(), y.data_ptr(), x.data_ptr(), _lib.ptr(weight),
-                None if grad_x is None else grad_x.data_ptr(),
-                _lib.ptr(grad_weight), _lib.ptr(grad_bias), *sizes, ctx.slope,
-                None if workspace is None else workspace.data_ptr(),
-                0 if workspace is None else workspace.numel(), _lib.stream()))
-        return (grad_x, grad_weight if need_weight else None,
-                grad_bias if need_bias else None, None, None)
+_BAND_ENTRIES = (
+    'pm_dconv_forward', 'pm_dconv_backward', 'pm_dconv_workspace_bytes',
+    lambda batch, channels, out_channels, height, width, kernel_width, stride:
+        (batch, out_channels, height, (width - 1) // stride + 1))
 
 
 def band_conv(x, weight, bias, stride=1, slope=1.0):
@@ -634,32 +644,21 @@ def band_conv(x, weight, bias, stride=1, slope=1.0):
     one-channel x that is not contiguous (a band of the spectrogram) is copied
     once. Differentiable in x, weight and bias. Other float dtypes are cast to
     fp32 and their gradients return in their dtype."""
-    sizes, slope = _band_sizes(x, weight, bias, stride, slope)
+    sizes, scalars = _band_sizes(x, weight, bias, stride, slope)
     _lib.require_gpu(x)
-    return _BandConv.apply(
+    return _ConvLayer.apply(
         x.to(torch.float32), weight.to(torch.float32),
-        bias.to(torch.float32), sizes, slope)
+        bias.to(torch.float32), _BAND_ENTRIES, sizes, scalars)
 
 
-class _NormedBandConv(torch.nn.Module):
-    """The parameters of a weight-normed Conv2d(channels, out_channels, (3,
-    kernel_width), (1, stride)), under the names torch.nn.utils.weight_norm
-    gives"""
+def _band_module(channels, out_channels, kernel_width, stride):
+    conv = _NormedConv2d(channels, out_channels, (3, kernel_width))
+    conv.stride = stride
+    return conv
 
-    def __init__(self, channels, out_channels, kernel_width, stride):
-        super().__init__()
-        conv = torch.nn.Conv2d(channels, out_channels, (3, kernel_width))
-        weight = conv.weight.detach()
-        self.bias = torch.nn.Parameter(conv.bias.detach().clone())
-        self.weight_g = torch.nn.Parameter(
-            weight.flatten(1).norm(dim=1).reshape(-1, 1, 1, 1))
-        self.weight_v = torch.nn.Parameter(weight.clone())
-        self.stride = stride
 
-    def apply_to(self, x, slope):
-        return band_conv(
-            x, weight_norm(self.weight_g, self.weight_v), self.bias,
-            self.stride, slope)
+def _apply_band(conv, x, slope):
+    return band_conv(x, conv.weight(), conv.bias, conv.stride, slope)
 
 
 class DiscriminatorCMB(torch.nn.Module):
@@ -675,11 +674,11 @@ class DiscriminatorCMB(torch.nn.Module):
         self.band_convs = torch.nn.ModuleList([
             torch.nn.ModuleList([
                 torch.nn.Sequential(
-                    _NormedBandConv(*form), torch.nn.LeakyReLU(0.1))
+                    _band_module(*form), torch.nn.LeakyReLU(0.1))
                 for form in BAND_FORMS[:1] + BAND_FORMS[1:2] * 3 +
                 BAND_FORMS[2:3]])
             for _ in self.bands])
-        self.conv_post = _NormedBandConv(*BAND_FORMS[3])
+        self.conv_post = _band_module(*BAND_FORMS[3])
 
     def stack(self, bands_list):
         """The band tensors (B, 1, frames, bins of the band) -> (logits (B,
@@ -687,10 +686,10 @@ class DiscriminatorCMB(torch.nn.Module):
         last, maps = [], []
         for band, convs in zip(bands_list, self.band_convs):
             for layer in convs:
-                band = layer[0].apply_to(band, layer[1].negative_slope)
+                band = _apply_band(layer[0], band, layer[1].negative_slope)
                 maps.append(band)
             last.append(band)
-        logits = self.conv_post.apply_to(torch.cat(last, dim=-1), 1.)
+        logits = _apply_band(self.conv_post, torch.cat(last, dim=-1), 1.)
         maps.append(logits)
         return logits, maps
 
@@ -713,19 +712,19 @@ class DiscriminatorR(torch.nn.Module):
         super().__init__()
         self.resolution = tuple(int(v) for v in resolution)
         self.convs = torch.nn.ModuleList([
-            _NormedBandConv(*form)
+            _band_module(*form)
             for form in BAND_FORMS[:1] + BAND_FORMS[1:2] * 3 +
             BAND_FORMS[2:3]])
-        self.conv_post = _NormedBandConv(*BAND_FORMS[3])
+        self.conv_post = _band_module(*BAND_FORMS[3])
 
     def stack(self, x):
         """x (B, 1, bins, frames) -> (logits (B, 1, bins, width), the six
         maps)"""
         maps = []
         for conv in self.convs:
-            x = conv.apply_to(x, self.SLOPE)
+            x = _apply_band(conv, x, self.SLOPE)
             maps.append(x)
-        logits = self.conv_post.apply_to(x, 1.)
+        logits = _apply_band(self.conv_post, x, 1.)
         maps.append(logits)
         return logits, maps
 
@@ -739,9 +738,7 @@ class DiscriminatorR(torch.nn.Module):
 def _band_form(conv, channels):
     """The stride of a weight-normed Conv2d of one of BAND_FORMS that takes
     `channels` channels, or None"""
-    if not isinstance(conv, torch.nn.Conv2d) or conv.bias is None or \
-            not isinstance(getattr(conv, 'weight_g', None), torch.Tensor) or \
-            not isinstance(getattr(conv, 'weight_v', None), torch.Tensor):
+    if not _is_normed_conv(conv):
         return None
     kernel_width = conv.kernel_size[1]
     if conv.kernel_size[0] != 3 or conv.stride[0] != 1 or \
@@ -752,10 +749,6 @@ def _band_form(conv, channels):
             not in BAND_FORMS:
         return None
     return conv.stride[1]
-
-
-def _normed(conv):
-    return weight_norm(conv.weight_g, conv.weight_v)
 
 
 def _cmb_layers(self):
@@ -856,13 +849,6 @@ PERIOD_FORMS = ((1, 32, 5, 3), (32, 128, 5, 3), (128, 512, 5, 3),
 PERIODS = (2, 3, 5, 7, 11)
 
 
-def _check_slope(slope):
-    if isinstance(slope, bool) or not isinstance(slope, (int, float)) or \
-            not math.isfinite(slope) or not 0. < slope <= 1.:
-        raise ValueError(f'slope {slope!r}: must be finite and in (0, 1]')
-    return float(slope)
-
-
 def _check_period(period):
     if isinstance(period, bool) or not isinstance(period, int) or \
             not 1 <= period <= 64:
@@ -873,10 +859,7 @@ def _check_period(period):
 def _check_parameters(weight, bias, forms, stride):
     """The form of a checked (weight, bias) at a stride; ValueError
     otherwise"""
-    for name, tensor in (('weight', weight), ('bias', bias)):
-        if not isinstance(tensor, torch.Tensor) or \
-                not tensor.is_floating_point():
-            raise ValueError(f'{name} must be a float tensor')
+    _require_float(weight=weight, bias=bias)
     if isinstance(stride, (tuple, list)):
         if len(stride) != 2 or stride[1] != 1:
             raise ValueError(f'stride {stride!r}: must be (s, 1)')
@@ -895,10 +878,9 @@ def _check_parameters(weight, bias, forms, stride):
 
 
 def _period_sizes(x, weight, bias, stride, slope):
-    """((B, C, O, H, P, k, s), slope) of a checked call; ValueError
+    """((B, C, O, H, P, k, s), (slope,)) of a checked call; ValueError
     otherwise"""
-    if not isinstance(x, torch.Tensor) or not x.is_floating_point():
-        raise ValueError('x must be a float tensor')
+    _require_float(x=x)
     if x.ndim != 4 or not x.numel():
         raise ValueError(
             f'x {tuple(x.shape)}: must be (B, C, H, P) with no empty axis')
@@ -910,15 +892,14 @@ def _period_sizes(x, weight, bias, stride, slope):
             f'{form[0]} channels')
     _check_period(period)
     slope = _check_slope(slope)
-    if batch * height * period > 2 ** 31 - 1:
-        raise ValueError(f'x {tuple(x.shape)}: more than 2^31 - 1 pixels')
-    return (batch, channels, form[1], height, period, form[2], form[3]), slope
+    _check_pixels('x', x, batch * height * period)
+    return (batch, channels, form[1], height, period, form[2], form[3]), \
+        (slope,)
 
 
 def _fold_sizes(audio, weight, bias, period, slope):
-    """((B, T, P), slope) of a checked call; ValueError otherwise"""
-    if not isinstance(audio, torch.Tensor) or not audio.is_floating_point():
-        raise ValueError('audio must be a float tensor')
+    """((B, T, P), (slope,)) of a checked call; ValueError otherwise"""
+    _require_float(audio=audio)
     if not (audio.ndim == 2 or (audio.ndim == 3 and audio.shape[1] == 1)) or \
             not audio.numel():
         raise ValueError(
@@ -932,108 +913,21 @@ def _fold_sizes(audio, weight, bias, period, slope):
     if samples <= pad:
         raise ValueError(
             f'{samples} samples: reflect padding needs more than {pad}')
-    if batch * (samples + pad) > 2 ** 31 - 1:
-        raise ValueError(
-            f'audio {tuple(audio.shape)}: more than 2^31 - 1 pixels')
-    return (batch, samples, period), slope
+    _check_pixels('audio', audio, batch * (samples + pad))
+    return (batch, samples, period), (slope,)
 
 
-def _workspace_of(size, device):
-    return torch.empty(size, dtype=torch.uint8, device=device)
-
-
-class _PeriodConv(torch.autograd.Function):
-    """backward: gx, gW and gb from the upstream gradient, the saved output
-    and the saved input (pm_pconv_backward)"""
-
-    @staticmethod
-    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, x, weight, bias, sizes, slope):
-        lib = _lib.lib()
-        batch, _, out_channels, height, period, _, stride = sizes
-        x, weight, bias = _map_order(x), weight.contiguous(), bias.contiguous()
-        y = _empty_map(
-            batch, out_channels, (height - 1) // stride + 1, period, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.pm_pconv_forward(
-                x.data_ptr(), _lib.ptr(weight), _lib.ptr(bias), y.data_ptr(),
-                *sizes, slope, _lib.stream()))
-        ctx.save_for_backward(x, weight, y)
-        ctx.sizes, ctx.slope = sizes, slope
-        return y
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type='cuda')
-    def backward(ctx, grad):
-        lib = _lib.lib()
-        x, weight, y = ctx.saved_tensors
-        sizes = ctx.sizes
-        grad = _map_order(grad.to(torch.float32))
-        need_x, need_weight, need_bias = ctx.needs_input_grad[:3]
-        grad_x = torch.empty_like(x) if need_x else None
-        grad_weight = grad_bias = workspace = None
-        with torch.cuda.device(x.device):
-            if need_weight or need_bias:
-                grad_weight = torch.empty_like(weight)
-                grad_bias = torch.empty(sizes[2], device=x.device)
-                workspace = _workspace_of(
-                    lib.pm_pconv_workspace_bytes(*sizes), x.device)
-            _lib.check(lib.pm_pconv_backward(
-                grad.data_ptr(), y.data_ptr(), x.data_ptr(), _lib.ptr(weight),
-                None if grad_x is None else grad_x.data_ptr(),
-                _lib.ptr(grad_weight), _lib.ptr(grad_bias), *sizes, ctx.slope,
-                None if workspace is None else workspace.data_ptr(),
-                0 if workspace is None else workspace.numel(), _lib.stream()))
-        return (grad_x, grad_weight if need_weight else None,
-                grad_bias if need_bias else None, None, None)
-
-
-class _PeriodFoldConv(torch.autograd.Function):
-    """The first layer on the audio (B, T); backward: the gradient in the
-    audio with the adjoint of the reflection, gW and gb
-    (pm_pconv_fold_backward)"""
-
-    @staticmethod
-    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, audio, weight, bias, sizes, slope):
-        lib = _lib.lib()
-        batch, samples, period = sizes
-        audio, weight, bias = \
-            audio.contiguous(), weight.contiguous(), bias.contiguous()
-        height = -(-samples // period)
-        y = _empty_map(batch, 32, (height - 1) // 3 + 1, period, audio.device)
-        with torch.cuda.device(audio.device):
-            _lib.check(lib.pm_pconv_fold_forward(
-                _lib.ptr(audio), _lib.ptr(weight), _lib.ptr(bias),
-                y.data_ptr(), *sizes, slope, _lib.stream()))
-        ctx.save_for_backward(audio, weight, y)
-        ctx.sizes, ctx.slope = sizes, slope
-        return y
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type='cuda')
-    def backward(ctx, grad):
-        lib = _lib.lib()
-        audio, weight, y = ctx.saved_tensors
-        sizes = ctx.sizes
-        grad = _map_order(grad.to(torch.float32))
-        need_audio, need_weight, need_bias = ctx.needs_input_grad[:3]
-        grad_audio = torch.empty_like(audio) if need_audio else None
-        grad_weight = grad_bias = workspace = None
-        with torch.cuda.device(audio.device):
-            if need_weight or need_bias:
-                grad_weight = torch.empty_like(weight)
-                grad_bias = torch.empty(32, device=audio.device)
-                workspace = _workspace_of(
-                    lib.pm_pconv_fold_workspace_bytes(*sizes), audio.device)
-            _lib.check(lib.pm_pconv_fold_backward(
-                grad.data_ptr(), y.data_ptr(), _lib.ptr(audio),
-                _lib.ptr(weight), _lib.ptr(grad_audio), _lib.ptr(grad_weight),
-                _lib.ptr(grad_bias), *sizes, ctx.slope,
-                None if workspace is None else workspace.data_ptr(),
-                0 if workspace is None else workspace.numel(), _lib.stream()))
-        return (grad_audio, grad_weight if need_weight else None,
-                grad_bias if need_bias else None, None, None)
+_PERIOD_ENTRIES = (
+    'pm_pconv_forward', 'pm_pconv_backward', 'pm_pconv_workspace_bytes',
+    lambda batch, channels, out_channels, height, period, kernel, stride:
+        (batch, out_channels, (height - 1) // stride + 1, period))
+# the first layer on the audio (B, T): the gradient in the audio holds the
+# adjoint of the reflection
+_FOLD_ENTRIES = (
+    'pm_pconv_fold_forward', 'pm_pconv_fold_backward',
+    'pm_pconv_fold_workspace_bytes',
+    lambda batch, samples, period:
+        (batch, 32, (-(-samples // period) - 1) // 3 + 1, period))
 
 
 def period_conv(x, weight, bias, stride=1, slope=1.0):
@@ -1046,11 +940,11 @@ def period_conv(x, weight, bias, stride=1, slope=1.0):
     channels_last in memory, as is the gradient in x. Differentiable in x,
     weight and bias. Other float dtypes are cast to fp32 and their gradients
     return in their dtype."""
-    sizes, slope = _period_sizes(x, weight, bias, stride, slope)
+    sizes, scalars = _period_sizes(x, weight, bias, stride, slope)
     _lib.require_gpu(x)
-    return _PeriodConv.apply(
+    return _ConvLayer.apply(
         x.to(torch.float32), weight.to(torch.float32),
-        bias.to(torch.float32), sizes, slope)
+        bias.to(torch.float32), _PERIOD_ENTRIES, sizes, scalars)
 
 
 def period_fold_conv(audio, weight, bias, period, slope=1.0):
@@ -1061,31 +955,18 @@ def period_fold_conv(audio, weight, bias, period, slope=1.0):
     (32). Returns (B, 32, Ho, period) fp32, channels_last. Differentiable in
     the audio (the gradient has the audio's shape and holds the adjoint of the
     reflection), weight and bias."""
-    sizes, slope = _fold_sizes(audio, weight, bias, period, slope)
+    sizes, scalars = _fold_sizes(audio, weight, bias, period, slope)
     _lib.require_gpu(audio)
-    out = _PeriodFoldConv.apply(
+    return _ConvLayer.apply(
         audio.to(torch.float32).reshape(sizes[0], sizes[1]),
-        weight.to(torch.float32), bias.to(torch.float32), sizes, slope)
-    return out
+        weight.to(torch.float32), bias.to(torch.float32), _FOLD_ENTRIES,
+        sizes, scalars)
 
 
-class _NormedPeriodConv(torch.nn.Module):
-    """The parameters of a weight-normed Conv2d(channels, out_channels,
-    (kernel, 1), (stride, 1)), under the names torch.nn.utils.weight_norm
-    gives"""
-
-    def __init__(self, channels, out_channels, kernel, stride):
-        super().__init__()
-        conv = torch.nn.Conv2d(channels, out_channels, (kernel, 1))
-        weight = conv.weight.detach()
-        self.bias = torch.nn.Parameter(conv.bias.detach().clone())
-        self.weight_g = torch.nn.Parameter(
-            weight.flatten(1).norm(dim=1).reshape(-1, 1, 1, 1))
-        self.weight_v = torch.nn.Parameter(weight.clone())
-        self.stride = stride
-
-    def weight(self):
-        return weight_norm(self.weight_g, self.weight_v)
+def _period_module(channels, out_channels, kernel, stride):
+    conv = _NormedConv2d(channels, out_channels, (kernel, 1))
+    conv.stride = stride
+    return conv
 
 
 class DiscriminatorP(torch.nn.Module):
@@ -1099,8 +980,8 @@ class DiscriminatorP(torch.nn.Module):
         super().__init__()
         self.period = _check_period(period)
         self.convs = torch.nn.ModuleList(
-            [_NormedPeriodConv(*form) for form in PERIOD_FORMS[:5]])
-        self.conv_post = _NormedPeriodConv(*PERIOD_FORMS[5])
+            [_period_module(*form) for form in PERIOD_FORMS[:5]])
+        self.conv_post = _period_module(*PERIOD_FORMS[5])
 
     def stack(self, audio):
         """audio (B, 1, T) -> (logits (B, 1, H, period), the six maps)"""
@@ -1159,10 +1040,7 @@ def _period_form(conv, form):
     """Is `conv` a weight-normed Conv2d of `form`, the stride and the padding
     on the height?"""
     channels, out_channels, kernel, stride = form
-    return isinstance(conv, torch.nn.Conv2d) and conv.bias is not None and \
-        isinstance(getattr(conv, 'weight_g', None), torch.Tensor) and \
-        isinstance(getattr(conv, 'weight_v', None), torch.Tensor) and \
-        conv.in_channels == channels and \
+    return _is_normed_conv(conv) and conv.in_channels == channels and \
         conv.out_channels == out_channels and \
         tuple(conv.kernel_size) == (kernel, 1) and \
         tuple(conv.stride) == (stride, 1) and \

@@ -27,7 +27,6 @@ Prints one JSON line and writes profiles/dconv/bench.json (or --output).
 """
 import argparse
 import json
-import statistics
 import sys
 from pathlib import Path
 
@@ -36,8 +35,8 @@ import torch
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from promonet_amd.model import discriminator  # noqa: E402
+from disc_timing import ROUNDS, timed  # noqa: E402
 
-ROUNDS = 7
 BATCH, FRAMES, BINS = 64, 64, 513
 RESOLUTION = (1024, 120, 600)
 R_FRAMES = 1 + (16384 + 2 * ((1024 - 120) // 2) - 1024) // 120
@@ -96,26 +95,6 @@ def layer_costs(inputs, chains, post):
         backward += 4 * pixels * (4 + 64)
         flop += 2 * post.weight_v.numel() * pixels
     return forward, forward + backward, flop
-
-
-def timed(functions, calls):
-    """Interleaved: every round times each function once, `calls` calls"""
-    for function in functions.values():
-        function()
-    torch.cuda.synchronize()
-    start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
-    rounds = {name: [] for name in functions}
-    for _ in range(ROUNDS):
-        for name, function in functions.items():
-            start.record()
-            for _ in range(calls):
-                function()
-            end.record()
-            end.synchronize()
-            rounds[name].append(start.elapsed_time(end) * 1e3 / calls)
-    return {name: {'median_us': statistics.median(r), 'min_us': min(r),
-                   'max_us': max(r), 'calls_per_round': calls}
-            for name, r in rounds.items()}
 
 
 def main():

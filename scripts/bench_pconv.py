@@ -30,7 +30,6 @@ Prints one JSON line and writes profiles/pconv/bench.json (or --output).
 """
 import argparse
 import json
-import statistics
 import sys
 from pathlib import Path
 
@@ -40,8 +39,8 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from promonet_amd import _lib  # noqa: E402
 from promonet_amd.model import discriminator  # noqa: E402
+from disc_timing import ROUNDS, timed  # noqa: E402
 
-ROUNDS = 7
 BATCH, SAMPLES = 64, 16384
 SLOPE = 0.1
 MATRIX_FP32 = 155e12        # the fp32 matrix rate the ratios are quoted against
@@ -117,26 +116,6 @@ def costs(members):
             flop += 2 * weights * out_pixels
             height = out_height
     return forward, forward + backward, flop
-
-
-def timed(functions, calls):
-    """Interleaved: every round times each function once, `calls` calls"""
-    for function in functions.values():
-        function()
-    torch.cuda.synchronize()
-    start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
-    rounds = {name: [] for name in functions}
-    for _ in range(ROUNDS):
-        for name, function in functions.items():
-            start.record()
-            for _ in range(calls):
-                function()
-            end.record()
-            end.synchronize()
-            rounds[name].append(start.elapsed_time(end) * 1e3 / calls)
-    return {name: {'median_us': statistics.median(r), 'min_us': min(r),
-                   'max_us': max(r), 'calls_per_round': calls}
-            for name, r in rounds.items()}
 
 
 def main():
