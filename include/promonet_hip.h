@@ -242,6 +242,17 @@ int pm_block_iteration_cl(int dtype, const float* x_cl, float* out_cl,
                           int channels, int kernel_size, int dilation,
                           int mode, float scale, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* pm_block_iteration_cl on a ragged batch, as a forward with `lengths` launches
+ * the layer: lengths (B) int32 on the device, rows per utterance (clamped to
+ * `length`). Rows of x past lengths[b] read as zero, and the rows of out_cl
+ * past lengths[b] are neither read nor written. */
+int pm_block_iteration_ragged_cl(int dtype, const float* x_cl, float* out_cl,
+                                 const float* w1, const float* b1,
+                                 const float* w2, const float* b2,
+                                 const int* lengths, int batch, int length,
+                                 int channels, int kernel_size, int dilation,
+                                 int mode, float scale, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 /* A whole Block (hifigan.py:198-210), all `niter` <= 3 dilations fused in
  * one kernel: 16-bit operands for channels <= 64 at every k, 128 at k 3 and -
  * walked / skewed variants, taken for long inputs or through pm_debug_force -

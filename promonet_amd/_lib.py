@@ -83,6 +83,8 @@ SIGNATURES = {
     'pm_prepare_global_features_linear': (_I, [_P] * 6 + [_I, _I, _I, _P]),
     'pm_op_workspace_bytes': (_S, [_I, _I, _I]),
     'pm_block_iteration_cl': (_I, [_I] + [_P] * 6 + [_I] * 6 + [_F, _P, _S, _P]),
+    'pm_block_iteration_ragged_cl': (
+        _I, [_I] + [_P] * 7 + [_I] * 6 + [_F, _P, _S, _P]),
     'pm_block_cl': (_I, [_I, _P, _P] + [_P] * 5 + [_I] * 6 + [_F, _P, _S, _P]),
     'pm_block_act16_cl': (
         _I, [_I, _I, _P, _P, _P] + [_P] * 5 + [_I] * 6 + [_F, _P, _S, _P]),

@@ -1146,10 +1146,11 @@ static int pack_iteration(
     return PM_OK;
 }
 
-extern "C" int pm_block_iteration_cl(
+static int block_iteration_cl_impl(
     int dtype, const float* x, float* out, const float* w1, const float* b1,
-    const float* w2, const float* b2, int B, int L, int C, int K, int d,
-    int mode, float scale, void* ws, size_t ws_bytes, void* stream) {
+    const float* w2, const float* b2, const int* lengths, int B, int L, int C,
+    int K, int d, int mode, float scale, void* ws, size_t ws_bytes,
+    void* stream) {
     if (!x || !out || !w1 || !b1 || !w2 || !b2 || !ws)
         return pm_fail(PM_EINVAL, "null argument");
     const int Cp = pm_pad32(C);
@@ -1167,8 +1168,32 @@ extern "C" int pm_block_iteration_cl(
     PairArgs a = {};
     a.x = x; a.out = out; a.w1 = p1; a.w2 = p2;
     a.B = B; a.L = L; a.dilation = d; a.mode = mode; a.scale = scale;
+    a.lengths = lengths; a.len_scale = 1;
     PM_HIP_TRY(launch_pair(dtype, Cp, K, a, s));
     return PM_OK;
+}
+
+extern "C" int pm_block_iteration_cl(
+    int dtype, const float* x, float* out, const float* w1, const float* b1,
+    const float* w2, const float* b2, int B, int L, int C, int K, int d,
+    int mode, float scale, void* ws, size_t ws_bytes, void* stream) {
+    return block_iteration_cl_impl(dtype, x, out, w1, b1, w2, b2, nullptr, B,
+                                   L, C, K, d, mode, scale, ws, ws_bytes,
+                                   stream);
+}
+
+// pm_block_iteration_cl on a ragged batch, as a forward with `lengths`
+// launches the layer: utterance b has lengths[b] rows (device int32, clamped
+// to `length`); rows past them are neither read nor written.
+extern "C" int pm_block_iteration_ragged_cl(
+    int dtype, const float* x, float* out, const float* w1, const float* b1,
+    const float* w2, const float* b2, const int* lengths, int B, int L, int C,
+    int K, int d, int mode, float scale, void* ws, size_t ws_bytes,
+    void* stream) {
+    if (!lengths) return pm_fail(PM_EINVAL, "null argument");
+    return block_iteration_cl_impl(dtype, x, out, w1, b1, w2, b2, lengths, B,
+                                   L, C, K, d, mode, scale, ws, ws_bytes,
+                                   stream);
 }
 
 // Debug (-DPM_TUNING builds): subsequent pair / whole-Block launches make

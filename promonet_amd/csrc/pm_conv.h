@@ -561,6 +561,230 @@ __device__ __forceinline__ void store_tile_lrelu(
 }
 
 // ---------------------------------------------------------------------------
+// Row stores. The outputs here are (B, L, M) with M floats a column. In the
+// MFMA C/D layout a lane holds one column, so a direct b128 store writes 32
+// pieces of 32 bytes, one per column: 32-byte write requests to the L2.
+// pm_store_rows turns a wave's 32-column tiles round, CP columns at a time,
+// in an LDS buffer of the wave's own (no workgroup barrier: pm_wave_lds_sync)
+// and stores them with RUN / 16 lanes on one column's run of MTW * 32 floats:
+// whole 128-byte lines, half the write requests. Same acc + bias additions,
+// the same bytes. Read by one later launch only, hence non-temporal: such
+// stores do not wait in the L2 to be merged, which whole lines do not need
+// (on the 32-byte pieces of the direct stores nt takes 2.4 times as long).
+// ---------------------------------------------------------------------------
+#ifndef PM_ROWS_AUX
+#define PM_ROWS_AUX 2       // nt
+#endif
+#ifndef PM_SINGLE_ROWS
+#define PM_SINGLE_ROWS 1    // conv_single_kernel's r = 2 upsamplers too
+#endif
+template <int MTW, int CP>
+struct RowStores {
+    static constexpr int RUN = MTW * 32 * 4;   // bytes of one column per wave
+    static constexpr int WAVE = CP * RUN;      // CP columns of a wave's tile
+    static constexpr int LPR = RUN / 16;       // lanes on one run
+    static constexpr int CPI = 64 / LPR;       // columns per store instruction
+    static_assert(MTW == 1 || MTW == 2, "8 or 16 slots of 16 bytes");
+    static_assert(CP == 8 || CP == 16 || CP == 32, "whole 8-lane store groups");
+    // slot (16 bytes) `s` of column `col`: XOR-swizzled so that the 8-lane
+    // groups of ds_write_b128 (8 columns, one slot) and the 16-lane groups of
+    // ds_read_b128 (pieces of two or four columns) each cover every bank once
+    static __device__ __forceinline__ int at(int col, int s) {
+        return col * RUN + ((s ^ (col & 7)) << 4);
+    }
+};
+
+// acc: the wave's tiles, rows m0 ... of M, columns n0 ... of the descriptor
+// `orsrc` (which drops the columns past its end); ebuf: RowStores::WAVE bytes
+template <int MTW, int NTW, int CP>
+__device__ __forceinline__ void pm_store_rows(
+    const floatx16 (&acc)[MTW][NTW], char* ebuf, const float* bias_ptr,
+    const float* gb, __amdgpu_buffer_rsrc_t orsrc, int M, int m0, int n0,
+    int lane) {
+    typedef RowStores<MTW, CP> R;
+    const int ln = lane & 31, lh = lane >> 5;
+    // after the turn: lane = (column % CPI, 4 output channels)
+    const int q = lane % R::LPR, h = lane / R::LPR;
+    const int co = m0 + 4 * q;
+    float4 bias = *reinterpret_cast<const float4*>(bias_ptr + co);
+    if (gb) {
+        const float4 g = *reinterpret_cast<const float4*>(gb + co);
+        bias.x += g.x; bias.y += g.y; bias.z += g.z; bias.w += g.w;
+    }
+#pragma unroll
+    for (int pass = 0; pass < NTW * (32 / CP); ++pass) {
+        const int nt = pass / (32 / CP), sub = pass % (32 / CP);
+        pm_wave_lds_sync();     // the last pass's reads are done
+        if (CP == 32 || ln / CP == sub) {
+#pragma unroll
+            for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4)
+                    *reinterpret_cast<float4*>(
+                        ebuf + R::at(ln % CP, mt * 8 + 2 * g4 + lh)) =
+                        make_float4(acc[mt][nt][4 * g4 + 0],
+                                    acc[mt][nt][4 * g4 + 1],
+                                    acc[mt][nt][4 * g4 + 2],
+                                    acc[mt][nt][4 * g4 + 3]);
+        }
+        pm_wave_lds_sync();
+        const int n = n0 + nt * 32 + sub * CP + h;
+        const unsigned voff = (unsigned)((n * M + co) * 4);
+#pragma unroll
+        for (int k = 0; k < CP / R::CPI; ++k) {
+            const float4 v = *reinterpret_cast<const float4*>(
+                ebuf + R::at(R::CPI * k + h, q));
+            pm_u4 r;
+            r.x = __float_as_uint(v.x + bias.x);
+            r.y = __float_as_uint(v.y + bias.y);
+            r.z = __float_as_uint(v.z + bias.z);
+            r.w = __float_as_uint(v.w + bias.w);
+            // (the column step is part of the range-checked vector offset)
+            __builtin_amdgcn_raw_buffer_store_b128(
+                r, orsrc, voff + (unsigned)(k * R::CPI * M * 4), 0,
+                PM_ROWS_AUX);
+        }
+    }
+}
+
+// The Block kernels' `out` tile the same way, 32 columns (one N tile) a pass:
+// the store modes (0 out = y, 1 out = y * scale, 2 out += y * scale) are
+// applied after the turn, and mode 2 reads the old values in the row layout
+// too - whole lines both ways. The loads of NB passes go out before the first
+// store of the batch (one round trip per batch). The per-element expressions
+// are those of the direct stores, which hipcc contracts: `old + v * scale`,
+// `v * s`; ZADD: the skewed kernels' single form, `old + v * sc` with old = 0
+// in modes 0 / 1. A16: optionally (`a16`) the tile goes to the 16-bit operand
+// tensor behind `arsrc` instead - lrelu, packed, a lane on 8 consecutive
+// channels of a column (two LDS slots, no half-wave exchange), 16 bytes a
+// store. Every column and row step is part of the range-checked vector offset.
+// `out` and `act16` are read by a later launch only: non-temporal.
+// PM_OUT_ROWS: a bit per site - 1 conv_pair_kernel, 2 the skewed whole-Block
+// walk, 4 block3_body (the tiled and walked whole-Block / whole-MRF kernels);
+// -DPM_OUT_ROWS=0 compiles the direct stores everywhere.
+#ifndef PM_OUT_ROWS
+#define PM_OUT_ROWS 7
+#endif
+#ifndef PM_OUT_ROWS_AUX
+#define PM_OUT_ROWS_AUX 2   // nt
+#endif
+// The skewed walk at k 11 keeps the direct stores: its store phase is the
+// smallest share of a step and the added barrier costs what the lines save -
+// block_c128_k11 and block_c64_k11 measured the same either way
+// (profiles/out_rows/NOTES.md). 1 turns them too.
+#ifndef PM_OUT_ROWS_K11
+#define PM_OUT_ROWS_K11 0
+#endif
+// acc: the wave's tiles, channels m0 ... of C, columns n0 ... (may be
+// negative: dropped) of the descriptors; ebuf: RowStores<MTW, 32>::WAVE bytes
+// that no other wave touches until this wave's next workgroup barrier
+template <int MTW, int NTW, int NB, bool ZADD, bool A16>
+__device__ __forceinline__ void pm_store_out_rows(
+    const floatx16 (&acc)[MTW][NTW], char* ebuf, __amdgpu_buffer_rsrc_t orsrc,
+    int C, int m0, int n0, int mode, float scale, int lane,
+    __amdgpu_buffer_rsrc_t arsrc, bool a16, bool a16f) {
+    typedef RowStores<MTW, 32> R;
+    constexpr int KI = 32 / R::CPI;     // store instructions a pass
+    const int ln = lane & 31, lh = lane >> 5;
+    // after the turn: lane = (column % CPI, 4 channels), or - 16-bit output -
+    // (column % (2 CPI), 8 channels)
+    const int q = lane % R::LPR, h = lane / R::LPR;
+    const int q8 = lane % (R::LPR / 2), h8 = lane / (R::LPR / 2);
+    const unsigned voff0 = (unsigned)(((n0 + h) * C + m0 + 4 * q) * 4);
+    const unsigned voff8 = (unsigned)(((n0 + h8) * C + m0 + 8 * q8) * 4);
+    const float s = mode == 0 ? 1.f : scale;
+    const bool wide = A16 && a16;
+#pragma unroll
+    for (int p0 = 0; p0 < NTW; p0 += NB) {
+        pm_u4 old[NB][KI] = {};
+        if (mode == 2) {
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                if (p0 + i >= NTW) break;
+                const unsigned col = (unsigned)((p0 + i) * 32 * C * 4);
+#pragma unroll
+                for (int k = 0; k < KI; ++k)
+                    old[i][k] = __builtin_amdgcn_raw_buffer_load_b128(
+                        orsrc,
+                        wide ? voff8 + col +
+                                   (unsigned)((k / 2) * 2 * R::CPI * C * 4 +
+                                              (k % 2) * 16)
+                             : voff0 + col + (unsigned)(k * R::CPI * C * 4),
+                        0, 0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            if (p0 + i >= NTW) break;
+            const int nt = p0 + i;
+            const unsigned col = (unsigned)(nt * 32 * C * 4);
+            pm_wave_lds_sync();     // the last pass's reads are done
+#pragma unroll
+            for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4)
+                    *reinterpret_cast<float4*>(
+                        ebuf + R::at(ln, mt * 8 + 2 * g4 + lh)) =
+                        acc_quad(acc[mt][nt], g4);
+            pm_wave_lds_sync();
+            if (wide) {
+                if constexpr (A16) {
+#pragma unroll
+                    for (int k = 0; k < KI; k += 2) {
+                        const int c8 = R::CPI * k + h8;
+                        float4 rq[2];
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const float4 v = *reinterpret_cast<const float4*>(
+                                ebuf + R::at(c8, 2 * q8 + j));
+                            const pm_u4 o = old[i][k + j];
+                            rq[j] = make_float4(
+                                __uint_as_float(o.x) + v.x * s,
+                                __uint_as_float(o.y) + v.y * s,
+                                __uint_as_float(o.z) + v.z * s,
+                                __uint_as_float(o.w) + v.w * s);
+                        }
+                        const float4 lo = pm_lrelu4(rq[0]);
+                        const float4 hi = pm_lrelu4(rq[1]);
+                        const uint2 pa = a16f ? ElemF16::pack4(lo)
+                                              : ElemBF16::pack4(lo);
+                        const uint2 pb = a16f ? ElemF16::pack4(hi)
+                                              : ElemBF16::pack4(hi);
+                        const pm_u4 u = {pa.x, pa.y, pb.x, pb.y};
+                        __builtin_amdgcn_raw_buffer_store_b128(
+                            u, arsrc,
+                            (voff8 + col + (unsigned)(k * R::CPI * C * 4)) / 2,
+                            0, PM_OUT_ROWS_AUX);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < KI; ++k) {
+                    const float4 v = *reinterpret_cast<const float4*>(
+                        ebuf + R::at(R::CPI * k + h, q));
+                    const pm_u4 o = old[i][k];
+                    pm_u4 r;
+                    if (ZADD || mode == 2) {
+                        r.x = __float_as_uint(__uint_as_float(o.x) + v.x * s);
+                        r.y = __float_as_uint(__uint_as_float(o.y) + v.y * s);
+                        r.z = __float_as_uint(__uint_as_float(o.z) + v.z * s);
+                        r.w = __float_as_uint(__uint_as_float(o.w) + v.w * s);
+                    } else {
+                        r.x = __float_as_uint(v.x * s);
+                        r.y = __float_as_uint(v.y * s);
+                        r.z = __float_as_uint(v.z * s);
+                        r.w = __float_as_uint(v.w * s);
+                    }
+                    __builtin_amdgcn_raw_buffer_store_b128(
+                        r, orsrc, voff0 + col + (unsigned)(k * R::CPI * C * 4),
+                        0, PM_OUT_ROWS_AUX);
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Fused Block iteration
 // ---------------------------------------------------------------------------
 
@@ -769,11 +993,25 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_pair_kernel(
         a.out + ((size_t)b * a.L + t0) * C, 0, rows * C * 4, 0x00020000);
     const unsigned voff0 =
         (unsigned)(((wn * NTW * 32 + ln) * C + wm * MTW * 32 + 4 * lh) * 4);
-    if (mode == 2) {
-        // MRF accumulation: the reads of `out` are issued in batches before
-        // the first store of a batch (one round trip per batch, not per
-        // tile; the operand fragment registers are dead by now)
-        constexpr int NB = NTW > 4 ? (NTW + 1) / 2 : NTW;
+    // MRF accumulation: the reads of `out` are issued in batches before
+    // the first store of a batch (one round trip per batch, not per
+    // tile; the operand fragment registers are dead by now)
+    constexpr int NB = NTW > 4 ? (NTW + 1) / 2 : NTW;
+    // 16-bit operands: whole lines through LDS (pm_store_out_rows). One
+    // barrier makes `inter` and the x chunks dead; a wave then owns 4 KB.
+    constexpr bool OUT_ROWS =
+        (PM_OUT_ROWS & 1) && ET::ESZ == 2 && MTW == 1 &&
+        pair_smem_bytes<ET, C, K, WM, WN, NTW, CH, ALIAS>(1) >=
+            WM * WN * MTW * 4096;
+    static_assert(OUT_ROWS || !(PM_OUT_ROWS & 1) || ET::ESZ != 2,
+                  "a 16-bit pair geometry lost the row stores");
+    if constexpr (OUT_ROWS) {
+        pm_block_sync();
+        pm_store_out_rows<MTW, NTW, NB, false, false>(
+            acc, smem + wave * RowStores<MTW, 32>::WAVE, orsrc, C,
+            wm * MTW * 32, wn * NTW * 32, mode, scale, lane, orsrc, false,
+            false);
+    } else if (mode == 2) {
 #pragma unroll
         for (int mt = 0; mt < MTW; ++mt)
 #pragma unroll
@@ -839,93 +1077,6 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_pair_kernel(
 // ---------------------------------------------------------------------------
 // Generic single convolution / polyphase transposed convolution
 // ---------------------------------------------------------------------------
-
-// ---------------------------------------------------------------------------
-// Row stores. The outputs here are (B, L, M) with M floats a column. In the
-// MFMA C/D layout a lane holds one column, so a direct b128 store writes 32
-// pieces of 32 bytes, one per column: 32-byte write requests to the L2.
-// pm_store_rows turns a wave's 32-column tiles round, CP columns at a time,
-// in an LDS buffer of the wave's own (no workgroup barrier: pm_wave_lds_sync)
-// and stores them with RUN / 16 lanes on one column's run of MTW * 32 floats:
-// whole 128-byte lines, half the write requests. Same acc + bias additions,
-// the same bytes. Read by one later launch only, hence non-temporal: such
-// stores do not wait in the L2 to be merged, which whole lines do not need
-// (on the 32-byte pieces of the direct stores nt takes 2.4 times as long).
-// ---------------------------------------------------------------------------
-#ifndef PM_ROWS_AUX
-#define PM_ROWS_AUX 2       // nt
-#endif
-#ifndef PM_SINGLE_ROWS
-#define PM_SINGLE_ROWS 1    // conv_single_kernel's r = 2 upsamplers too
-#endif
-template <int MTW, int CP>
-struct RowStores {
-    static constexpr int RUN = MTW * 32 * 4;   // bytes of one column per wave
-    static constexpr int WAVE = CP * RUN;      // CP columns of a wave's tile
-    static constexpr int LPR = RUN / 16;       // lanes on one run
-    static constexpr int CPI = 64 / LPR;       // columns per store instruction
-    static_assert(MTW == 1 || MTW == 2, "8 or 16 slots of 16 bytes");
-    static_assert(CP == 8 || CP == 16 || CP == 32, "whole 8-lane store groups");
-    // slot (16 bytes) `s` of column `col`: XOR-swizzled so that the 8-lane
-    // groups of ds_write_b128 (8 columns, one slot) and the 16-lane groups of
-    // ds_read_b128 (pieces of two or four columns) each cover every bank once
-    static __device__ __forceinline__ int at(int col, int s) {
-        return col * RUN + ((s ^ (col & 7)) << 4);
-    }
-};
-
-// acc: the wave's tiles, rows m0 ... of M, columns n0 ... of the descriptor
-// `orsrc` (which drops the columns past its end); ebuf: RowStores::WAVE bytes
-template <int MTW, int NTW, int CP>
-__device__ __forceinline__ void pm_store_rows(
-    const floatx16 (&acc)[MTW][NTW], char* ebuf, const float* bias_ptr,
-    const float* gb, __amdgpu_buffer_rsrc_t orsrc, int M, int m0, int n0,
-    int lane) {
-    typedef RowStores<MTW, CP> R;
-    const int ln = lane & 31, lh = lane >> 5;
-    // after the turn: lane = (column % CPI, 4 output channels)
-    const int q = lane % R::LPR, h = lane / R::LPR;
-    const int co = m0 + 4 * q;
-    float4 bias = *reinterpret_cast<const float4*>(bias_ptr + co);
-    if (gb) {
-        const float4 g = *reinterpret_cast<const float4*>(gb + co);
-        bias.x += g.x; bias.y += g.y; bias.z += g.z; bias.w += g.w;
-    }
-#pragma unroll
-    for (int pass = 0; pass < NTW * (32 / CP); ++pass) {
-        const int nt = pass / (32 / CP), sub = pass % (32 / CP);
-        pm_wave_lds_sync();     // the last pass's reads are done
-        if (CP == 32 || ln / CP == sub) {
-#pragma unroll
-            for (int mt = 0; mt < MTW; ++mt)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4)
-                    *reinterpret_cast<float4*>(
-                        ebuf + R::at(ln % CP, mt * 8 + 2 * g4 + lh)) =
-                        make_float4(acc[mt][nt][4 * g4 + 0],
-                                    acc[mt][nt][4 * g4 + 1],
-                                    acc[mt][nt][4 * g4 + 2],
-                                    acc[mt][nt][4 * g4 + 3]);
-        }
-        pm_wave_lds_sync();
-        const int n = n0 + nt * 32 + sub * CP + h;
-        const unsigned voff = (unsigned)((n * M + co) * 4);
-#pragma unroll
-        for (int k = 0; k < CP / R::CPI; ++k) {
-            const float4 v = *reinterpret_cast<const float4*>(
-                ebuf + R::at(R::CPI * k + h, q));
-            pm_u4 r;
-            r.x = __float_as_uint(v.x + bias.x);
-            r.y = __float_as_uint(v.y + bias.y);
-            r.z = __float_as_uint(v.z + bias.z);
-            r.w = __float_as_uint(v.w + bias.w);
-            // (the column step is part of the range-checked vector offset)
-            __builtin_amdgcn_raw_buffer_store_b128(
-                r, orsrc, voff + (unsigned)(k * R::CPI * M * 4), 0,
-                PM_ROWS_AUX);
-        }
-    }
-}
 
 struct SingleArgs {
     const void* x16;      // (B, L, Cin) operand-type copy of act(x), or null:
@@ -1772,10 +1923,24 @@ __device__ __forceinline__ void block3_body(
     const unsigned ovoff0 = (unsigned)(
         (((wave_s % WN) * NTW * 32 + (lane_s & 31) - store_lo) * C +
          (wave_s / WN) * MTW * 32 + 4 * (lane_s >> 5)) * 4);
-    if (mode == 2) {
-        // the reads of `out` go out in batches before the first store of a
-        // batch: one round trip per batch, not per 32 x 32 tile
-        constexpr int NB = NTW > 4 ? (NTW + 1) / 2 : NTW;
+    // the reads of `out` go out in batches before the first store of a
+    // batch: one round trip per batch, not per 32 x 32 tile
+    constexpr int NB = NTW > 4 ? (NTW + 1) / 2 : NTW;
+    // 16-bit operands: whole lines through LDS (pm_store_out_rows). `a` is
+    // dead behind the last iteration's epilogue-1 barrier (its last readers
+    // are that conv1 and the carry copy in front of the barrier) until the
+    // next tile or Block stages x, behind the caller's barrier: a wave takes
+    // 4 KB of it, no barrier added.
+    constexpr bool OUT_ROWS = (PM_OUT_ROWS & 4) && ET::ESZ == 2 && MTW == 1 &&
+                              ROWS_A * S >= WM * WN * MTW * 4096;
+    static_assert(OUT_ROWS || !(PM_OUT_ROWS & 4) || ET::ESZ != 2,
+                  "a 16-bit whole-Block geometry lost the row stores");
+    if constexpr (OUT_ROWS) {
+        pm_store_out_rows<MTW, NTW, NB, false, false>(
+            trunk, abuf + wave_s * RowStores<MTW, 32>::WAVE, orsrc, C,
+            (wave_s / WN) * MTW * 32, (wave_s % WN) * NTW * 32 - store_lo,
+            mode, scale, lane_s, orsrc, false, false);
+    } else if (mode == 2) {
 #pragma unroll
         for (int mt = 0; mt < MTW; ++mt)
 #pragma unroll
@@ -2577,6 +2742,24 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_block3_skew_kernel(
         // here -, one HBM round trip per step instead of one per tile)
         const float sc = mode == 0 ? 1.f : scale;
         constexpr int NB = MTW * NTW < 4 ? MTW * NTW : 4;
+        // 16-bit operands: whole lines through LDS (pm_store_out_rows). `t`
+        // is dead once every wave is behind its last conv2 and its t-carry
+        // copy (rows_out reads LDS in front of this barrier); the next writer
+        // is the next step's epilogue 1, two barriers on. A wave takes 4 KB.
+        // (k 11: see PM_OUT_ROWS_K11)
+        constexpr bool OUT_ROWS = (PM_OUT_ROWS & 2) && ET::ESZ == 2 &&
+                                  MTW == 1 && (K != 11 || PM_OUT_ROWS_K11) &&
+                                  GE::RT * S >= WM * WN * MTW * 4096;
+        static_assert(OUT_ROWS || !(PM_OUT_ROWS & 2) || ET::ESZ != 2 ||
+                          (K == 11 && !PM_OUT_ROWS_K11),
+                      "a 16-bit skewed geometry lost the row stores");
+        if constexpr (OUT_ROWS) {
+            pm_block_sync();
+            pm_store_out_rows<MTW, NTW, NB, true, true>(
+                trunk, tbuf + wave * RowStores<MTW, 32>::WAVE, orsrc, C,
+                m_first, o - own_first + wn * NTW * 32, mode, scale, ts & 63,
+                arsrc, a16, a16f);
+        } else
 #pragma unroll
         for (int t0 = 0; t0 < MTW * NTW; t0 += NB) {
             pm_u4 old[NB][4] = {};
