@@ -900,6 +900,38 @@ int pm_fdisc_conv_backward(const float* upstream, const float* y,
                            int frames, int dilation, int activation,
                            void* workspace, size_t workspace_bytes,
                            void* stream);
+/* pm_fdisc_layer_*: one layer of a stack at any of the six resolutions,
+ *   y = act(conv2d(cat(x, sin, cos), weight, bias, stride (stride, 1),
+ *                  dilation 1, padding (1, 1)))
+ * with `bins` the input's and (bins - 1) / stride + 1 output bins: output row
+ * fo reads the input rows stride * fo + kf - 1, zero outside the map for the
+ * map and the embedding alike; `table` (bins, 2) is the embedding of the
+ * INPUT. (channels, out_channels, stride) is one of (1, 16, s), (16, 32, s),
+ * (32, 64, s), (64, 128, s), (128, 256, s) with s 1 or 2, (16, 16, 1),
+ * (32, 32, 1), (64, 64, 1), (128, 128, 1) and (C, 1, 1) with C 16, 32, 64, 128
+ * or 256: what the reference builds. The three forms of pm_fdisc_conv_* at
+ * stride 1 run its kernels. Memory order, backward, partials and refusals as
+ * above: a map of 16 or more channels is channels_last. A form outside the
+ * list, a stride other than 1 or 2, batch, bins or frames below 1, an unknown
+ * activation, more than 2^31 - 1 input or output pixels, a null pointer or a
+ * workspace that is too small (PM_ENOMEM) are refused before any device work;
+ * the workspace query returns 0 for such sizes.                              */
+size_t pm_fdisc_layer_workspace_bytes(int batch, int channels,
+                                      int out_channels, int bins, int frames,
+                                      int stride);
+int pm_fdisc_layer_forward(const float* x, const float* weight,
+                           const float* bias, const float* table, float* y,
+                           int batch, int channels, int out_channels, int bins,
+                           int frames, int stride, int activation,
+                           void* stream);
+int pm_fdisc_layer_backward(const float* upstream, const float* y,
+                            const float* x, const float* weight,
+                            const float* table, float* grad_x,
+                            float* grad_weight, float* grad_bias, int batch,
+                            int channels, int out_channels, int bins,
+                            int frames, int stride, int activation,
+                            void* workspace, size_t workspace_bytes,
+                            void* stream);
 int pm_fdisc_weight_norm_forward(const float* g, const float* v, float* w,
                                  int out_channels, int fan, void* stream);
 int pm_fdisc_weight_norm_backward(const float* grad_w, const float* g,

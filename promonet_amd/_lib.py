@@ -165,6 +165,9 @@ SIGNATURES = {
     'pm_fdisc_workspace_bytes': (_S, [_I] * 5),
     'pm_fdisc_conv_forward': (_I, [_P] * 5 + [_I] * 7 + [_P]),
     'pm_fdisc_conv_backward': (_I, [_P] * 8 + [_I] * 7 + [_P, _S, _P]),
+    'pm_fdisc_layer_workspace_bytes': (_S, [_I] * 6),
+    'pm_fdisc_layer_forward': (_I, [_P] * 5 + [_I] * 7 + [_P]),
+    'pm_fdisc_layer_backward': (_I, [_P] * 8 + [_I] * 7 + [_P, _S, _P]),
     'pm_fdisc_weight_norm_forward': (_I, [_P] * 3 + [_I, _I, _P]),
     'pm_fdisc_weight_norm_backward': (_I, [_P] * 5 + [_I, _I, _P]),
     'pm_dconv_workspace_bytes': (_S, [_I] * 7),

@@ -1,7 +1,7 @@
 """The spectrograms at the entrance of the spectral discriminators on the HIP
 kernels (pm_disc_spec.h), differentiable in the audio, and the conv stacks of
-the FARGAN discriminator (pm_fdisc.h), differentiable in the maps and the
-parameters.
+the FARGAN discriminator (pm_fdisc.h, pm_fdisc_strided.h), differentiable in
+the maps and the parameters.
 
 API of the three `spectrogram` methods of `promonet.model.discriminator`
 (promonet/model/discriminator.py): DiscriminatorR (:129-143),
@@ -374,6 +374,14 @@ def _normed(conv):
 
 DILATIONS = (1, 2, 4, 8, 16)
 RESOLUTIONS = (64, 128, 256, 512, 1024, 2048)
+# (channels, out_channels, frequency stride) of the layers that the reference
+# builds over its six resolutions beside the narrow ones, 1 or 16 channels on
+# either side at stride 1 (magfree_plan): the kernels of pm_fdisc_strided.h
+STRIDED_FORMS = frozenset(
+    [(1, 16, 2)] +
+    [(c, 2 * c, s) for c in (16, 32, 64, 128) for s in (1, 2)] +
+    [(c, c, 1) for c in (32, 64, 128)] +
+    [(c, 1, 1) for c in (32, 64, 128, 256)])
 _TABLES = {}
 
 
@@ -389,22 +397,29 @@ def _embedding_table(device, bins):
     return _TABLES[key]
 
 
-def _layer_sizes(x, weight, bias, dilation, activation):
-    """((B, C, O, F, T), (d, act)) of a checked call; ValueError otherwise"""
+def _layer_sizes(x, weight, bias, dilation, activation, stride=1):
+    """((B, C, O, F, T), (d, act)) of a checked call of a narrow form, or
+    ((B, C, O, F, T, s), (act,)) of one of STRIDED_FORMS; ValueError
+    otherwise"""
     _require_float(x=x, weight=weight, bias=bias)
-    if x.ndim != 4 or x.shape[1] not in (1, 16) or not x.numel():
+    if isinstance(stride, bool) or stride not in (1, 2):
+        raise ValueError(f'stride {stride!r}: must be 1 or 2')
+    if x.ndim != 4 or not x.numel():
         raise ValueError(
-            f'x {tuple(x.shape)}: must be (B, C, F, T) with C 1 or 16 and no '
-            'empty axis')
+            f'x {tuple(x.shape)}: must be (B, C, F, T) with no empty axis')
     batch, channels, bins, frames = x.shape
-    if weight.ndim != 4 or weight.shape[0] not in (1, 16) or \
-            tuple(weight.shape[1:]) != (channels + 2, 3, 3):
+    if weight.ndim != 4 or tuple(weight.shape[1:]) != (channels + 2, 3, 3):
         raise ValueError(
-            f'weight {tuple(weight.shape)}: must be (O, {channels + 2}, 3, 3) '
-            'with O 1 or 16')
+            f'weight {tuple(weight.shape)}: must be (O, {channels + 2}, 3, 3)')
     out_channels = weight.shape[0]
-    if channels == 1 and out_channels == 1:
-        raise ValueError('no layer has one channel on both sides')
+    narrow = stride == 1 and channels in (1, 16) and \
+        out_channels in (1, 16) and (channels, out_channels) != (1, 1)
+    if not narrow and (channels, out_channels, stride) not in STRIDED_FORMS:
+        raise ValueError(
+            f'channels {channels} -> {out_channels} at stride {stride}: no '
+            'layer of the six stacks has that form (1 or 16 channels on '
+            'either side at stride 1, not 1 on both, or one of '
+            'STRIDED_FORMS)')
     if tuple(bias.shape) != (out_channels,):
         raise ValueError(
             f'bias {tuple(bias.shape)}: must be ({out_channels},)')
@@ -418,8 +433,14 @@ def _layer_sizes(x, weight, bias, dilation, activation):
         raise ValueError(
             f'activation {activation!r}: must be one of '
             f'{tuple(_lib.FDISC_ACTIVATIONS)}')
-    return (batch, channels, out_channels, bins, frames), \
-        (int(dilation), _lib.FDISC_ACTIVATIONS[activation])
+    if narrow:
+        return (batch, channels, out_channels, bins, frames), \
+            (int(dilation), _lib.FDISC_ACTIVATIONS[activation])
+    if dilation != 1:
+        raise ValueError(
+            f'dilation {dilation!r}: a strided or wider layer has none')
+    return (batch, channels, out_channels, bins, frames, int(stride)), \
+        (_lib.FDISC_ACTIVATIONS[activation],)
 
 
 _FREQUENCY_ENTRIES = (
@@ -429,18 +450,29 @@ _FREQUENCY_ENTRIES = (
         (batch, out_channels, bins, frames))
 
 
-def frequency_conv(x, weight, bias, dilation=1, activation='relu', table=None):
+_STRIDED_ENTRIES = (
+    'pm_fdisc_layer_forward', 'pm_fdisc_layer_backward',
+    'pm_fdisc_layer_workspace_bytes',
+    lambda batch, channels, out_channels, bins, frames, stride:
+        (batch, out_channels, (bins - 1) // stride + 1, frames))
+
+
+def frequency_conv(x, weight, bias, dilation=1, activation='relu', table=None,
+                   stride=1):
     """One layer of DiscriminatorMagFree (:343-369) without its weight norm:
-    act(conv2d(cat(x, sin, cos), weight, bias, stride 1, dilation (d, 1),
+    act(conv2d(cat(x, sin, cos), weight, bias, stride (s, 1), dilation (d, 1),
     padding (d, 1))), sin and cos of 2 pi f / F being the two channels of
-    FrequencyPositionalEmbedding. x (B, C, F, T) on the device with C 1 or 16,
-    weight (O, C + 2, 3, 3) with O 16 or 1, bias (O); activation 'relu',
-    'sigmoid' or 'none'. Returns (B, O, F, T) fp32; with 16 channels it is
-    channels_last in memory, as is the gradient in x. Differentiable in x,
-    weight and bias. Other float dtypes are cast to fp32 and their gradients
-    return in their dtype. `table` (F, 2) replaces sin and cos (the tests'
-    integer embedding)."""
-    sizes, scalars = _layer_sizes(x, weight, bias, dilation, activation)
+    FrequencyPositionalEmbedding on the layer's input. x (B, C, F, T) on the
+    device, weight (O, C + 2, 3, 3), bias (O); activation 'relu', 'sigmoid' or
+    'none'. With stride 1 and C, O in {1, 16} (not 1 on both sides) the
+    dilation is one of DILATIONS; any other (C, O, stride) is one of
+    STRIDED_FORMS and has dilation 1. Returns (B, O, (F - 1) // s + 1, T)
+    fp32; with 16 or more channels it is channels_last in memory, as is the
+    gradient in x. Differentiable in x, weight and bias. Other float dtypes
+    are cast to fp32 and their gradients return in their dtype. `table` (F, 2)
+    replaces sin and cos (the tests' integer embedding)."""
+    sizes, scalars = _layer_sizes(
+        x, weight, bias, dilation, activation, stride)
     if table is not None and tuple(table.shape) != (sizes[3], 2):
         raise ValueError(f'table {tuple(table.shape)}: must be (F, 2)')
     _lib.require_gpu(x)
@@ -448,7 +480,9 @@ def frequency_conv(x, weight, bias, dilation=1, activation='relu', table=None):
         table = _embedding_table(x.device, sizes[3])
     return _ConvLayer.apply(
         x.to(torch.float32), weight.to(torch.float32),
-        bias.to(torch.float32), _FREQUENCY_ENTRIES, sizes, scalars, table)
+        bias.to(torch.float32),
+        _FREQUENCY_ENTRIES if len(sizes) == 5 else _STRIDED_ENTRIES, sizes,
+        scalars, table)
 
 
 def magfree_plan(n_fft):
@@ -475,11 +509,12 @@ class FrequencyPositionalEmbedding(torch.nn.Identity):
     add the embedding themselves."""
 
 
-def _frequency_module(channels, out_channels, dilation):
+def _frequency_module(channels, out_channels, dilation, stride=1):
     """Slot 1 of a layer: the parameters of its conv over the map and the two
     channels of the embedding"""
     conv = _NormedConv2d(channels + 2, out_channels, 3)
     conv.dilation = dilation
+    conv.stride = stride
     return conv
 
 
@@ -491,28 +526,31 @@ class DiscriminatorMagFree(torch.nn.Module):
     reference's keys and shapes. `filterbank` is carried for the checkpoint
     only (the reference's forward never reads it) and starts as zeros.
 
-    Only the resolution whose stack has that form is accepted, n_fft = 64: at
-    128 ... 2048 the reference's layers halve the frequency axis and widen to
-    32 ... 256 channels (magfree_plan), which the kernels do not compute, and
-    a missing kernel is an error, not a reason to run torch's."""
+    `strided=True` builds any of the six resolutions: at 128 ... 2048 the
+    reference's layers halve the frequency axis and widen to 32 ... 256
+    channels (magfree_plan, STRIDED_FORMS). Without it only n_fft = 64, whose
+    stack is stride 1 and 16 channels throughout, is accepted and the others
+    raise a ValueError. The keyword exists for that reason alone: the refusal
+    was the interface while those layers had no kernel and the tests of that
+    time pin it; a later change that may touch them flips the default."""
 
-    def __init__(self, resolution):
+    def __init__(self, resolution, strided=False):
         super().__init__()
         self.resolution = tuple(int(v) for v in resolution)
         plan = magfree_plan(self.resolution[0])
-        if any(stride != 1 or out_channels > 16
-               for stride, _, _, out_channels in plan):
+        if not strided and any(stride != 1 or out_channels > 16
+                               for stride, _, _, out_channels in plan):
             raise ValueError(
                 f'n_fft {self.resolution[0]}: the layers of this resolution '
-                'have a frequency stride of 2 and up to 256 channels, which '
-                'the kernels do not compute (n_fft 64 alone is all stride 1 '
+                'have a frequency stride of 2 and up to 256 channels; pass '
+                'strided=True to build them (n_fft 64 alone is all stride 1 '
                 'and 16 channels)')
         layers = []
         for stride, dilation, channels, out_channels in plan:
             last = out_channels == 1
             layers.append(torch.nn.Sequential(
                 FrequencyPositionalEmbedding(),
-                _frequency_module(channels, out_channels, dilation),
+                _frequency_module(channels, out_channels, dilation, stride),
                 torch.nn.Sigmoid() if last else torch.nn.ReLU()))
         self.layers = torch.nn.ModuleList(layers)
         bins = self.resolution[0] // 2 + 1
@@ -520,15 +558,15 @@ class DiscriminatorMagFree(torch.nn.Module):
             torch.zeros(bins, bins), requires_grad=False)
 
     def stack(self, x):
-        """The six layers on x (B, 1, F, T): (logits (B, 1, F, T), [five
-        maps])"""
+        """The six layers on x (B, 1, F, T): (logits (B, 1, F', T), [five
+        maps]), F' the bins that the strided layers leave"""
         maps = []
         for layer in self.layers:
             conv = layer[1]
             x = frequency_conv(
                 x, conv.weight(), conv.bias, conv.dilation,
                 'sigmoid' if isinstance(layer[2], torch.nn.Sigmoid)
-                else 'relu')
+                else 'relu', stride=conv.stride)
             maps.append(x)
         return maps[-1], maps[:-1]
 
@@ -541,8 +579,8 @@ class DiscriminatorMagFree(torch.nn.Module):
 
 
 def _stack_layers(self):
-    """[(conv, dilation, activation)] where every layer of a reference-style
-    module has the form the kernels compute, or None"""
+    """[(conv, dilation, activation, stride)] where every layer of a
+    reference-style module has a form the kernels compute, or None"""
     layers, channels = [], 1
     for layer in getattr(self, 'layers', ()):
         if not isinstance(layer, torch.nn.Sequential) or len(layer) != 3:
@@ -551,13 +589,18 @@ def _stack_layers(self):
         if type(embedding).__name__ != 'FrequencyPositionalEmbedding' or \
                 not _is_normed_conv(conv):
             return None
-        if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or \
+        if conv.kernel_size != (3, 3) or conv.stride[1] != 1 or \
                 conv.groups != 1 or conv.padding_mode != 'zeros' or \
                 conv.dilation[1] != 1 or conv.dilation[0] not in DILATIONS or \
                 tuple(conv.padding) != (conv.dilation[0], 1) or \
-                conv.in_channels != channels + 2 or \
-                conv.out_channels not in (1, 16) or \
-                (channels == 1 and conv.out_channels == 1):
+                conv.in_channels != channels + 2:
+            return None
+        narrow = conv.stride[0] == 1 and channels in (1, 16) and \
+            conv.out_channels in (1, 16) and \
+            (channels, conv.out_channels) != (1, 1)
+        strided = conv.dilation[0] == 1 and \
+            (channels, conv.out_channels, conv.stride[0]) in STRIDED_FORMS
+        if not narrow and not strided:
             return None
         if isinstance(activation, torch.nn.ReLU):
             name = 'relu'
@@ -565,7 +608,7 @@ def _stack_layers(self):
             name = 'sigmoid'
         else:
             return None
-        layers.append((conv, conv.dilation[0], name))
+        layers.append((conv, conv.dilation[0], name, conv.stride[0]))
         channels = conv.out_channels
     return layers or None
 
@@ -577,9 +620,10 @@ def _wrap_forward(original):
             return original(self, x)
         x = spectrogram_decibel(x, self.resolution).unsqueeze(1)
         output = []
-        for conv, dilation, activation in layers:
+        for conv, dilation, activation, stride in layers:
             x = frequency_conv(
-                x, _normed(conv), conv.bias, dilation, activation)
+                x, _normed(conv), conv.bias, dilation, activation,
+                stride=stride)
             output.append(x)
         return torch.flatten(output[-1], 1, -1), output[:-1]
     forward.original = original
@@ -1009,17 +1053,21 @@ class DiscriminatorP(torch.nn.Module):
 class Discriminator(torch.nn.Module):
     """promonet.model.discriminator.Discriminator (:13-49) over the members
     that run on the device, in the reference's order: DiscriminatorP at each
-    of `periods`, DiscriminatorR at each of `resolutions`, DiscriminatorCMB.
-    The defaults are the reference's default configuration, whose checkpoint
-    loads with strict=True."""
+    of `periods`, DiscriminatorR at each of `resolutions`, DiscriminatorCMB,
+    DiscriminatorMagFree at each n_fft of `fargan`. The defaults are the
+    reference's default configuration, whose checkpoint loads with
+    strict=True; periods=(), complex_multiband=False, fargan=RESOLUTIONS is
+    that of the two configurations with FARGAN_DISCRIMINATOR."""
 
     def __init__(self, periods=PERIODS, complex_multiband=True,
-                 resolutions=()):
+                 resolutions=(), fargan=()):
         super().__init__()
         members = [DiscriminatorP(period) for period in periods]
         members += [DiscriminatorR(resolution) for resolution in resolutions]
         if complex_multiband:
             members.append(DiscriminatorCMB())
+        members += [DiscriminatorMagFree([n, n // 4, n], strided=True)
+                    for n in fargan]
         self.discriminators = torch.nn.ModuleList(members)
 
     def forward(self, y, y_hat, **kwargs):
@@ -1109,8 +1157,9 @@ def patch_module(module):
     module, where it has them, and the `forward` of SpecDiscriminatorBase,
     where it has one; a tensor that is not on a GPU goes to the original
     method, and so does a module whose layers are not weight-normed 3x3 convs
-    of stride 1 with a frequency dilation of 1 ... 16 under the frequency
-    embedding, each followed by ReLU or Sigmoid. The `forward` of
+    under the frequency embedding, each followed by ReLU or Sigmoid, of
+    stride 1 with a frequency dilation of 1 ... 16 and 1 or 16 channels or of
+    one of STRIDED_FORMS with no dilation. The `forward` of
     DiscriminatorCMB and of DiscriminatorR is replaced in the same way, where
     the class has one, for modules whose layers all have one of BAND_FORMS,
     and so is the `forward` of DiscriminatorP for modules whose layers are the
