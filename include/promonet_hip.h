@@ -1031,6 +1031,42 @@ int pm_pconv_fold_backward(const float* upstream, const float* y,
                            int period, float slope, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- generator training: one conv of an MRF Block --------------------------
+ * One conv of Block (promonet/model/hifigan.py:198-210) with its input
+ * activation and its residual add, forward and backward:
+ *   y = conv1d(leaky(x, slope), weight, bias, dilation,
+ *              padding (kernel - 1) dilation / 2) [+ residual]
+ * with x, y and residual (batch, channels, frames), channels in and out
+ * equal, channels 32, 64, 128 or 256, kernel 3, 7 or 11, dilation 1, 3 or 5:
+ * 36 forms. slope 1 is no activation; residual may be NULL. fp32 throughout,
+ * the products on the fp32-input MFMA.
+ * MEMORY ORDER: channels_last, in memory (batch, frames, channels). weight is
+ * torch's (channels, channels, kernel), bias (channels). A tap outside [0,
+ * frames) of its own utterance reads zero.
+ * Backward: from upstream and the saved INPUT x: grad_x = leaky'(x) * (the
+ * conv of upstream with the transposed, tap-mirrored weight), x = 0 taking
+ * the slope (NULL skips it); grad_weight and grad_bias from upstream and
+ * leaky(x) (both NULL skips them). The gradient of the residual is upstream
+ * itself. The sums over all pixels go through partials in the workspace,
+ * whose count depends on the sizes alone, added in a fixed order in double:
+ * no float atomics, the same bits on every run. All asynchronous, no
+ * allocation, capturable.
+ * Another form, batch or frames below 1, more than 2^31 - 1 pixels, a slope
+ * that is not finite or not in (0, 1], a null pointer other than the optional
+ * ones or a workspace that is too small (PM_ENOMEM) are refused before any
+ * device work; the workspace query returns 0 for such sizes.               */
+size_t pm_gconv_workspace_bytes(int batch, int channels, int frames,
+                                int kernel, int dilation);
+int pm_gconv_forward(const float* x, const float* weight, const float* bias,
+                     const float* residual, float* y, int batch, int channels,
+                     int frames, int kernel, int dilation, float slope,
+                     void* stream);
+int pm_gconv_backward(const float* upstream, const float* x,
+                      const float* weight, float* grad_x, float* grad_weight,
+                      float* grad_bias, int batch, int channels, int frames,
+                      int kernel, int dilation, float slope, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* ---- adversarial losses: promonet/train/loss.py:11-53 ---------------------
  * feature_matching, discriminator and generator are each a sum of means over
  * a list of tensors of unrelated sizes. pm_multi_mean takes the whole list:

@@ -179,6 +179,9 @@ SIGNATURES = {
     'pm_pconv_fold_workspace_bytes': (_S, [_I] * 3),
     'pm_pconv_fold_forward': (_I, [_P] * 4 + [_I] * 3 + [_F, _P]),
     'pm_pconv_fold_backward': (_I, [_P] * 7 + [_I] * 3 + [_F, _P, _S, _P]),
+    'pm_gconv_workspace_bytes': (_S, [_I] * 5),
+    'pm_gconv_forward': (_I, [_P] * 5 + [_I] * 5 + [_F, _P]),
+    'pm_gconv_backward': (_I, [_P] * 6 + [_I] * 5 + [_F, _P, _S, _P]),
     'pm_multi_mean_chunk': (_I, []),
     'pm_multi_mean_workspace_bytes': (_S, [_P, _I]),
     'pm_multi_mean': (_I, [_P] * 5 + [_I, _P, _P, _S, _P]),

@@ -14,7 +14,9 @@ of stride 1 and 16 channels under the frequency embedding on the device
 (DiscriminatorMagFree at n_fft 64) and leaves every other stack to the
 target's own method, and the `forward` of DiscriminatorCMB, DiscriminatorR
 and DiscriminatorP, which run their conv stacks on the device where every
-layer has one of the reference's forms.
+layer has one of the reference's forms, and the `forward` of
+`promonet.model.hifigan.Block`, which runs its convs on the device in both
+directions where autograd is on (model/hifigan_train.py).
 """
 import promonet_amd
 
@@ -65,6 +67,11 @@ def patch(promonet):
     discriminator = getattr(promonet.model, 'discriminator', None)
     if discriminator is not None:
         promonet_amd.model.discriminator.patch_module(discriminator)
+    # the convs of the generator's MRF Blocks under autograd (training), where
+    # the target has the module; its own forward everywhere else
+    hifigan = getattr(promonet.model, 'hifigan', None)
+    if hifigan is not None:
+        promonet_amd.model.hifigan_train.patch_module(hifigan)
     mels = getattr(getattr(promonet, 'baseline', None), 'mels', None)
     if mels is not None:
         for name in (
