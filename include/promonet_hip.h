@@ -353,6 +353,13 @@ int pm_debug_force(int walk_nseg, int upsample_groups);
  * default (the shapes it measured faster on). Per host thread, and only
  * with PROMONET_HIP_DEBUG=1, like pm_debug_force.                           */
 int pm_debug_skew(int mode);
+/* Test hook: what the last pm_block_cl / pm_block_act16_cl / pm_mrf_cl of
+ * this HOST THREAD launched - kernel: 1 the skewed walk, 2 the walked tiling,
+ * 3 the two-sided tiling; nseg: segments per utterance (0: no walk); narrow:
+ * the latency geometry; act16: the result left as 16-bit operands. PM_ESTATE
+ * before any such launch and unless the process runs with
+ * PROMONET_HIP_DEBUG=1. Host side only: it changes nothing that is launched. */
+int pm_debug_last_launch(int* kernel, int* nseg, int* narrow, int* act16);
 /* Measurement aid (bench.py): a register-resident loop of v_mfma_f32_32x32x16
  * (dtype PM_F16 | PM_BF16) - `workgroups` x 4 waves x `iterations` x 16 MFMAs
  * of 32 768 FLOP each - whose HIP-event time gives the matrix pipe's SUSTAINED

@@ -1211,6 +1211,19 @@ extern "C" int pm_debug_timeline(void* dev_buffer) {
 #endif
 }
 
+// What the last pm_block_cl / pm_block_act16_cl / pm_mrf_cl of this host
+// thread launched (pm_debug_last_launch below): written after the launch,
+// read by nothing that plans or launches.
+struct PmLastLaunch { bool valid = false; PmLaunch launch; };
+static PmLastLaunch& last_launch() {
+    static thread_local PmLastLaunch l;
+    return l;
+}
+static void record_launch(const PmLaunch& l) {
+    last_launch().valid = true;
+    last_launch().launch = l;
+}
+
 static int block_cl_impl(
     int dtype, const float* x, float* out, const float* const* w1,
     const float* const* b1, const float* const* w2, const float* const* b2,
@@ -1250,6 +1263,7 @@ static int block_cl_impl(
     if (plan.block[0].kernel == PM_PAIRS)
         return pm_fail(PM_EINVAL, "no whole-Block kernel for this shape");
     PM_HIP_TRY(launch_block3(dtype, plan.block[0], d, 0, s));
+    record_launch(plan.block[0]);
     if (act16 && !plan.block[0].act16)
         return pm_fail(PM_ESTATE,
                        "the launch did not take the skewed walk: `out` "
@@ -1333,6 +1347,7 @@ extern "C" int pm_mrf_cl(
     if (!planned)
         return pm_fail(PM_EINVAL, "no whole-MRF kernel for this shape");
     PM_HIP_TRY(launch_mrf(dtype, l, d, s));
+    record_launch(l);
     return PM_OK;
 }
 
@@ -1525,6 +1540,29 @@ extern "C" int pm_debug_skew(int mode) {
                        "(start the process with PROMONET_HIP_DEBUG=1)");
     if (mode < -1 || mode > 1) return pm_fail(PM_EINVAL, "mode is -1, 0 or 1");
     pm_force().skew = mode;
+    return PM_OK;
+}
+
+// Test hook: the PmLaunch the last pm_block_cl / pm_block_act16_cl / pm_mrf_cl
+// of this host thread took - kernel (the PmKernel values: 1 skewed, 2 walked,
+// 3 two-sided tiling), segments per utterance (0: no walk), the latency
+// geometry, the 16-bit operand output. PM_ESTATE before any such launch.
+// Reads what the launch recorded; changes nothing that is launched.
+extern "C" int pm_debug_last_launch(int* kernel, int* nseg, int* narrow,
+                                    int* act16) {
+    if (!debug_hooks_enabled())
+        return pm_fail(PM_ESTATE, "debug hooks are disabled "
+                       "(start the process with PROMONET_HIP_DEBUG=1)");
+    if (!kernel || !nseg || !narrow || !act16)
+        return pm_fail(PM_EINVAL, "null argument");
+    const PmLastLaunch& l = last_launch();
+    if (!l.valid)
+        return pm_fail(PM_ESTATE, "no whole-Block or whole-MRF launch on "
+                       "this thread yet");
+    *kernel = (int)l.launch.kernel;
+    *nseg = l.launch.nseg;
+    *narrow = l.launch.narrow;
+    *act16 = l.launch.act16;
     return PM_OK;
 }
 

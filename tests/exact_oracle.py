@@ -8,6 +8,9 @@ are compared with `torch.equal` against float64, with no tolerance. A wrong
 index, tap, column, channel, dilation, rounding mode or a stale byte moves an
 output by whole units of q.
 
+One iteration runs dense, two sparse (sparse_block), three lifted
+(lifted_block: what keeps three iterations inside the bound is said there).
+
 Everything here restates what the kernels do to a value, read from the code:
 
   activations  cvt(pm_lrelu(v)), pm_lrelu(v) = fmax(v, v * 0.1f) in fp32
@@ -306,6 +309,139 @@ def sparse_input(batch, c, length, seed):
     return 10 * _choice((-1, 0, 1), (batch, c, length), gen)
 
 
+# Three iterations. sparse_block multiplies by 10 at every conv so that the
+# values stay multiples of 10 for v * 0.1f: 20 x a conv, 20**6 over three
+# iterations. A lifted Block pays that in ONE iteration, the signed one:
+#
+#   signed   conv1 one weight 10 {+-1} per row, bias 10 {-1, 0, 1}: the hidden
+#            activation is a multiple of 10 of both signs; conv2 10 {+-1}.
+#   lifted   conv1 weights +1 and a constant bias, the lift, no smaller than
+#            the weights per row times the largest |negative| operand the
+#            trunk can hand it: the hidden activation is >= 0, its LeakyReLU
+#            the identity, and it is an integer whatever the operand rounding
+#            did to the trunk. conv2 10 {+-1}, bias 10 {-1, 0, 1}: the trunk
+#            stays a multiple of 10 of both signs.
+#   the Block's last conv2: {+-1}, bias -9..9 - no LeakyReLU follows.
+#
+# LIFTED_ROWS[position of the signed iteration] = weights per row of
+# (conv1, conv2) per iteration, chosen so that the WORST case of every
+# operand (lifted_block walks it) stays under 65504 with bf16's rounding on
+# top; the cases assert what they actually reach.
+LIFTED_ROWS = {0: ((1, 2, 1), (1, 2, 2)),
+               1: ((2, 1, 1), (1, 2, 2)),
+               2: ((1, 1, 1), (1, 1, 2))}
+
+
+def _ceil_bits(v, bits):
+    """The smallest integer >= v with at most `bits` significant bits."""
+    v = int(math.ceil(v))
+    shift = max(v.bit_length() - bits, 0)
+    return -(-v // (1 << shift)) << shift
+
+
+def lifted_weight(c, k, per_row, values, gen):
+    """(c, c, k) with `per_row` non-zeros from `values` per output row, and
+    every input channel and every tap non-zero (c >= k): weight j of row r
+    reads input channel p[(r + j) % c] at tap t[(r + 3 j) % k], p and t drawn
+    from `gen`. (A run of a permutation of all c k positions, as
+    sparse_weight takes it, leaves input channels out at one weight per
+    row.)"""
+    assert per_row <= 3 <= k <= c
+    p, t = torch.randperm(c, generator=gen), torch.randperm(k, generator=gen)
+    values = torch.tensor(values, dtype=torch.float32)
+    w = torch.zeros(c, c, k)
+    rows = torch.arange(c)
+    for j in range(per_row):
+        # (as many rows of one value as of the other: with one weight per
+        # row its sign is the sign of the whole output row)
+        w[rows, p[(rows + j) % c], t[(rows + 3 * j) % k]] = \
+            values[torch.randperm(c, generator=gen) % len(values)]
+    return w
+
+
+def lifted_block(c, k, seed, signed):
+    """Weights of three iterations, the `signed`-th signed and the others
+    lifted (above), and the worst case of |operand| in front of each of the
+    six convs."""
+    gen = torch.Generator().manual_seed(seed)
+    n1, n2 = LIFTED_ROWS[signed]
+    out, worst = ([], [], [], []), []
+    trunk = 10                          # sparse_input
+    for n in range(3):
+        worst.append(trunk)
+        if n == signed:
+            out[0].append(lifted_weight(c, k, n1[n], (-10, 10), gen))
+            out[1].append(10 * _choice((-1, 0, 1), (c,), gen))
+            hidden = 10 * n1[n] * trunk + 10
+        else:
+            # the largest negative operand: trunk / 10, rounded away from
+            # zero to bf16's 8 bits at the most
+            lift = _ceil_bits(n1[n] * _ceil_bits(trunk / 10, 8), 4)
+            out[0].append(lifted_weight(c, k, n1[n], (1,), gen))
+            out[1].append(torch.full((c,), float(lift)))
+            hidden = n1[n] * trunk + lift
+        worst.append(hidden)
+        if n == 2:
+            out[2].append(lifted_weight(c, k, n2[n], (-1, 1), gen))
+            out[3].append(_choice(range(-9, 10), (c,), gen))
+        else:
+            out[2].append(lifted_weight(c, k, n2[n], (-10, 10), gen))
+            out[3].append(10 * _choice((-1, 0, 1), (c,), gen))
+            trunk = trunk + 10 * n2[n] * _ceil_bits(hidden, 8) + 10
+    assert max(worst) * (1 + 2. ** -8) < F16_MAX, worst
+    return out, worst
+
+
+def lifted_operands(x, w, mode, dilations):
+    """fp32 values in front of every conv of a Block (before LeakyReLU and
+    operand rounding): trunk, hidden, trunk, hidden, ..."""
+    out = []
+    y = x.double()
+    w1, b1, w2, b2 = w
+    for n, d in enumerate(dilations):
+        h, _ = conv(lrelu32(y.float()), w1[n],
+                    round_operand(b1[n], mode, 'bias'), mode, d)
+        out += [y.float(), h.float()]
+        y, _ = conv(lrelu32(h.float()), w2[n],
+                    round_operand(b2[n], mode, 'bias'), mode, 1, y)
+    return out
+
+
+def first_accepted(draw, draws=4):
+    """draw(0), or the first of the next draws that meets its conditions: a
+    short case (one column: all taps but the centre read padding) can miss a
+    share of negative values by chance. The conditions stay as they are."""
+    for n in range(draws):
+        try:
+            return draw(n)
+        except NotExact as error:
+            refused = error
+    raise refused
+
+
+def assert_lifted(x, w, mode, dilations, signed):
+    """The conditions of a three-iteration case (NotExact otherwise); returns
+    the largest operand."""
+    before = lifted_operands(x, w, mode, dilations)
+    largest = max(lrelu32(t).abs().max().item() for t in before)
+    if not largest < F16_MAX:       # in EVERY mode: no clamp makes a case pass
+        raise NotExact(f'operand {largest:g} >= {F16_MAX:g}')
+    for n in range(3):
+        trunk, hidden = before[2 * n], before[2 * n + 1]
+        if not (trunk < 0).float().mean() >= .25:
+            raise NotExact(f'trunk of iteration {n} negative in < 25 %')
+        if n == signed:
+            if not (hidden < 0).float().mean() >= .25:
+                raise NotExact('signed hidden activation negative in < 25 %')
+        elif not (hidden >= 0).all():
+            raise NotExact(f'lifted hidden activation of iteration {n} < 0')
+    for weight in w[0] + w[2]:
+        hit = weight != 0
+        if not (hit.any(dim=(0, 2)).all() and hit.any(dim=(0, 1)).all()):
+            raise NotExact('an input channel or a tap without a weight')
+    return largest
+
+
 def int_fill(batch, c, length, seed):
     """A pre-filled `out` (store mode 2): integers in -99..99."""
     gen = torch.Generator().manual_seed(seed)
@@ -411,8 +547,12 @@ def block_runs(mode, c, k, niter):
     columns = block_geometry(mode, c, k)[1]
     if niter == 1:
         dilations = ((1,), (3,), (5,))
-    else:
+    elif niter == 2:
         dilations = ((1, 3), (3, 5), (5, 1))
+    else:
+        # (61: shorter than the 64-column skew of three iterations, one more
+        # than their halo at k 11; every rotation passes pm_skew_dilations)
+        dilations = ((1, 3, 5), (3, 5, 1), (5, 1, 3))
     return ((2, 9 * columns + 37, dilations[0], 0),
             (3, 2 * columns + 1, dilations[1], 2),
             (2, 61, dilations[2], 1))
@@ -431,46 +571,85 @@ def block_phase(mode, c, k, run):
 def block_case(mode, c, k, niter, run):
     nseg, length, dilations, store_mode = block_runs(mode, c, k, niter)[run]
     seed = 1000 * c + 10 * k + run
+    extra = {}
     if niter == 1:
         w = tuple([t] for t in dense_iteration(c, k, seed))
         x = dense_input(BATCH, c, length, seed + 1)
-    else:
+    elif niter == 2:
         w = sparse_block(c, k, niter, seed, block_phase(mode, c, k, run))
         x = sparse_input(BATCH, c, length, seed + 1)
+    else:
+        # the signed iteration is the run's: over the runs of a shape every
+        # iteration's hidden LeakyReLU sees negative values; the weight
+        # positions are drawn anew for every case of (c, k)
+        def draw(n):
+            w, worst = lifted_block(
+                c, k, seed + 100003 * block_phase(mode, c, k, run) + 977 * n,
+                run)
+            x = sparse_input(BATCH, c, length, seed + 1 + 977 * n)
+            return x, w, dict(
+                signed=run, worst=worst,
+                largest=assert_lifted(x, w, mode, dilations, run))
+        x, w, extra = first_accepted(draw)
     prev = int_fill(BATCH, c, length, seed + 2)
     y, bits = block(x, *w, mode, dilations)
     want = store(y, store_mode, SCALES[store_mode], prev)
     return dict(x=x, w=w, prev=prev, want=want, bits=bits, raw=y, nseg=nseg,
-                length=length, dilations=dilations, store_mode=store_mode)
+                length=length, dilations=dilations, store_mode=store_mode,
+                **extra)
 
 
 def block_table():
     """(mode, c, k, niter) of every Block case of (b) and (c)."""
-    return [(mode, c, k, niter) for niter in (1, 2) for c, k in BLOCK_SHAPES
+    return [(mode, c, k, niter) for niter in (1, 2, 3) for c, k in BLOCK_SHAPES
             for mode in block_modes(c)]
 
 
 # (d) pm_mrf_cl
 MRF_CHANNELS = (32, 20)
 MRF_LENGTHS = (1, 61, 700, 3000)
-MRF_DILATIONS = {1: ((1,), (3,), (5,), (3,)), 2: ((1, 3), (3, 5), (5, 1), (1, 3))}
+MRF_DILATIONS = {1: ((1,), (3,), (5,), (3,)), 2: ((1, 3), (3, 5), (5, 1), (1, 3)),
+                 3: ((1, 3, 5), (3, 5, 1), (5, 1, 3), (1, 3, 5))}
+
+
+def mrf_lengths(mode, niter):
+    """Three iterations reach the walked and the skewed whole-MRF kernels
+    (plan_mrf_cfg): in columns NC of the k 11 geometry they run on, shorter
+    than a tile, the skew and the halo's neighbour 61, 2 NC + 1 - 3 segments
+    take less than a tile each -, 5 NC + 37 - uneven segments, ragged ends."""
+    if niter < 3:
+        return MRF_LENGTHS
+    columns = block_geometry(mode, 32, 11)[1]
+    return (1, 61, 2 * columns + 1, 5 * columns + 37)
 
 
 @functools.lru_cache(maxsize=None)
 def mrf_case(mode, c, niter, run):
-    length, dilations = MRF_LENGTHS[run], MRF_DILATIONS[niter][run]
-    blocks = []
-    for k in (3, 7, 11):
-        seed = 500 * c + 10 * k + run
-        if niter == 1:
-            blocks.append(tuple([t] for t in dense_iteration(c, k, seed)))
-        else:
-            blocks.append(sparse_block(c, k, niter, seed, run))
-    x = (dense_input if niter == 1 else sparse_input)(
-        BATCH, c, length, 77 * c + run)
+    length = mrf_lengths(mode, niter)[run]
+    dilations = MRF_DILATIONS[niter][run]
+    def draw(n):
+        blocks, extra = [], {}
+        x = (dense_input if niter == 1 else sparse_input)(
+            BATCH, c, length, 77 * c + run + 977 * n)
+        for k in (3, 7, 11):
+            seed = 500 * c + 10 * k + run + 977 * n
+            if niter == 1:
+                blocks.append(tuple([t] for t in dense_iteration(c, k, seed)))
+            elif niter == 2:
+                blocks.append(sparse_block(c, k, niter, seed, run))
+            else:
+                # (the three Blocks' signed iteration is the same one)
+                w, _ = lifted_block(c, k, seed, run % 3)
+                blocks.append(w)
+                extra = dict(signed=run % 3, largest=max(
+                    extra.get('largest', 0.),
+                    assert_lifted(x, w, mode, dilations, run % 3)))
+        return x, blocks, extra
+    # (one and two iterations have no conditions to miss: draw(0) as ever)
+    x, blocks, extra = first_accepted(draw) if niter == 3 else draw(0)
     parts, total, bits = mrf_sum(x, blocks, mode, dilations)
     return dict(x=x, blocks=blocks, parts=parts, total=total, bits=bits,
-                length=length, dilations=dilations)
+                length=length, dilations=dilations, **extra)
 
 
 # (e) the upsamplers: test_conv_transpose's shapes

@@ -14,7 +14,14 @@ turned out to EXCEED that gate and are left as they are: two input channels
 swapped in one row (its k = 11 taps: 22 products) measures 1.13e-2, just over;
 dilation 3 taken as 2 for one tap (C products of every output) 1.7e-1 - the
 tolerance tests see those two. On the exact inputs each of the four moves
-outputs by thousands of whole units of q."""
+outputs by thousands of whole units of q.
+
+Three iterations (the lifted cases of exact_oracle.py): every case is built
+and its conditions written out once more (lifted_conditions), the bits and the
+largest operand printed; the planted defects of three iterations - dilations
+swapped, the third iteration dropped, truncation, a hidden LeakyReLU left
+out, one tile with the halo of two iterations - are held by the SHARE of the
+elements they move."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -73,7 +80,54 @@ def block_operands(case, mode):
     return out
 
 
-@pytest.mark.parametrize('niter', [1, 2])
+def lifted_conditions(x, w, mode, dilations, signed):
+    """The conditions of a three-iteration Block, written out on the values
+    in front of its six convs (E.assert_lifted holds the same at build time);
+    returns the largest operand."""
+    w1, b1, w2, b2 = w
+    before = E.lifted_operands(x, w, mode, dilations)
+    operands = [E.lrelu32(t) for t in before]
+    # under 65504 in EVERY mode: the clamp is not what makes a case pass
+    largest = max(t.abs().max().item() for t in operands)
+    assert largest < E.F16_MAX
+    for t in operands:      # integers: v * 0.1f met multiples of 10 only
+        assert torch.equal(t, t.round())
+    for n in range(3):
+        trunk, hidden = before[2 * n], before[2 * n + 1]
+        assert (trunk < 0).float().mean() >= .25, n
+        assert torch.equal(trunk, (trunk / 10).round() * 10)
+        last = n == 2
+        if n == signed:
+            assert (hidden < 0).float().mean() >= .25
+            assert torch.equal(hidden, (hidden / 10).round() * 10)
+            assert (w1[n] != 0).sum(dim=(1, 2)).eq(1).all()
+            assert set(w1[n].unique().tolist()) == {-10., 0., 10.}
+            assert set(b1[n].unique().tolist()) <= {-10., 0., 10.}
+        else:
+            assert (hidden >= 0).all()      # its LeakyReLU is the identity
+            assert set(w1[n].unique().tolist()) == {0., 1.}
+            assert (w1[n] != 0).sum(dim=(1, 2)).le(2).all()
+            lift = b1[n]
+            assert (lift == lift[0]).all() and lift[0] > 0
+            for half in ('f16', 'bf16'):    # 16 bits hold it
+                assert torch.equal(
+                    E.round_operand(lift, half, 'bias'), lift.double())
+            # no smaller than weights per row x the largest negative operand
+            per_row = (w1[n] != 0).sum(dim=(1, 2)).max().item()
+            assert lift[0] >= per_row * -operands[2 * n].min().item()
+        unit = 1. if last else 10.
+        assert set(w2[n].unique().tolist()) == {-unit, 0., unit}
+        assert (w2[n] != 0).sum(dim=(1, 2)).le(2).all()
+        assert b2[n].abs().max() <= (9. if last else 10.)
+        assert torch.equal(b2[n], (b2[n] / unit).round() * unit)
+        for weight in (w1[n], w2[n]):
+            hit = weight != 0
+            assert hit.any(dim=(0, 2)).all()        # every input channel
+            assert hit.any(dim=(0, 1)).all()        # every tap
+    return largest
+
+
+@pytest.mark.parametrize('niter', [1, 2, 3])
 @pytest.mark.parametrize('channels,kernel_size', E.BLOCK_SHAPES)
 def test_block_cases_exact(channels, kernel_size, niter):
     for mode in E.block_modes(channels):
@@ -81,7 +135,24 @@ def test_block_cases_exact(channels, kernel_size, niter):
         for run in range(3):
             case = E.block_case(mode, channels, kernel_size, niter, run)
             assert case['bits'] <= E.EXACT_BITS
-            f16_range(mode, *block_operands(case, mode))
+            if niter < 3:
+                f16_range(mode, *block_operands(case, mode))
+                continue
+            # the signed iteration rotates over the runs; the lengths are the
+            # runs' of three iterations
+            assert case['signed'] == run
+            assert sorted(case['dilations']) == [1, 3, 5]
+            largest = lifted_conditions(
+                case['x'], case['w'], mode, case['dilations'], run)
+            assert largest == case['largest'] <= max(case['worst']) * (
+                1 + 2. ** -8)
+            print(f'{mode} C {channels} k {kernel_size} run {run}: '
+                  f'{case["bits"]:.1f} bits, largest operand {largest:g}')
+    if niter == 3:
+        columns = E.block_geometry('bf16', channels, kernel_size)[1]
+        runs = E.block_runs('bf16', channels, kernel_size, 3)
+        assert [(r[0], r[1], r[3]) for r in runs] == [
+            (2, 9 * columns + 37, 0), (3, 2 * columns + 1, 2), (2, 61, 1)]
     # the kernels that exist in one form only are in the table in that form
     forms = {(c, k): [E.block_form('bf16', c, k, r)
                       for r in E.block_requests('bf16', c, k)]
@@ -111,9 +182,27 @@ def test_sparse_cases_cover_every_weight_position(channels, kernel_size):
 @pytest.mark.parametrize('mode', E.MODES)
 def test_other_cases_exact(mode):
     for c in E.MRF_CHANNELS:
-        for niter in (1, 2):
+        for niter in (1, 2, 3):
             for run in range(len(E.MRF_LENGTHS)):
-                assert E.mrf_case(mode, c, niter, run)['bits'] <= E.EXACT_BITS
+                case = E.mrf_case(mode, c, niter, run)
+                assert case['bits'] <= E.EXACT_BITS
+                if niter < 3:
+                    continue
+                # three lifted Blocks on one input, their sum exact in fp32
+                largest = max(
+                    lifted_conditions(case['x'], w, mode, case['dilations'],
+                                      case['signed'])
+                    for w in case['blocks'])
+                assert largest == case['largest']
+                total = case['total']
+                assert torch.equal(total.float().double(), total)
+                print(f'MRF {mode} C {c} L {case["length"]}: '
+                      f'{case["bits"]:.1f} bits, largest operand {largest:g}, '
+                      f'largest sum {total.abs().max().item():g}')
+        columns = 768 if mode in ('f16', 'bf16') else 512
+        assert E.mrf_lengths(mode, 3) == (
+            1, 61, 2 * columns + 1, 5 * columns + 37)
+        assert E.mrf_lengths(mode, 2) == E.MRF_LENGTHS
     for shape in E.UPSAMPLE_SHAPES:
         for length in E.UPSAMPLE_LENGTHS:
             case = E.upsample_case(mode, *shape, length)
@@ -171,7 +260,7 @@ def state_of(w, prefix='p'):
     return state
 
 
-@pytest.mark.parametrize('niter', [1, 2])
+@pytest.mark.parametrize('niter', [1, 2, 3])
 def test_fp32_oracle_equals_restatement(niter):
     cases = [E.block_case('fp32', 32, 3, niter, 1),
              E.block_case('fp32', 64, 11, niter, 0)]
@@ -230,10 +319,11 @@ def test_16bit_oracle_equals_restatement_on_rounded_operands(mode):
     def bias(t):
         return rn(t).double() + rn(t - rn(t)).double()
 
-    for c, k, niter in ((64, 7, 1), (64, 11, 2), (128, 3, 2)):
+    for c, k, niter, run in ((64, 7, 1, 1), (64, 11, 2, 1), (128, 3, 2, 1),
+                             (64, 11, 3, 0), (32, 7, 3, 1), (128, 11, 3, 2)):
         if c > 64 and mode not in ('f16', 'bf16'):
             continue
-        case = E.block_case(mode, c, k, niter, 1)
+        case = E.block_case(mode, c, k, niter, run)
         x = case['x'].double()
         w1, b1, w2, b2 = case['w']
         for n, d in enumerate(case['dilations']):
@@ -426,3 +516,133 @@ def test_planted_rounding_defects():
     got = defective_iteration(x, w1, b1, w2, b2, 'bf16', d, 'bias_unrounded')
     assert got is not None and not torch.equal(got, want)
     assert E.round_operand(b2, 'bf16', 'bias')[7].item() == 174764.
+
+
+# ---------------------------------------------------------------------------
+# Three iterations: the lifted cases have teeth
+# ---------------------------------------------------------------------------
+def forward3(x, w, mode, dilations, lo=0, length=None, truncate=False,
+             plain_hidden=None):
+    """A Block in float64 with no exactness check (the wrong kernel need not
+    be exact) on the columns lo ... lo + x.shape[-1] of an utterance of
+    `length` columns: as a tile computes it, values outside the utterance are
+    zero in front of every conv, the window's own edges read zeros too.
+    plain_hidden: the iteration whose hidden LeakyReLU is left out."""
+    defects = dict(truncate=truncate)
+    length = x.shape[-1] if length is None else length
+    at = torch.arange(lo, lo + x.shape[-1])
+    inside = ((at >= 0) & (at < length)).double()
+    w1, b1, w2, b2 = w
+    k = w1[0].shape[-1]
+    y = x.double() * inside
+    for n, d in enumerate(dilations):
+        a = E.round_operand(E.lrelu32(y.float()), mode, 'act', **defects)
+        h = F.conv1d(a, E.round_operand(w1[n], mode, 'weight', **defects),
+                     E.round_operand(b1[n], mode, 'bias', **defects),
+                     padding=d * (k - 1) // 2, dilation=d) * inside
+        h = h.float() if n == plain_hidden else E.lrelu32(h.float())
+        a = E.round_operand(h, mode, 'act', **defects)
+        y = (y + F.conv1d(a, E.round_operand(w2[n], mode, 'weight', **defects),
+                          E.round_operand(b2[n], mode, 'bias', **defects),
+                          padding=(k - 1) // 2)) * inside
+    return y
+
+
+def share(got, want):
+    return (got != want).double().mean().item()
+
+
+LIFTED_TEETH = (('bf16', 128, 11), ('f16', 64, 7), ('fp32', 32, 3))
+
+
+@pytest.mark.parametrize('mode,channels,kernel_size', LIFTED_TEETH)
+def test_planted_defects_three_iterations(mode, channels, kernel_size):
+    """Each defect moves a three-iteration case, by the SHARE of its elements
+    that differ: what a wrong kernel would show to `torch.equal`. The floors
+    are reasoned, the measured shares printed."""
+    for run in range(3):
+        case = E.block_case(mode, channels, kernel_size, 3, run)
+        x, w, dilations, want = (
+            case['x'], case['w'], case['dilations'], case['raw'])
+        # (forward3 itself is right: no defect, the oracle's bits)
+        assert torch.equal(forward3(x, w, mode, dilations), want)
+        # the dilations of iterations 2 and 3 swapped: every output reads
+        # other columns through two convs
+        d = dilations
+        swapped = share(forward3(x, w, mode, (d[0], d[2], d[1])), want)
+        # the third iteration dropped: its conv2 adds zero only where two
+        # hidden values in the thousands cancel to within the bias
+        first_two = [ts[:2] for ts in w]
+        dropped = share(forward3(x, first_two, mode, d[:2]), want)
+        # the hidden LeakyReLU of the signed iteration left out: at least a
+        # quarter of that activation is negative (asserted at build time),
+        # and every row of its conv2 reads one or two elements of it
+        plain = share(forward3(x, w, mode, d, plain_hidden=run), want)
+        print(f'{mode} C {channels} k {kernel_size} run {run}: swapped '
+              f'{swapped:.4f} dropped {dropped:.4f} no LeakyReLU in '
+              f'iteration {run + 1} {plain:.4f}')
+        assert swapped > .9 and dropped > .99 and plain >= .25
+        # ... and left out of a LIFTED iteration it is no defect at all: the
+        # construction knows which LeakyReLU each run tests
+        other = (run + 1) % 3
+        assert torch.equal(forward3(x, w, mode, d, plain_hidden=other), want)
+
+
+def test_planted_truncation_three_iterations():
+    """Round toward zero instead of to nearest even in bf16. Only values
+    above 256 have more than bf16's 8 bits: with the signed iteration first
+    or second they enter the second or third iteration's convs and spread
+    through what follows (more than half of the outputs); with the signed
+    iteration last the trunk stays below 1 600 and only the last hidden
+    activation passes 256, so an output sees the defect through the two
+    elements its last conv2 reads: a tenth at the least."""
+    for run, floor in enumerate((.5, .5, .1)):
+        case = E.block_case('bf16', 64, 7, 3, run)
+        got = forward3(case['x'], case['w'], 'bf16', case['dilations'],
+                       truncate=True)
+        truncated = share(got, case['raw'])
+        print(f'run {run}: truncation moves {truncated:.4f}')
+        assert truncated > floor
+
+
+def test_planted_two_iteration_halo():
+    """One tile of the two-sided tiling (the bf16 C 32 k 11 geometry: 768
+    columns) computed with the halo of TWO iterations instead of three: with
+    the right halo the tile is the oracle's, with the short one the columns
+    next to the tile's edges differ and nothing else."""
+    mode, c, k, run = 'bf16', 32, 11, 0
+    case = E.block_case(mode, c, k, 3, run)
+    x, w, dilations, want = (
+        case['x'], case['w'], case['dilations'], case['raw'])
+    length = case['length']
+    columns = E.block_geometry(mode, c, k)[1]
+    halo = sum((d + 1) * (k - 1) // 2 for d in dilations)
+    short = sum((d + 1) * (k - 1) // 2 for d in dilations[:2])
+    assert (halo, short) == (60, 30)
+    tile = columns - 2 * halo
+    start = 3 * tile                    # an inner tile
+    assert start + tile < length
+
+    def tile_with(margin):
+        lo, hi = start - margin, start + tile + margin
+        y = forward3(x[:, :, lo:hi], w, mode, dilations, lo, length)
+        return y[:, :, margin:margin + tile]
+
+    assert torch.equal(tile_with(halo), want[:, :, start:start + tile])
+    wrong = tile_with(short) != want[:, :, start:start + tile]
+    band = halo - short
+    assert not wrong[:, :, band:tile - band].any()
+    edges = torch.cat([wrong[:, :, :band], wrong[:, :, tile - band:]], dim=2)
+    print(f'two-iteration halo: {edges.double().mean().item():.4f} of the '
+          f'{2 * band} edge columns x channels differ, '
+          f'{edges.any(dim=1).double().mean().item():.4f} of the columns')
+    # An output depends on its inputs along 8 chains of six taps (1 x 1,
+    # 2 x 2, 1 x 2 weights per row), each chain's offset a sum of six uniform
+    # taps times (1, 1, 3, 1, 5, 1): deviation 19.5 columns. An output p
+    # columns inside the tile is wrong where a chain passes 30 + p columns:
+    # some 6 % of the chains at p = 0, next to none at p = 29 - a few per
+    # cent of the band, spread over both sides and every second column at
+    # the least; one such element fails `torch.equal`.
+    assert edges[:, :, 0].any() and edges[:, :, -1].any()
+    assert edges.double().mean().item() >= .03
+    assert edges.any(dim=1).double().mean().item() >= .25

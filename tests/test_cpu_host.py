@@ -402,3 +402,46 @@ def test_debug_hooks_are_off_in_a_production_process():
     finally:
         assert library.pm_debug_force(0, 0) == 0
         library.pm_hifigan_destroy(handle)
+
+
+def test_last_launch_hook_before_any_launch():
+    """pm_debug_last_launch reports what a launch recorded on the calling
+    host thread: PM_ESTATE where the hooks are off, and - opted in - on a
+    thread that has launched no whole-Block or whole-MRF kernel yet."""
+    import os
+    import subprocess
+    import sys
+    import threading
+    code = (
+        'import ctypes\n'
+        'from promonet_amd import _lib\n'
+        'lib = _lib.lib()\n'
+        'v = [ctypes.c_int(-7) for _ in range(4)]\n'
+        'print(lib.pm_debug_last_launch(*[ctypes.byref(i) for i in v]), '
+        '[i.value for i in v], lib.pm_last_error().decode())\n')
+    env = {k: v for k, v in os.environ.items() if k != 'PROMONET_HIP_DEBUG'}
+    env['PYTHONPATH'] = str(ROOT)
+    out = subprocess.run(
+        [sys.executable, '-c', code], env=env, capture_output=True, text=True,
+        timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.startswith(f'{_lib.PM_ESTATE} [-7, -7, -7, -7] ')
+    assert 'PROMONET_HIP_DEBUG' in out.stdout
+    library = _lib.lib()
+    seen = []
+
+    def fresh_thread():
+        values = [ctypes.c_int(-7) for _ in range(4)]
+        seen.append((library.pm_debug_last_launch(
+            *[ctypes.byref(v) for v in values]), [v.value for v in values],
+            library.pm_last_error().decode()))
+
+    worker = threading.Thread(target=fresh_thread)
+    worker.start()
+    worker.join()
+    code, values, message = seen[0]
+    assert code == _lib.PM_ESTATE and values == [-7] * 4
+    assert 'launch' in message and 'PROMONET_HIP_DEBUG' not in message
+    values = [ctypes.c_int() for _ in range(3)]
+    assert library.pm_debug_last_launch(
+        *[ctypes.byref(v) for v in values], None) == _lib.PM_EINVAL

@@ -5,24 +5,41 @@ and every partial sum of a conv is exactly representable in fp32; the result
 then does not depend on the order of summation, and a wrong index, tap,
 column, channel, dilation, rounding mode or stale byte shows as whole units of
 the value grid. test_gpu_kernels.py keeps guarding what these inputs cannot:
-conditioning on realistic values, three fused iterations (which cannot be made
-exact: 24.8 - 25.1 bits in bf16) and the ledger of measured errors.
+conditioning on realistic values, DENSE weights over three fused iterations
+and the ledger of measured errors.
+
+One iteration runs dense, two sparse (two weights 10 {+-1} per row), three -
+what every production Block has - lifted: the sparse construction continued
+to three reaches 24.8 - 25.1 bits in bf16 and leaves the f16 range, because
+it multiplies by 10 at every conv; a lifted Block does so in one iteration
+only, the signed one, and keeps the hidden activations of the other two
+non-negative with a constant bias (exact_oracle.py: 14.0 - 16.6 bits, the
+largest operand 53 240 < 65504, in all five modes).
 
 Every case asserts its exactness (<= 22 bits of bound / q, the result a
 fixed point of a round trip through fp32) before it compares; the case table
 is checked on the CPU by test_cpu_exact_oracle.py.
 
-Kernel forms reached (the form is part of a Block test's id):
+Kernel forms reached (the form is part of a Block test's id, and every Block
+and MRF launch is held to it through pm_debug_last_launch: the library's own
+report of the kernel and the segments it took, not E.block_form's restatement
+of the planner):
   test_block_iteration           conv_pair_kernel (C >= 128: latency geometry)
   test_block_iteration_wide_tiles  conv_pair_kernel, wide geometry, C 128 / 256
   test_whole_block[...-tiled]    conv_block3_kernel (two-sided tiling)
   test_whole_block[...-walked]   conv_block3_walk_kernel, 2 and 3 segments
   test_whole_block[...-skewed]   conv_block3_skew_kernel, 2 and 3 segments
-  test_whole_mrf                 the two-sided whole-MRF tiling only: the walked
-                                 and the skewed whole-MRF kernels exist for
-                                 three iterations (plan_mrf_cfg), which are
-                                 outside the exact set - the hooks are set as
-                                 for them all the same
+                                 (each with n1, n2 and n3 iterations)
+  test_block_output_as_operand   conv_block3_skew_kernel's 16-bit hand-over
+  test_whole_mrf                 conv_mrf_kernel, the two-sided whole-MRF
+                                 tiling: all there is for one and two
+                                 iterations (plan_mrf_cfg) - the hooks are set
+                                 as for the others all the same
+  test_whole_mrf_three_iterations[...-tiled]   conv_mrf_kernel
+  test_whole_mrf_three_iterations[...-walked]  conv_mrf_walk_kernel, 16-bit
+                                 operands, 2 and 3 segments
+  test_whole_mrf_three_iterations[...-skewed]  conv_mrf_skew_kernel, 4-byte
+                                 operands, 1, 2 and 3 segments
   test_conv_transpose            conv_single_kernel, conv_upsample_kernel with
                                  1, 2 and all M groups; the 16-bit input path
   test_conv_transpose_long_batch conv_single_kernel, 256 input columns a
@@ -59,6 +76,27 @@ def assert_equal(got, want, detail):
 
 def pointers(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+# PmKernel of pm_launch.h
+KERNELS = {1: 'skewed', 2: 'walked', 3: 'tiled'}
+
+
+def last_launch():
+    """(form, segments, act16) of this thread's last pm_block_cl /
+    pm_block_act16_cl / pm_mrf_cl, from the library (pm_debug_last_launch)."""
+    _lib = lib()
+    kernel, nseg, narrow, act16 = (ctypes.c_int(-1) for _ in range(4))
+    _lib.check(_lib.lib().pm_debug_last_launch(
+        *[ctypes.byref(v) for v in (kernel, nseg, narrow, act16)]))
+    return KERNELS[kernel.value], nseg.value, bool(act16.value)
+
+
+def assert_launch(form, nseg, act16=False):
+    """The device ran what the test's id says: E.block_form restates the
+    planner, this is the planner's own answer. A two-sided tiling has no
+    segments."""
+    assert last_launch() == (form, nseg if form != 'tiled' else 0, act16)
 
 
 # ---------------------------------------------------------------------------
@@ -128,10 +166,12 @@ class BlockRunner:
     """pm_block_cl / pm_block_act16_cl on a Block case in one of the forms
     the launcher has for the shape, through the test hooks."""
 
-    def __init__(self, device, mode, c, k, request):
+    def __init__(self, device, mode, c, k, request, form=None):
         _lib = lib()
         self.device, self.mode, self.c, self.k = device, mode, c, k
         self.request = request
+        # the kernel the test's id names: the library's report is held to it
+        self.form = form or E.block_form(mode, c, k, request)
         self.weights = 3 * _lib.lib().pm_op_workspace_bytes(c, c, k)
         scratch = _lib.lib().pm_walk_scratch_bytes(E.BATCH)
         assert scratch > 0
@@ -167,6 +207,7 @@ class BlockRunner:
                 _lib.DTYPES[self.mode], _lib.DTYPES[act], _lib.ptr(x_cl),
                 _lib.ptr(out), act16.data_ptr(), *args))
         torch.cuda.synchronize()
+        assert_launch(self.form, case['nseg'], act is not None)
         return out, act16
 
 
@@ -187,9 +228,13 @@ BLOCK_CASES = [
 def test_whole_block(device, mode, channels, kernel_size, niter, request_):
     """niter = 1: dense, each of d = 1, 3, 5. niter = 2: sparse, the pairs
     (1, 3), (3, 5), (5, 1) - the hand-over of the trunk between iterations
-    (the 32 i skew, the carries through LDS and scratch). 2 and 3 segments,
-    uneven, a boundary that is no tile multiple, an utterance end inside a
-    tile, L = 61 and 2 columns + 1; every store mode."""
+    (the 32 i skew, the carries through LDS and scratch). niter = 3: lifted
+    (exact_oracle.py), the rotations of (1, 3, 5) - what production
+    launches: the third iteration, the 64-column skew, the second hand-over,
+    the 60-column halo at k 11. 2 and 3 segments, uneven, a boundary that is
+    no tile multiple, an utterance end inside a tile, L = 61 and
+    2 columns + 1; every store mode. The library says which kernel ran
+    (BlockRunner)."""
     run = BlockRunner(device, mode, channels, kernel_size, request_)
     try:
         for index in range(3):
@@ -202,10 +247,36 @@ def test_whole_block(device, mode, channels, kernel_size, niter, request_):
         restore_hooks()
 
 
+def test_form_assertion_is_live(device):
+    """pm_debug_last_launch follows the launch, not the request's name: the
+    same case on the skewed walk, then as the launcher chooses - whose
+    report fails the skewed id's assertion - and a thread that has launched
+    nothing is told so."""
+    import threading
+    mode, c, k = 'bf16', 64, 7
+    case = E.block_case(mode, c, k, 3, 1)
+    try:
+        BlockRunner(device, mode, c, k, 'skewed')(case)
+        assert last_launch() == ('skewed', case['nseg'], False)
+        BlockRunner(device, mode, c, k, 'own')(case)
+        assert last_launch() == ('tiled', 0, False)
+        with pytest.raises(AssertionError):
+            BlockRunner(device, mode, c, k, 'own', form='skewed')(case)
+        seen = []
+        worker = threading.Thread(target=lambda: seen.append(
+            lib().lib().pm_debug_last_launch(
+                *[ctypes.byref(ctypes.c_int()) for _ in range(4)])))
+        worker.start()
+        worker.join()
+        assert seen == [lib().PM_ESTATE]
+    finally:
+        restore_hooks()
+
+
 @pytest.mark.parametrize('act', ['f16', 'bf16'])
 @pytest.mark.parametrize('mode', ['f16', 'bf16'])
 @pytest.mark.parametrize('channels,kernel_size,niter',
-                         [(128, 11, 1), (64, 7, 2)])
+                         [(128, 11, 1), (64, 7, 2), (128, 11, 3), (64, 7, 3)])
 def test_block_output_as_operand(device, mode, act, channels, kernel_size, niter):
     """pm_block_act16_cl on Block cases: act16 holds the oracle's operand
     bits, cvt(lrelu(result)) in the next stage's type, `out` is left alone."""
@@ -228,6 +299,51 @@ def test_block_output_as_operand(device, mode, act, channels, kernel_size, niter
 # ---------------------------------------------------------------------------
 # (d) the whole MRF
 # ---------------------------------------------------------------------------
+class MrfRunner:
+    """pm_mrf_cl on the MRF cases of (mode, channels, niter): the workspace
+    holds the packed weights and, behind them, the skewed walk's scratch,
+    which a launch is handed or not."""
+
+    def __init__(self, device, mode, channels, niter):
+        _lib = lib()
+        self.device, self.mode, self.channels = device, mode, channels
+        self.niter = niter
+        per = _lib.lib().pm_op_workspace_bytes(channels, channels, 11)
+        self.weights = 3 * niter * per
+        scratch = _lib.lib().pm_walk_scratch_bytes(E.BATCH)
+        assert scratch > 0
+        self.ws = torch.empty(
+            self.weights + scratch, dtype=torch.uint8, device=device)
+
+    def __call__(self, case, nseg, scratch, form):
+        """The launch forced to `nseg` segments (0: the launcher's choice),
+        with or without scratch; asserts the kernel the library reports and
+        the derived bound; returns `out` as the kernel left it."""
+        _lib = lib()
+        x_cl = to_cl(case['x']).to(self.device)
+        order = [[t.to(self.device).contiguous()
+                  for block in case['blocks'] for t in block[which]]
+                 for which in range(4)]
+        dil = (ctypes.c_int * self.niter)(*case['dilations'])
+        _lib.check(_lib.lib().pm_debug_force(nseg, 0))
+        self.ws[self.weights:].fill_(0xff)  # (NaNs: nothing stale is read)
+        out = torch.full_like(x_cl, 7.)
+        _lib.check(_lib.lib().pm_mrf_cl(
+            _lib.DTYPES[self.mode], _lib.ptr(x_cl), _lib.ptr(out),
+            *[pointers(ts) for ts in order], dil, self.niter, E.BATCH,
+            case['length'], self.channels, self.ws.data_ptr(),
+            self.ws.numel() if scratch else self.weights, _lib.stream()))
+        torch.cuda.synchronize()
+        assert_launch(form, nseg)
+        bound = 4 * 2. ** -24 * sum(p.abs() for p in case['parts']) / 3
+        got = from_cl(out, self.channels).double().cpu()
+        error = (got - case['total'] / 3).abs()
+        assert (error <= bound).all(), (
+            form, nseg, case['length'], (error - bound).max().item(),
+            E.first_difference(got, case['total'] / 3))
+        return out
+
+
 @pytest.mark.parametrize('mode', E.MODES)
 @pytest.mark.parametrize('channels', E.MRF_CHANNELS)
 @pytest.mark.parametrize('niter', [1, 2])
@@ -236,36 +352,55 @@ def test_whole_mrf(device, mode, channels, niter):
     more fp32 roundings of partial results (at most three: each Block's share
     or the sum's), and whether they are fused is the compiler's, so
     |got - S / 3| <= 4 * 2**-24 * (|B3| + |B7| + |B11|) / 3 elementwise -
-    derived, not measured."""
-    _lib = lib()
-    per = _lib.lib().pm_op_workspace_bytes(channels, channels, 11)
-    weights = 3 * niter * per
-    scratch = _lib.lib().pm_walk_scratch_bytes(E.BATCH)
-    ws = torch.empty(weights + scratch, dtype=torch.uint8, device=device)
+    derived, not measured. One and two iterations have the two-sided tiling
+    only, whatever the hooks ask for (asserted)."""
+    run = MrfRunner(device, mode, channels, niter)
     wide = mode not in ('f16', 'bf16')
     try:
-        for index, length in enumerate(E.MRF_LENGTHS):
+        for index in range(len(E.MRF_LENGTHS)):
             case = E.mrf_case(mode, channels, niter, index)
             assert_exact(case)
-            x_cl = to_cl(case['x']).to(device)
-            order = [[t.to(device).contiguous()
-                      for block in case['blocks'] for t in block[which]]
-                     for which in range(4)]
-            dil = (ctypes.c_int * niter)(*case['dilations'])
-            bound = 4 * 2. ** -24 * sum(p.abs() for p in case['parts']) / 3
-            for nseg, size in ((0, weights), (2, ws.numel() if wide else weights)):
-                _lib.check(_lib.lib().pm_debug_force(nseg, 0))
-                ws[weights:].fill_(0xff)
-                out = torch.full_like(x_cl, 7.)
-                _lib.check(_lib.lib().pm_mrf_cl(
-                    _lib.DTYPES[mode], _lib.ptr(x_cl), _lib.ptr(out),
-                    *[pointers(ts) for ts in order], dil, niter, E.BATCH,
-                    length, channels, ws.data_ptr(), size, _lib.stream()))
-                torch.cuda.synchronize()
-                got = from_cl(out, channels).double().cpu()
-                error = (got - case['total'] / 3).abs()
-                assert (error <= bound).all(), (
-                    nseg, length, (error - bound).max().item())
+            run(case, 0, False, 'tiled')
+            run(case, 2, wide, 'tiled')
+    finally:
+        restore_hooks()
+
+
+# The whole-MRF kernels of three iterations (plan_mrf_cfg): (form, segments
+# forced, scratch handed over)
+MRF_FORMS = {'tiled': ((0, False),),
+             'walked': ((2, False), (3, False)),
+             'skewed': ((1, True), (2, True), (3, True))}
+
+
+def mrf_forms(mode):
+    return ('tiled', 'walked') if mode in HALF else ('tiled', 'skewed')
+
+
+@pytest.mark.parametrize('mode,channels,form', [
+    pytest.param(mode, c, form, id=f'{mode}-C{c}-n3-{form}')
+    for mode in E.MODES for c in E.MRF_CHANNELS for form in mrf_forms(mode)])
+def test_whole_mrf_three_iterations(device, mode, channels, form):
+    """What production launches: three lifted Blocks (exact_oracle.py) of
+    three iterations each, the rotations of (1, 3, 5). conv_mrf_kernel (no
+    force, no scratch), conv_mrf_walk_kernel (16-bit operands, 2 and 3
+    segments), conv_mrf_skew_kernel (4-byte operands, 1, 2 and 3 segments,
+    scratch behind the weights - NaNs before every launch); L = 1, 61,
+    2 NC + 1 and 5 NC + 37 of the k 11 geometry's NC columns. Held to the
+    bound of test_whole_mrf, and the walked and the skewed launch bit for bit
+    to the two-sided tiling, whose sum order (B11 + B7 + B3) / 3 is theirs
+    (test_gpu_kernels.py::test_whole_mrf)."""
+    run = MrfRunner(device, mode, channels, 3)
+    try:
+        for index in range(len(E.MRF_LENGTHS)):
+            case = E.mrf_case(mode, channels, 3, index)
+            assert_exact(case)
+            tiled = run(case, 0, False, 'tiled')
+            if form == 'tiled':
+                continue
+            for nseg, scratch in MRF_FORMS[form]:
+                out = run(case, nseg, scratch, form)
+                assert torch.equal(out, tiled), (nseg, case['length'])
     finally:
         restore_hooks()
 
