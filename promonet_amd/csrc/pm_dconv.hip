@@ -70,11 +70,9 @@ PmSplit split_of(const Sizes& z) {
 }
 
 // backward: the partials
-struct DcLayout { float* parts; size_t total; };
-DcLayout backward_layout(const Sizes& z, void* base) {
-    PmCarve c(base);
-    return {c.take<float>((size_t)split_of(z).parts * z.partial_floats()),
-            c.used};
+PmPartsLayout backward_layout(const Sizes& z, void* base) {
+    return pm_parts_layout(base, (size_t)split_of(z).parts,
+                           (size_t)z.partial_floats());
 }
 
 unsigned walked(int tiles) {
@@ -98,13 +96,9 @@ int launch_conv32(DcArgs a, const Sizes& z, hipStream_t s) {
     typedef Dc32<KW, S> D;
     const int lds =
         (D::WEIGHTS + (DC_ROWS + 2) * D::NP * DC_PITCH) * (int)sizeof(float);
-    auto kern = dc_conv32_kernel<KW, S>;
-    PM_HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
     set_tiles(a, tiles_of(z, z.Wo, DC_COLS));
-    hipLaunchKernelGGL(kern, dim3(walked(a.tiles)), dim3(DC_THREADS), lds, s,
-                       a);
-    PM_HIP_TRY(hipGetLastError());
-    return PM_OK;
+    return pm_launch_dynamic(dc_conv32_kernel<KW, S>, walked(a.tiles),
+                             DC_THREADS, lds, s, a);
 }
 
 template <int KW, int S>
@@ -112,13 +106,9 @@ int launch_gx32(DcArgs a, const Sizes& z, hipStream_t s) {
     typedef Dc32<KW, S> D;
     const int lds =
         (D::WEIGHTS + (DC_ROWS + 2) * D::NG * DC_PITCH) * (int)sizeof(float);
-    auto kern = dc_gx32_kernel<KW, S>;
-    PM_HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
     set_tiles(a, tiles_of(z, z.W, D::GX_COLS));
-    hipLaunchKernelGGL(kern, dim3(walked(a.tiles)), dim3(DC_THREADS), lds, s,
-                       a);
-    PM_HIP_TRY(hipGetLastError());
-    return PM_OK;
+    return pm_launch_dynamic(dc_gx32_kernel<KW, S>, walked(a.tiles),
+                             DC_THREADS, lds, s, a);
 }
 
 template <int KW, int S>
@@ -126,14 +116,11 @@ int launch_gw32(DcArgs a, const Sizes& z, hipStream_t s) {
     typedef Dc32<KW, S> D;
     const int lds = ((DC_ROWS + 2) * D::NP + DC_ROWS * DC_COLS) * DC_PITCH *
         (int)sizeof(float);
-    auto kern = dc_gw32_kernel<KW, S>;
-    PM_HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
     set_tiles(a, tiles_of(z, z.Wo, DC_COLS));
     const PmSplit split = split_of(z);
     a.per = split.each;
-    hipLaunchKernelGGL(kern, dim3(split.parts), dim3(DC_THREADS), lds, s, a);
-    PM_HIP_TRY(hipGetLastError());
-    return PM_OK;
+    return pm_launch_dynamic(dc_gw32_kernel<KW, S>, (unsigned)split.parts,
+                             DC_THREADS, lds, s, a);
 }
 
 }  // namespace
@@ -192,7 +179,7 @@ extern "C" int pm_dconv_backward(
         return pm_fail(PM_EINVAL, "pm_dconv_backward: %s", why);
     if (const char* why = pm_check_slope(slope))
         return pm_fail(PM_EINVAL, "pm_dconv_backward: %s", why);
-    const DcLayout l = backward_layout(z, workspace);
+    const PmPartsLayout l = backward_layout(z, workspace);
     if (const int code = pm_check_backward(
             "pm_dconv_backward", upstream && y && x && weight, grad_weight,
             grad_bias, workspace, workspace_bytes, l.total))

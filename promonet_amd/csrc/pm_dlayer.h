@@ -1,9 +1,12 @@
-// What the discriminator conv layers' kernels share (pm_fdisc.h, pm_dconv.h,
-// pm_pconv.h): the leaky activation and its gate, the fp32 MFMA step, the
-// walker of the flattened pixels of a stride-1 layer, the span and the
-// epilogue of the gW kernels that run over such pixels, and the reduce of the
-// gW | gb partials. fp32 throughout; every kernel is a workgroup of
-// DL_THREADS, which FD_THREADS, DC_THREADS and PC_THREADS equal.
+// What the conv layers' training kernels share (pm_fdisc.h, pm_dconv.h,
+// pm_pconv.h, pm_gconv.h): the leaky activation and its gate, the fp32 MFMA
+// step, the flattened pixels of a map (DlPixel walks a stride-1 layer,
+// DlBatchPixel finds the batch row too), the span and the epilogue of the gW
+// kernels that walk such pixels, and the reduce of the gW | gb partials. The
+// gemm kernels of pm_pconv.h and pm_gconv.h share their weight chunk and their
+// chains as well: pm_pixel_gemm.h. fp32 throughout; every kernel is a
+// workgroup of DL_THREADS, which FD_THREADS, DC_THREADS, PC_THREADS and
+// GC_THREADS equal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +24,10 @@ __device__ __forceinline__ float dl_gate(float g, float y, float slope) {
 __device__ __forceinline__ float4 dl_gate4(float4 g, float4 y, float slope) {
     return make_float4(dl_gate(g.x, y.x, slope), dl_gate(g.y, y.y, slope),
                        dl_gate(g.z, y.z, slope), dl_gate(g.w, y.w, slope));
+}
+__device__ __forceinline__ float4 dl_leaky4(float4 v, float slope) {
+    return make_float4(dl_leaky(v.x, slope), dl_leaky(v.y, slope),
+                       dl_leaky(v.z, slope), dl_leaky(v.w, slope));
 }
 
 #define DL_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0)
@@ -61,6 +68,20 @@ struct DlPixel {
                                            int sign = 1) const {
         const int hh = h + sign * dh, ww = w + sign * dw;
         return hh >= 0 && hh < H && ww >= 0 && ww < W;
+    }
+};
+// (b, h, w) of the pixel p of a flattened (B, H, W) map, for the kernels of
+// the strided layers: their taps lie in another map, which the batch row finds
+// (the audio, in the period discriminator's first layer). Apart from DlPixel:
+// the kernels that use that one read no b, and none of these walks. The same
+// 32-bit arithmetic.
+struct DlBatchPixel {
+    int b, h, w;
+    __device__ __forceinline__ DlBatchPixel(long long p, int H, int W) {
+        const unsigned row = (unsigned)p / (unsigned)W;
+        w = (int)((unsigned)p - row * (unsigned)W);
+        h = (int)(row % (unsigned)H);
+        b = (int)(row / (unsigned)H);
     }
 };
 // (dh in 64 bits: a dilated tap's d T may leave 32)

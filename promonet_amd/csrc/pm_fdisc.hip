@@ -46,13 +46,10 @@ int partial_floats(int channels, int out_channels) {
 }
 
 // backward: the partials
-struct FdLayout { float* parts; size_t total; };
-FdLayout backward_layout(long long pixels, int channels, int out_channels,
-                         void* base) {
-    PmCarve c(base);
-    return {c.take<float>((size_t)split_of(pixels).parts *
-                          partial_floats(channels, out_channels)),
-            c.used};
+PmPartsLayout backward_layout(long long pixels, int channels, int out_channels,
+                              void* base) {
+    return pm_parts_layout(base, (size_t)split_of(pixels).parts,
+                           (size_t)partial_floats(channels, out_channels));
 }
 
 const char* check_norm(int out_channels, int fan) {
@@ -115,7 +112,7 @@ extern "C" int pm_fdisc_conv_backward(
                                       frames, dilation, activation))
         return pm_fail(PM_EINVAL, "pm_fdisc_conv_backward: %s", why);
     const long long pixels = (long long)batch * bins * frames;
-    const FdLayout l =
+    const PmPartsLayout l =
         backward_layout(pixels, channels, out_channels, workspace);
     if (const int code = pm_check_backward(
             "pm_fdisc_conv_backward", upstream && y && x && weight && table,
@@ -203,20 +200,14 @@ const char* check_strided(int batch, int channels, int out_channels, int bins,
     return nullptr;
 }
 
-// gW of the general layers: the tiles, the K chunks, the chunks of a partial
-// and the partials, from the sizes alone
-struct FsSplit { int tiles, chunks, per, parts; };
-FsSplit gemm_split(long long out_pixels, int channels, int out_channels) {
+// gW of the general layers: the tiles, and the split of their K chunks
+int gemm_tiles(int channels, int out_channels) {
     const int cb = channels == 16 ? 1 : 2;
-    const int tiles = channels / (16 * cb) *
-                      (int)pm_ceil_div(out_channels, 64 / cb);
-    const long long chunks = pm_ceil_div(out_pixels, FS_GW_PIX);
-    long long parts = FS_GW_WORKGROUPS / tiles;
-    const long long most = pm_ceil_div(chunks, FS_GW_MIN_CHUNKS);
-    if (parts > most) parts = most;
-    if (parts < 1) parts = 1;
-    const long long per = pm_ceil_div(chunks, parts);
-    return {tiles, (int)chunks, (int)per, (int)pm_ceil_div(chunks, per)};
+    return channels / (16 * cb) * (int)pm_ceil_div(out_channels, 64 / cb);
+}
+PmChunkSplit gemm_split(long long out_pixels, int tiles) {
+    return pm_chunk_split(out_pixels, FS_GW_PIX, tiles, FS_GW_WORKGROUPS,
+                          FS_GW_MIN_CHUNKS);
 }
 
 // the partials of the layer's gW | gb (the edge kernels: one a workgroup of
@@ -224,18 +215,20 @@ FsSplit gemm_split(long long out_pixels, int channels, int out_channels) {
 int strided_parts(FsKind kind, long long in_pixels, long long out_pixels,
                   int channels, int out_channels) {
     if (kind == FS_GEMM)
-        return gemm_split(out_pixels, channels, out_channels).parts;
+        return gemm_split(out_pixels,
+                          gemm_tiles(channels, out_channels)).parts;
     return pm_pixel_split(kind == FS_FIRST ? out_pixels : in_pixels,
                           FS_EDGE_CHUNK, FS_EDGE_MAX_PARTS).parts;
 }
 
-FdLayout strided_layout(FsKind kind, long long in_pixels, long long out_pixels,
-                        int channels, int out_channels, void* base) {
-    PmCarve c(base);
-    return {c.take<float>((size_t)strided_parts(kind, in_pixels, out_pixels,
-                                                channels, out_channels) *
-                          partial_floats(channels, out_channels)),
-            c.used};
+PmPartsLayout strided_layout(FsKind kind, long long in_pixels,
+                             long long out_pixels, int channels,
+                             int out_channels, void* base) {
+    return pm_parts_layout(
+        base,
+        (size_t)strided_parts(kind, in_pixels, out_pixels, channels,
+                              out_channels),
+        (size_t)partial_floats(channels, out_channels));
 }
 
 // `tiles` pixel tiles of every row tile: MT = 16, 32 or 64 rows
@@ -259,8 +252,9 @@ void launch_gemm(const FsArgs& a, unsigned tiles, hipStream_t s) {
 }
 
 template <int S>
-void launch_gw(const FsArgs& a, const FsSplit& split, hipStream_t s) {
-    const dim3 grid((unsigned)split.tiles * split.parts), block(FD_THREADS);
+void launch_gw(const FsArgs& a, int tiles, const PmChunkSplit& split,
+               hipStream_t s) {
+    const dim3 grid((unsigned)tiles * split.parts), block(FD_THREADS);
     if (a.C == 16)
         hipLaunchKernelGGL((fs_gw_kernel<S, 1>), grid, block, 0, s, a);
     else
@@ -353,7 +347,7 @@ extern "C" int pm_fdisc_layer_backward(
                                       out_channels, bins, frames, 1,
                                       activation, workspace, workspace_bytes,
                                       stream);
-    const FdLayout l = strided_layout(kind, in_pixels, out_pixels, channels,
+    const PmPartsLayout l = strided_layout(kind, in_pixels, out_pixels, channels,
                                       out_channels, workspace);
     FsArgs a = {};
     a.x = x; a.w = weight; a.table = table; a.g = upstream; a.y = y;
@@ -390,14 +384,14 @@ extern "C" int pm_fdisc_layer_backward(
         a.parts = l.parts;
         int parts;
         if (kind == FS_GEMM) {
-            const FsSplit split = gemm_split(out_pixels, channels,
-                                             out_channels);
+            const int tiles = gemm_tiles(channels, out_channels);
+            const PmChunkSplit split = gemm_split(out_pixels, tiles);
             a.pixels = out_pixels;
             a.chunks = split.chunks;
-            a.per = split.per;
+            a.per = split.each;
             parts = split.parts;
-            if (stride == 1) launch_gw<1>(a, split, s);
-            else launch_gw<2>(a, split, s);
+            if (stride == 1) launch_gw<1>(a, tiles, split, s);
+            else launch_gw<2>(a, tiles, split, s);
         } else {
             a.pixels = kind == FS_FIRST ? out_pixels : in_pixels;
             const PmSplit split =

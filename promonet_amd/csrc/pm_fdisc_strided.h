@@ -74,18 +74,8 @@ struct FsArgs {
     int span;               // edge gW: pixels of a workgroup
 };
 
-// (b, f, t) of the pixel p of a flattened (B, rows, T) map; 32-bit arithmetic:
-// the host refuses more than 2^31 - 1 pixels
-struct FsPixel {
-    int b, f, t;
-    __device__ __forceinline__ FsPixel(long long p, int rows, int T) {
-        const unsigned row = (unsigned)p / (unsigned)T;
-        t = (int)((unsigned)p - row * (unsigned)T);
-        f = (int)(row % (unsigned)rows);
-        b = (int)(row / (unsigned)rows);
-    }
-};
-
+// (A pixel of a flattened (B, rows, T) map is a DlBatchPixel: h its frequency
+// row, w its frame.)
 __device__ __forceinline__ float4 fs_gate4(float4 g, float4 y, int act) {
     return make_float4(fd_gate(g.x, y.x, act), fd_gate(g.y, y.y, act),
                        fd_gate(g.z, y.z, act), fd_gate(g.w, y.w, act));
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(FD_THREADS) void fs_gemm_kernel(FsArgs a) {
     // the pixel whose chunk this thread stages, the same at every time tap
     const long long ns = (long long)nt * FS_NT + ((threadIdx.x >> 2) & 63);
     const bool staged = ns < total;
-    const FsPixel sp(staged ? ns : 0, rows, a.T);
+    const DlBatchPixel sp(staged ? ns : 0, rows, a.T);
     const int q = threadIdx.x & 3;
     const int cblocks = KC / FS_KC;
 
@@ -156,11 +146,11 @@ __global__ __launch_bounds__(FD_THREADS) void fs_gemm_kernel(FsArgs a) {
             const int c = GX ? m0 + row : c0 + con;
             ar[u] = a.w[((long long)o * CIN + c) * 9 + kf * 3 + kt];
         }
-        const int row = row_of(slot, sp.f);
+        const int row = row_of(slot, sp.h);
         const bool ok = staged && row >= 0 && row < source_rows;
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
-            const int tt = sp.t + (GX ? 1 - u : u - 1);
+            const int tt = sp.w + (GX ? 1 - u : u - 1);
             br[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             if constexpr (GX) yr[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (ok && tt >= 0 && tt < a.T) {
@@ -223,18 +213,18 @@ __global__ __launch_bounds__(FD_THREADS) void fs_gemm_kernel(FsArgs a) {
 
     const long long n = (long long)nt * FS_NT + wave * 16 + col;
     const bool live = n < total;
-    const FsPixel px(live ? n : 0, rows, a.T);
+    const DlBatchPixel px(live ? n : 0, rows, a.T);
     if constexpr (!GX) {
         // the embedding: K element 4 step + k is (time tap, sin | cos), six
         // of the eight, read from the table at the tap's input row
 #pragma unroll
         for (int kf = 0; kf < 3; ++kf) {
-            const int row = S * px.f - 1 + kf;
+            const int row = S * px.h - 1 + kf;
             const bool ok = live && row >= 0 && row < a.F;
 #pragma unroll
             for (int step = 0; step < 2; ++step) {
                 const int id = 4 * step + k, kt = id >> 1, e = id & 1;
-                const int tt = px.t + kt - 1;
+                const int tt = px.w + kt - 1;
                 float v = 0.f;
                 if (ok && id < 6 && tt >= 0 && tt < a.T)
                     v = a.table[2 * row + e];
@@ -252,7 +242,7 @@ __global__ __launch_bounds__(FD_THREADS) void fs_gemm_kernel(FsArgs a) {
     if (!live) return;
     long long pixel = n;
     if (GX && S == 2)
-        pixel = ((long long)px.b * a.F + 2 * px.f + cls) * a.T + px.t;
+        pixel = ((long long)px.b * a.F + 2 * px.h + cls) * a.T + px.w;
     float* out = a.out + pixel * M + m0 + 4 * k;
 #pragma unroll
     for (int m = 0; m < MM; ++m) {
@@ -327,13 +317,13 @@ __global__ __launch_bounds__(FD_THREADS) void fs_gw_kernel(FsArgs a) {
             const int pix = ((int)threadIdx.x / QN) % FS_GW_PIX;
             const long long n = (long long)chunk * FS_GW_PIX + pix;
             const bool live = n < a.pixels;
-            const FsPixel px(live ? n : 0, a.Fo, a.T);
+            const DlBatchPixel px(live ? n : 0, a.Fo, a.T);
 #pragma unroll
             for (int u = 0; u < XV; ++u) {
                 const int idx = threadIdx.x + u * FD_THREADS;
                 const int tap = idx / (QN * FS_GW_PIX);
-                const int row = S * px.f - 1 + tap / 3;
-                const int tt = px.t - 1 + tap % 3;
+                const int row = S * px.h - 1 + tap / 3;
+                const int tt = px.w - 1 + tap % 3;
                 xr[u] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (live && idx < XN && row >= 0 && row < a.F && tt >= 0 &&
                     tt < a.T)
@@ -351,10 +341,10 @@ __global__ __launch_bounds__(FD_THREADS) void fs_gw_kernel(FsArgs a) {
                 const long long n = (long long)chunk * FS_GW_PIX + pix;
                 er[u] = 0.f;
                 if (n < a.pixels && column < 18) {
-                    const FsPixel px(n, a.Fo, a.T);
+                    const DlBatchPixel px(n, a.Fo, a.T);
                     const int tap = column >> 1;
-                    const int row = S * px.f - 1 + tap / 3;
-                    const int tt = px.t - 1 + tap % 3;
+                    const int row = S * px.h - 1 + tap / 3;
+                    const int tt = px.w - 1 + tap % 3;
                     if (row >= 0 && row < a.F && tt >= 0 && tt < a.T)
                         er[u] = a.table[2 * row + (column & 1)];
                 } else if (n < a.pixels && column == 18) {
@@ -441,16 +431,16 @@ __global__ __launch_bounds__(FD_THREADS) void fs_first_conv_kernel(FsArgs a) {
     if (idx >= a.pixels * 4) return;
     const long long p = idx >> 2;
     const int q = (int)(idx & 3);
-    const FsPixel px(p, a.Fo, a.T);
+    const DlBatchPixel px(p, a.Fo, a.T);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int kf = 0; kf < 3; ++kf) {
-        const int row = a.s * px.f - 1 + kf;
+        const int row = a.s * px.h - 1 + kf;
         if (row < 0 || row >= a.F) continue;
         const float sin = a.table[2 * row], cos = a.table[2 * row + 1];
 #pragma unroll
         for (int kt = 0; kt < 3; ++kt) {
-            const int tt = px.t - 1 + kt;
+            const int tt = px.w - 1 + kt;
             if (tt < 0 || tt >= a.T) continue;
             const float v = a.x[((long long)px.b * a.F + row) * a.T + tt];
             const float* w = wl + (kf * 3 + kt) * 48 + 4 * q;
@@ -474,15 +464,15 @@ __global__ __launch_bounds__(FD_THREADS) void fs_first_conv_kernel(FsArgs a) {
 __global__ __launch_bounds__(FD_THREADS) void fs_first_gx_kernel(FsArgs a) {
     const long long p = (long long)blockIdx.x * FD_THREADS + threadIdx.x;
     if (p >= a.pixels) return;
-    const FsPixel px(p, a.F, a.T);
+    const DlBatchPixel px(p, a.F, a.T);
     float acc = 0.f;
 #pragma unroll
     for (int kf = 0; kf < 3; ++kf) {
-        const int num = px.f + 1 - kf;
+        const int num = px.h + 1 - kf;
         if (num < 0 || num % a.s != 0 || num / a.s >= a.Fo) continue;
 #pragma unroll
         for (int kt = 0; kt < 3; ++kt) {
-            const int tt = px.t + 1 - kt;
+            const int tt = px.w + 1 - kt;
             if (tt < 0 || tt >= a.T) continue;
             const long long at =
                 (((long long)px.b * a.Fo + num / a.s) * a.T + tt) * 16;
@@ -515,17 +505,17 @@ __global__ __launch_bounds__(FD_THREADS) void fs_first_gw_kernel(FsArgs a) {
 #pragma unroll
     for (int e = 0; e < 28; ++e) acc[e] = 0.f;
     for (long long p = begin + slice; p < end; p += 16) {
-        const FsPixel px(p, a.Fo, a.T);
+        const DlBatchPixel px(p, a.Fo, a.T);
         const float gz = fd_gate(a.g[p * 16 + o], a.y[p * 16 + o], a.act);
 #pragma unroll
         for (int kf = 0; kf < 3; ++kf) {
-            const int row = a.s * px.f - 1 + kf;
+            const int row = a.s * px.h - 1 + kf;
             const bool in_f = row >= 0 && row < a.F;
             const float sin = in_f ? a.table[2 * row] : 0.f;
             const float cos = in_f ? a.table[2 * row + 1] : 0.f;
 #pragma unroll
             for (int kt = 0; kt < 3; ++kt) {
-                const int tt = px.t - 1 + kt;
+                const int tt = px.w - 1 + kt;
                 const bool in = in_f && tt >= 0 && tt < a.T;
                 const float v =
                     in ? a.x[((long long)px.b * a.F + row) * a.T + tt] : 0.f;

@@ -12,7 +12,8 @@
 // ARITHMETIC. fp32 throughout, on v_mfma_f32_16x16x4_f32 (DL_MFMA).
 //
 // THE KERNELS are implicit GEMMs over flattened pixels, as pc_gemm_kernel and
-// pc_gw_kernel (pm_pconv.h) are:
+// pc_gw_kernel (pm_pconv.h) are; the weight chunk and the chains of the
+// forward / gx kernel are the shared ones of pm_pixel_gemm.h:
 //   forward  M = output channels, N = pixels, K = (tap, channel). A tile is
 //            MT rows x GC_NT pixels, a wave 16 pixels of all rows. K runs in
 //            chunks of GC_KC channels: the chunk of the weight (the k taps of
@@ -41,7 +42,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "pm_dlayer.h"
+#include "pm_pixel_gemm.h"
 
 #define GC_THREADS 256
 #define GC_NT 64                // pixels of a tile of the forward and of gx
@@ -89,10 +90,9 @@ template <int K, int MT> constexpr int gc_gemm_lds() {
 template <bool GX, int K, int MT>
 __global__ __launch_bounds__(GC_THREADS) void gc_gemm_kernel(GcArgs a) {
     constexpr int MM = MT / 16, HALF = (K - 1) / 2;
-    constexpr int AV = MT * GC_KC * K / 4 / GC_THREADS;
+    constexpr int AV = pg_weight_vecs<K, MT, GC_KC>();
     constexpr int BV =
         (gc_rows<K>(GC_MAX_DILATION) * 8 + GC_THREADS - 1) / GC_THREADS;
-    static_assert(MT * GC_KC * K % (4 * GC_THREADS) == 0, "whole float4s");
     extern __shared__ float gc_lds[];
     float* wl = gc_lds;
     float* xl = gc_lds + K * MT * GC_PITCH;
@@ -114,23 +114,9 @@ __global__ __launch_bounds__(GC_THREADS) void gc_gemm_kernel(GcArgs a) {
     }
 
     float4 ar[AV], br[BV];
-    auto load = [&](int c0) {
-#pragma unroll
-        for (int u = 0; u < AV; ++u) {
-            const int idx = threadIdx.x + u * GC_THREADS;
-            if (!GX) {
-                // row o: the chunk's channels x the k taps in a run
-                const int row = idx / (GC_KC * K / 4);
-                const int f = idx % (GC_KC * K / 4);
-                ar[u] = *(const float4*)(
-                    a.w + ((long long)(m0 + row) * a.C + c0) * K + 4 * f);
-            } else {
-                // contracted o: the tile's rows c x the k taps in a run
-                const int o = idx / (MT * K / 4), f = idx % (MT * K / 4);
-                ar[u] = *(const float4*)(
-                    a.w + ((long long)(c0 + o) * a.C + m0) * K + 4 * f);
-            }
-        }
+    auto load = [&](int ci) {
+        const int c0 = ci * GC_KC;
+        pg_weight_load<GX, K, MT, GC_KC>(ar, a.w, a.C, m0, c0);
 #pragma unroll
         for (int u = 0; u < BV; ++u) {
             const int q = (threadIdx.x + u * GC_THREADS) & 7;
@@ -141,32 +127,14 @@ __global__ __launch_bounds__(GC_THREADS) void gc_gemm_kernel(GcArgs a) {
         }
     };
     auto store = [&]() {
-#pragma unroll
-        for (int u = 0; u < AV; ++u) {
-            const int idx = threadIdx.x + u * GC_THREADS;
-            const float v[4] = {ar[u].x, ar[u].y, ar[u].z, ar[u].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int row, con, slot;
-                if (!GX) {
-                    const int jj = 4 * (idx % (GC_KC * K / 4)) + e;
-                    row = idx / (GC_KC * K / 4); con = jj / K; slot = jj % K;
-                } else {
-                    const int jj = 4 * (idx % (MT * K / 4)) + e;
-                    con = idx / (MT * K / 4); row = jj / K;
-                    slot = K - 1 - jj % K;
-                }
-                wl[(slot * MT + row) * GC_PITCH + con] = v[e];
-            }
-        }
+        pg_weight_store<GX, K, MT, GC_KC, GC_PITCH>(
+            ar, wl, [](int tap) { return GX ? K - 1 - tap : tap; });
 #pragma unroll
         for (int u = 0; u < BV; ++u) {
             const int idx = threadIdx.x + u * GC_THREADS;
             if ((idx >> 3) >= rows) continue;
             float4 v = br[u];
-            if (!GX)
-                v = make_float4(dl_leaky(v.x, a.slope), dl_leaky(v.y, a.slope),
-                                dl_leaky(v.z, a.slope), dl_leaky(v.w, a.slope));
+            if (!GX) v = dl_leaky4(v, a.slope);
             *(float4*)(xl + (idx >> 3) * GC_PITCH + 4 * (idx & 7)) = v;
         }
     };
@@ -176,15 +144,7 @@ __global__ __launch_bounds__(GC_THREADS) void gc_gemm_kernel(GcArgs a) {
     const int t = n < a.pixels ? (int)((unsigned)n % (unsigned)a.T)
                                : -(1 << 30);
 
-    // [chunk parity][row tile][channel half]
-    dl_f4 acc[2][MM][2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int m = 0; m < MM; ++m)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                acc[p][m][h] = dl_f4{0.f, 0.f, 0.f, 0.f};
+    PgChains<MM> acc;
     auto mma = [&](dl_f4 (&to)[MM][2]) {
 #pragma unroll
         for (int slot = 0; slot < K; ++slot) {
@@ -214,17 +174,15 @@ __global__ __launch_bounds__(GC_THREADS) void gc_gemm_kernel(GcArgs a) {
         __syncthreads();            // the chunk before is read
         store();
         __syncthreads();
-        if (ci + 1 < chunks) load((ci + 1) * GC_KC);
-        if (ci & 1) mma(acc[1]);
-        else mma(acc[0]);
+        if (ci + 1 < chunks) load(ci + 1);
+        acc.step(ci, mma);
     }
 
     if (n >= a.pixels) return;
     const long long at = n * a.C + m0 + 4 * k;
 #pragma unroll
     for (int m = 0; m < MM; ++m) {
-        const dl_f4 sum =
-            (acc[0][m][0] + acc[0][m][1]) + (acc[1][m][0] + acc[1][m][1]);
+        const dl_f4 sum = acc.sum(m);
         float4 v = make_float4(sum[0], sum[1], sum[2], sum[3]);
         if (GX) {
             v = dl_gate4(v, *(const float4*)(a.x + at + 16 * m), a.slope);

@@ -37,25 +37,16 @@ const char* check_layer(int batch, int channels, int frames, int kernel,
 
 // The partials of gW and gb and the K chunks each takes. A function of the
 // sizes alone.
-struct Split { int parts, each, chunks; };
-Split split_of(const Sizes& z) {
-    const int chunks = (int)pm_ceil_div(z.pixels, GC_GW_PIX);
+PmChunkSplit split_of(const Sizes& z) {
     const int tiles = (z.C / z.gw_rows()) * (z.C / GC_GW_CT);
-    long long want = pm_ceil_div(chunks, GC_GW_MIN_CHUNKS);
-    const long long room = GC_GW_WORKGROUPS / tiles > 1
-        ? GC_GW_WORKGROUPS / tiles : 1;
-    if (want > room) want = room;
-    const int each = (int)pm_ceil_div(chunks, want);
-    return {(int)pm_ceil_div(chunks, each), each, chunks};
+    return pm_chunk_split(z.pixels, GC_GW_PIX, tiles, GC_GW_WORKGROUPS,
+                          GC_GW_MIN_CHUNKS);
 }
 
 // backward: the partials
-struct GcLayout { float* parts; size_t total; };
-GcLayout backward_layout(const Sizes& z, void* base) {
-    PmCarve c(base);
-    return {c.take<float>((size_t)split_of(z).parts *
-                          (size_t)z.partial_floats()),
-            c.used};
+PmPartsLayout backward_layout(const Sizes& z, void* base) {
+    return pm_parts_layout(base, (size_t)split_of(z).parts,
+                           (size_t)z.partial_floats());
 }
 
 GcArgs args_of(const Sizes& z, float slope) {
@@ -67,13 +58,10 @@ GcArgs args_of(const Sizes& z, float slope) {
 template <bool GX, int K, int MT>
 int launch_gemm(const GcArgs& a, hipStream_t s) {
     const int lds = gc_gemm_lds<K, MT>() * (int)sizeof(float);
-    auto kern = gc_gemm_kernel<GX, K, MT>;
-    PM_HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
     // (at most 2^25 pixel tiles x 4 row tiles)
     const long long grid = pm_ceil_div(a.pixels, GC_NT) * (a.C / MT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(GC_THREADS), lds, s, a);
-    PM_HIP_TRY(hipGetLastError());
-    return PM_OK;
+    return pm_launch_dynamic(gc_gemm_kernel<GX, K, MT>, (unsigned)grid,
+                             GC_THREADS, lds, s, a);
 }
 
 template <bool GX>
@@ -88,19 +76,16 @@ int launch_gemm_of(const GcArgs& a, const Sizes& z, hipStream_t s) {
 }
 
 template <int K, int OT>
-int launch_gw(GcArgs a, const Split& split, hipStream_t s) {
+int launch_gw(GcArgs a, const PmChunkSplit& split, hipStream_t s) {
     const int lds = gc_gw_lds<K, OT>() * (int)sizeof(float);
-    auto kern = gc_gw_kernel<K, OT>;
-    PM_HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
     a.chunks = split.chunks; a.per = split.each;
     const int tiles = (a.C / OT) * (a.C / GC_GW_CT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * split.parts)),
-                       dim3(GC_THREADS), lds, s, a);
-    PM_HIP_TRY(hipGetLastError());
-    return PM_OK;
+    return pm_launch_dynamic(gc_gw_kernel<K, OT>,
+                             (unsigned)(tiles * split.parts), GC_THREADS, lds,
+                             s, a);
 }
 
-int launch_gw_of(const GcArgs& a, const Sizes& z, const Split& split,
+int launch_gw_of(const GcArgs& a, const Sizes& z, const PmChunkSplit& split,
                  hipStream_t s) {
     if (z.C == 32)
         return z.K == 3 ? launch_gw<3, 32>(a, split, s)
@@ -149,7 +134,7 @@ extern "C" int pm_gconv_backward(
         return pm_fail(PM_EINVAL, "pm_gconv_backward: %s", why);
     if (const char* why = pm_check_slope(slope))
         return pm_fail(PM_EINVAL, "pm_gconv_backward: %s", why);
-    const GcLayout l = backward_layout(z, workspace);
+    const PmPartsLayout l = backward_layout(z, workspace);
     if (const int code = pm_check_backward(
             "pm_gconv_backward", upstream && x && weight, grad_weight,
             grad_bias, workspace, workspace_bytes, l.total))
@@ -163,7 +148,7 @@ extern "C" int pm_gconv_backward(
     }
     if (grad_weight) {      // (and grad_bias: pm_check_backward)
         a.parts = l.parts;
-        const Split split = split_of(z);
+        const PmChunkSplit split = split_of(z);
         if (const int code = launch_gw_of(a, z, split, s)) return code;
         PM_HIP_TRY(dl_reduce(l.parts, split.parts, z.partial_floats(), z.C,
                              grad_weight, grad_bias, s));

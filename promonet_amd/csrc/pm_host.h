@@ -65,6 +65,24 @@ static inline PmSplit pm_pixel_split(long long pixels, int chunk,
     return {(int)pm_ceil_div(pixels, each), each};
 }
 
+// The partials a tile of the gW kernels that are GEMMs over flattened pixels
+// (pc_gw_kernel, gc_gw_kernel, fs_gw_kernel), and the K
+// chunks of each: K = `pixels` runs in chunks of `pixels_per_chunk`, and a
+// tile's chunks go to at most `workgroups` / `tiles` partials (one at the
+// least) of `min_chunks` chunks or more (but the last). A function of the
+// sizes alone.
+struct PmChunkSplit { int parts, each, chunks; };
+static inline PmChunkSplit pm_chunk_split(long long pixels,
+                                          int pixels_per_chunk, int tiles,
+                                          int workgroups, int min_chunks) {
+    const int chunks = (int)pm_ceil_div(pixels, pixels_per_chunk);
+    long long want = pm_ceil_div(chunks, min_chunks);
+    const long long room = workgroups / tiles > 1 ? workgroups / tiles : 1;
+    if (want > room) want = room;
+    const int each = (int)pm_ceil_div(chunks, want);
+    return {(int)pm_ceil_div(chunks, each), each, chunks};
+}
+
 // The checks of a conv layer's backward after its sizes: the pointers, then
 // the workspace of `needed` bytes, which only the weight gradients use.
 // `inputs`: no tensor that the entry reads is null.
@@ -97,6 +115,15 @@ struct PmCarve {
     }
 };
 
+// The workspace of a conv layer's backward: the `parts` partials of gW | gb,
+// `partial_floats` each
+struct PmPartsLayout { float* parts; size_t total; };
+static inline PmPartsLayout pm_parts_layout(void* base, size_t parts,
+                                            size_t partial_floats) {
+    PmCarve c(base);
+    return {c.take<float>(parts * partial_floats), c.used};
+}
+
 // Do the byte ranges [a, a + an) and [b, b + bn) share a byte? A null or an
 // empty range overlaps nothing.
 static inline bool pm_overlap(
@@ -111,6 +138,17 @@ static inline bool pm_overlap(
 // driving several GPUs sets it on each, and guarded so that concurrent
 // launches from several host threads / streams are safe.
 hipError_t pm_ensure_dynamic_lds(const void* kern, int bytes);
+
+// Launch `kern` on `grid` workgroups of `threads` with `lds` bytes of dynamic
+// LDS, granted first
+template <class Kernel, class Args>
+int pm_launch_dynamic(Kernel kern, unsigned grid, int threads, int lds,
+                      hipStream_t s, const Args& a) {
+    PM_HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
+    PM_HIP_TRY(hipGetLastError());
+    return PM_OK;
+}
 
 // Compute units of the current device, queried once per device (the walked
 // launches size their grids from it on every forward).

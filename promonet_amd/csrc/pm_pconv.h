@@ -16,7 +16,9 @@
 // v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 sums).
 //
 // THE GENERAL KERNELS (layers 2 to 5) are implicit GEMMs over flattened
-// pixels, so that a tile is full whatever the period and the height:
+// pixels, so that a tile is full whatever the period and the height; the
+// weight chunk and the chains of the forward / gx kernel are the shared ones
+// of pm_pixel_gemm.h:
 //   forward  M = O, N = output pixels (b, ho, w), K = (tap, channel). A tile
 //            is 64 rows x PC_NT pixels, a wave 16 pixels of all rows. K
 //            runs in chunks of PC_KC channels: the chunk of the weight (all
@@ -55,7 +57,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "pm_dlayer.h"
+#include "pm_pixel_gemm.h"
 
 #define PC_THREADS 256
 #define PC_NT 64                // pixels of a tile of the forward and of gx
@@ -98,7 +100,7 @@ template <bool GX, int S, int MT>
 __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
     constexpr int SLOTS = (GX && S == 3) ? 2 : 5;
     constexpr int MM = MT / 16;
-    constexpr int AV = MT * PC_KC * 5 / 4 / PC_THREADS;
+    constexpr int AV = pg_weight_vecs<5, MT, PC_KC>();
     constexpr int BV = SLOTS * PC_NT * 8 / PC_THREADS;
     extern __shared__ float pc_lds[];
     float* wl = pc_lds;
@@ -149,22 +151,9 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
     }
 
     float4 ar[AV], br[BV], yr[GX ? BV : 1];
-    auto load = [&](int c0) {
-#pragma unroll
-        for (int u = 0; u < AV; ++u) {
-            const int idx = threadIdx.x + u * PC_THREADS;
-            if (!GX) {
-                // row o: the chunk's channels x five taps, 160 floats in a run
-                const int row = idx / 40, f = idx % 40;
-                ar[u] = *(const float4*)(
-                    a.w + ((long long)(m0 + row) * a.C + c0) * 5 + 4 * f);
-            } else {
-                // contracted o: the tile's rows c x five taps in a run
-                const int o = idx / (MT * 5 / 4), f = idx % (MT * 5 / 4);
-                ar[u] = *(const float4*)(
-                    a.w + ((long long)(c0 + o) * a.C + m0) * 5 + 4 * f);
-            }
-        }
+    auto load = [&](int ci) {
+        const int c0 = ci * PC_KC;
+        pg_weight_load<GX, 5, MT, PC_KC>(ar, a.w, a.C, m0, c0);
 #pragma unroll
         for (int u = 0; u < BV; ++u) {
             const int q = (threadIdx.x + u * PC_THREADS) & 7;
@@ -178,27 +167,11 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
         }
     };
     auto store = [&]() {
-#pragma unroll
-        for (int u = 0; u < AV; ++u) {
-            const int idx = threadIdx.x + u * PC_THREADS;
-            const float v[4] = {ar[u].x, ar[u].y, ar[u].z, ar[u].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int row, con, tap;
-                if (!GX) {
-                    const int jj = 4 * (idx % 40) + e;
-                    row = idx / 40; con = jj / 5; tap = jj % 5;
-                } else {
-                    const int jj = 4 * (idx % (MT * 5 / 4)) + e;
-                    con = idx / (MT * 5 / 4); row = jj / 5; tap = jj % 5;
-                }
-                int slot = tap;
-                if (GX && S == 3)
-                    slot = tap == tap0 ? 0 : (cls && tap == tap1) ? 1 : -1;
-                if (slot >= 0)
-                    wl[(slot * MT + row) * PC_PITCH + con] = v[e];
-            }
-        }
+        pg_weight_store<GX, 5, MT, PC_KC, PC_PITCH>(ar, wl, [&](int tap) {
+            if (GX && S == 3)
+                return tap == tap0 ? 0 : (cls && tap == tap1) ? 1 : -1;
+            return tap;
+        });
 #pragma unroll
         for (int u = 0; u < BV; ++u) {
             const int idx = threadIdx.x + u * PC_THREADS;
@@ -208,15 +181,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
         }
     };
 
-    // [chunk parity][row tile][channel half]
-    dl_f4 acc[2][MM][2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int m = 0; m < MM; ++m)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                acc[p][m][h] = dl_f4{0.f, 0.f, 0.f, 0.f};
+    PgChains<MM> acc;
     auto mma = [&](dl_f4 (&to)[MM][2]) {
 #pragma unroll
         for (int slot = 0; slot < SLOTS; ++slot) {
@@ -236,16 +201,14 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
             }
         }
     };
-
     const int chunks = KC / PC_KC;
     load(0);
     for (int ci = 0; ci < chunks; ++ci) {
         __syncthreads();            // the chunk before is read
         store();
         __syncthreads();
-        if (ci + 1 < chunks) load((ci + 1) * PC_KC);
-        if (ci & 1) mma(acc[1]);
-        else mma(acc[0]);
+        if (ci + 1 < chunks) load(ci + 1);
+        acc.step(ci, mma);
     }
 
     const long long n = (long long)nt * PC_NT + wave * 16 + col;
@@ -259,8 +222,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gemm_kernel(PcArgs a) {
     float* out = a.out + pixel * M + m0 + 4 * k;
 #pragma unroll
     for (int m = 0; m < MM; ++m) {
-        const dl_f4 sum =
-            (acc[0][m][0] + acc[0][m][1]) + (acc[1][m][0] + acc[1][m][1]);
+        const dl_f4 sum = acc.sum(m);
         if (GX) {
             *(float4*)(out + 16 * m) =
                 make_float4(sum[0], sum[1], sum[2], sum[3]);
@@ -393,18 +355,9 @@ __global__ __launch_bounds__(PC_THREADS) void pc_gw_kernel(PcArgs a) {
 // The first layer, 1 -> 32 at k 5, s 3, on the audio (B, T). The folded map
 // is (B, H, P) with H = (T + pad) / P; its pixel (h, w) is the sample h P + w,
 // reflected about T - 1 past the end. 32-bit pixel arithmetic: the host
-// refuses more than 2^31 - 1 pixels. (DlPixel with the batch row, which finds
-// the audio: the kernels of the last layer read h alone, and none walks.)
+// refuses more than 2^31 - 1 pixels. The batch row of a pixel (DlBatchPixel)
+// finds the audio.
 // ---------------------------------------------------------------------------
-struct PcPixel {
-    int b, h, w;
-    __device__ __forceinline__ PcPixel(long long p, int H, int P) {
-        const unsigned row = (unsigned)p / (unsigned)P;
-        w = (int)((unsigned)p - row * (unsigned)P);
-        h = (int)(row % (unsigned)H);
-        b = (int)(row / (unsigned)H);
-    }
-};
 
 // the folded map at row h (zero outside), column w of the batch row `audio`
 __device__ __forceinline__ float pc_folded(const float* __restrict__ audio,
@@ -431,7 +384,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_fold_conv_kernel(PcArgs a) {
     if (idx >= a.pixels * 8) return;
     const long long p = idx >> 3;
     const int q = (int)(idx & 7);
-    const PcPixel px(p, a.Ho, a.P);
+    const DlBatchPixel px(p, a.Ho, a.P);
     const float* audio = a.x + (long long)px.b * a.T;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -503,7 +456,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_fold_gw_kernel(PcArgs a) {
         begin + a.span < a.pixels ? begin + a.span : a.pixels;
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (long long p = begin + slice; p < end; p += 8) {
-        const PcPixel px(p, a.Ho, a.P);
+        const DlBatchPixel px(p, a.Ho, a.P);
         const float* audio = a.x + (long long)px.b * a.T;
         const float gz = dl_gate(a.g[p * 32 + o], a.y[p * 32 + o], a.slope);
 #pragma unroll
@@ -534,7 +487,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_post_conv_kernel(PcArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long p = (long long)blockIdx.x * 4 + wave;
     if (p >= a.pixels) return;
-    const PcPixel px(p, a.H, a.P);
+    const DlBatchPixel px(p, a.H, a.P);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -570,7 +523,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_post_gx_kernel(PcArgs a) {
     if (idx >= a.pixels * 256) return;
     const long long p = idx >> 8;
     const int c = 4 * (int)(idx & 255);
-    const PcPixel px(p, a.H, a.P);
+    const DlBatchPixel px(p, a.H, a.P);
     float wv[12];
 #pragma unroll
     for (int f = 0; f < 3; ++f) {
@@ -604,7 +557,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_post_gw_kernel(PcArgs a) {
     float acc[4][3] = {};
     float accb = 0.f;
     for (long long p = begin; p < end; ++p) {
-        const PcPixel px(p, a.H, a.P);
+        const DlBatchPixel px(p, a.H, a.P);
         const float4 v = *(const float4*)(a.x + p * 1024 + c);
 #pragma unroll
         for (int t = 0; t < 3; ++t) {

@@ -72,8 +72,7 @@ const char* check_fold(int batch, int samples, int period, Sizes* z) {
 
 // The partials of gW and gb and what each takes: K chunks of a tile (the
 // general layers) or pixels (the edges). A function of the sizes alone.
-struct Split { int parts, each, chunks; };
-Split split_of(const Sizes& z) {
+PmChunkSplit split_of(const Sizes& z) {
     if (z.first() || z.post()) {
         const long long pixels = z.first() ? z.out_pixels : z.in_pixels;
         long long each = pm_ceil_div(pixels, PC_EDGE_MAX_PARTS);
@@ -81,23 +80,15 @@ Split split_of(const Sizes& z) {
         if (each < least) each = least;
         return {(int)pm_ceil_div(pixels, each), (int)each, 0};
     }
-    const int chunks = (int)pm_ceil_div(z.out_pixels, PC_GW_PIX);
     const int tiles = (z.O / 64) * (z.C / (z.C < 64 ? 32 : 64));
-    long long want = pm_ceil_div(chunks, PC_GW_MIN_CHUNKS);
-    const long long room = PC_GW_WORKGROUPS / tiles > 1
-        ? PC_GW_WORKGROUPS / tiles : 1;
-    if (want > room) want = room;
-    const int each = (int)pm_ceil_div(chunks, want);
-    return {(int)pm_ceil_div(chunks, each), each, chunks};
+    return pm_chunk_split(z.out_pixels, PC_GW_PIX, tiles, PC_GW_WORKGROUPS,
+                          PC_GW_MIN_CHUNKS);
 }
 
 // backward: the partials
-struct PcLayout { float* parts; size_t total; };
-PcLayout backward_layout(const Sizes& z, void* base) {
-    PmCarve c(base);
-    return {c.take<float>((size_t)split_of(z).parts *
-                          (size_t)z.partial_floats()),
-            c.used};
+PmPartsLayout backward_layout(const Sizes& z, void* base) {
+    return pm_parts_layout(base, (size_t)split_of(z).parts,
+                           (size_t)z.partial_floats());
 }
 
 PcArgs args_of(const Sizes& z, float slope) {
@@ -112,8 +103,6 @@ template <bool GX, int S, int MT>
 int launch_gemm(PcArgs a, const Sizes& z, hipStream_t s) {
     constexpr int SLOTS = (GX && S == 3) ? 2 : 5;
     const int lds = SLOTS * (MT + PC_NT) * PC_PITCH * (int)sizeof(float);
-    auto kern = pc_gemm_kernel<GX, S, MT>;
-    PM_HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
     long long ntiles;
     if (GX && S == 3) {
         ntiles = 0;
@@ -126,23 +115,20 @@ int launch_gemm(PcArgs a, const Sizes& z, hipStream_t s) {
         ntiles = pm_ceil_div(GX ? z.in_pixels : z.out_pixels, PC_NT);
     }
     const long long grid = ntiles * ((GX ? z.C : z.O) / MT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(PC_THREADS), lds, s, a);
-    PM_HIP_TRY(hipGetLastError());
-    return PM_OK;
+    return pm_launch_dynamic(pc_gemm_kernel<GX, S, MT>, (unsigned)grid,
+                             PC_THREADS, lds, s, a);
 }
 
 template <int S, int CT>
-int launch_gw(PcArgs a, const Sizes& z, const Split& split, hipStream_t s) {
+int launch_gw(PcArgs a, const Sizes& z, const PmChunkSplit& split,
+              hipStream_t s) {
     const int lds =
         PC_GW_PIX * (64 + 16 + 5 * (CT + 16)) * (int)sizeof(float);
-    auto kern = pc_gw_kernel<S, CT>;
-    PM_HIP_TRY(pm_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
     a.chunks = split.chunks; a.per = split.each;
     const int tiles = (z.O / 64) * (z.C / CT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * split.parts)),
-                       dim3(PC_THREADS), lds, s, a);
-    PM_HIP_TRY(hipGetLastError());
-    return PM_OK;
+    return pm_launch_dynamic(pc_gw_kernel<S, CT>,
+                             (unsigned)(tiles * split.parts), PC_THREADS, lds,
+                             s, a);
 }
 
 int forward(const char* entry, const Sizes& z, const float* x,
@@ -176,7 +162,7 @@ int backward(const char* entry, const Sizes& z, const float* upstream,
              void* workspace, size_t workspace_bytes, void* stream) {
     if (const char* why = pm_check_slope(slope))
         return pm_fail(PM_EINVAL, "%s: %s", entry, why);
-    const PcLayout l = backward_layout(z, workspace);
+    const PmPartsLayout l = backward_layout(z, workspace);
     if (const int code = pm_check_backward(
             entry, upstream && y && x && weight, grad_weight, grad_bias,
             workspace, workspace_bytes, l.total))
@@ -208,7 +194,7 @@ int backward(const char* entry, const Sizes& z, const float* upstream,
     }
     if (grad_weight) {      // (and grad_bias: pm_check_backward)
         a.parts = l.parts;
-        const Split split = split_of(z);
+        const PmChunkSplit split = split_of(z);
         if (z.first() || z.post()) {
             a.span = split.each;
             if (z.first())
