@@ -28,8 +28,15 @@ $(OBJ)/pm_lpc.o: CXXFLAGS += -fhonor-nans -fno-slp-vectorize
 # its own (pm_limit.h)
 $(OBJ)/pm_limit.o: CXXFLAGS += -ffp-contract=off
 # the multi-tensor mean rounds every product and sum on its own, as the fp32
-# restatement of its tests does; its division stays correctly rounded (pm_adv.h)
-$(OBJ)/pm_adv.o: CXXFLAGS += -ffp-contract=off
+# restatement of its tests does; its division stays correctly rounded
+# (pm_adv.h); the hinge of a NaN logit is NaN, as torch.clamp's is
+$(OBJ)/pm_adv.o: CXXFLAGS += -ffp-contract=off -fhonor-nans
+# torch's semantics on inf and NaN (pm_nonfinite.h): the
+# ReLU of the FARGAN discriminator's layers, the decibel spectrogram's clamp,
+# maximum and floor, and the spectral-convergence loss's clamp keep a NaN, so
+# an overflow reaches the optimizer's scaler; without -fhonor-nans the tests
+# of a NaN fold to false
+$(OBJ)/pm_fdisc.o $(OBJ)/pm_disc_spec.o $(OBJ)/pm_loss.o: CXXFLAGS += -fhonor-nans
 # the optimizer step is bit for bit its restatement (tests/optim_oracle.py):
 # every fp32 and double product and sum rounds on its own, and a NaN gradient
 # is counted: without -fhonor-nans the compiler reads the test of the exponent

@@ -22,12 +22,18 @@
 //
 // Built with -ffp-contract=off (Makefile): every product and sum rounds on
 // its own, as the fp32 restatement of the tests does.
+//
+// NON-FINITE VALUES. This header promises torch's semantics on inf and NaN
+// (DESIGN section 27): a term of a NaN is NaN, as torch.clamp(min=0) keeps
+// it, so an overflowed logit reaches the mean, the total and the scaler. The
+// object is built with -fhonor-nans (Makefile), or the test of a NaN folds.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "promonet_hip.h"
 // the chunk, the loads and stores, adv_block_sum and adv_ordered_sum
 #include "pm_multi.h"
+#include "pm_nonfinite.h"
 
 #define ADV_MAX_ENTRIES 64
 #define ADV_FINAL_THREADS 1024
@@ -62,8 +68,8 @@ __device__ __forceinline__ float adv_term(float a, float b) {
     if (OP == PM_ADV_ABS_DIFF) return fabsf(a - b);
     if (OP == PM_ADV_SQ_ONE_MINUS) { const float d = 1.f - a; return d * d; }
     if (OP == PM_ADV_SQ) return a * a;
-    if (OP == PM_ADV_HINGE_ONE_MINUS) return fmaxf(1.f - a, 0.f);
-    return fmaxf(1.f + a, 0.f);
+    if (OP == PM_ADV_HINGE_ONE_MINUS) return pm_max_nan(1.f - a, 0.f);
+    return pm_max_nan(1.f + a, 0.f);
 }
 
 // c = grad_out / numel; at most one multiplication that rounds (2 x is exact)

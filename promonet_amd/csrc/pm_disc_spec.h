@@ -24,9 +24,17 @@
 // whole upstream goes to the floor (torch gives each side a half).
 //
 // No float atomics, fixed-order partial sums: the same bits on every run.
+//
+// NON-FINITE VALUES. This header promises torch's semantics on inf and NaN
+// (DESIGN section 27): torch.clamp, amax and maximum keep a NaN, so one NaN
+// bin makes the maximum, the floor and with them the whole decibel
+// spectrogram NaN, and amax's backward (the upstream over the number of
+// maxima, none of which equals a NaN) makes the whole gradient NaN. The
+// object is built with -fhonor-nans (Makefile), or the test of a NaN folds.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pm_nonfinite.h"
 #include "pm_stockham.h"
 
 #define DS_R 0
@@ -51,15 +59,15 @@ struct DsArgs {
     ScPlan p;
 };
 
-// Maximum over the workgroup; the result is valid in thread 0.
+// Maximum over the workgroup (NaN if any is); the result is valid in thread 0.
 __device__ __forceinline__ float ds_block_max(float v, float* scratch) {
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+    for (int m = 32; m >= 1; m >>= 1) v = pm_max_nan(v, __shfl_xor(v, m, 64));
     __syncthreads();
     if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
     __syncthreads();
     float top = scratch[0];
-    for (int w = 1; w < SC_THREADS / 64; ++w) top = fmaxf(top, scratch[w]);
+    for (int w = 1; w < SC_THREADS / 64; ++w) top = pm_max_nan(top, scratch[w]);
     return top;
 }
 
@@ -108,8 +116,8 @@ __global__ __launch_bounds__(SC_THREADS) void ds_transform_kernel(DsArgs a) {
         const float mx = sqrtf(X.x * X.x + X.y * X.y);
         if (!GRAD) {
             if (MODE == DS_DB) {
-                const float db = 20.f * log10f(fmaxf(mx, DS_AMIN));
-                top = fmaxf(top, db);
+                const float db = 20.f * log10f(pm_max_nan(mx, DS_AMIN));
+                top = pm_max_nan(top, db);
                 a.out[at] = db;
             } else {
                 a.out[at] = mx;
@@ -120,6 +128,9 @@ __global__ __launch_bounds__(SC_THREADS) void ds_transform_kernel(DsArgs a) {
                 const float o = a.saved[at];
                 float f = o > floor_db ? a.upstream[at] : 0.f;
                 if (o == peak) f += share;
+                // (a NaN maximum: no element holds it, and the floored
+                // upstream over their number, none, is NaN everywhere)
+                if (peak != peak) f = peak;
                 if (mx >= DS_AMIN) c = f * DS_DB_SLOPE / (mx * mx);
             } else if (mx > 0.f) {
                 c = a.upstream[at] / mx;
@@ -141,7 +152,7 @@ __global__ __launch_bounds__(SC_THREADS) void ds_floor_kernel(
     __shared__ float scratch[SC_THREADS / 64];
     float top = -3.0e38f;
     for (long long i = threadIdx.x; i < count; i += SC_THREADS)
-        top = fmaxf(top, partials[i]);
+        top = pm_max_nan(top, partials[i]);
     top = ds_block_max(top, scratch);
     if (threadIdx.x == 0) {
         stats[0] = top;
@@ -155,7 +166,7 @@ __global__ __launch_bounds__(SC_THREADS) void ds_apply_floor_kernel(
     const float* __restrict__ stats) {
     const long long at = (long long)blockIdx.x * SC_THREADS + threadIdx.x;
     if (at >= total) return;
-    out[at] = fmaxf(out[at], stats[1]);
+    out[at] = pm_max_nan(out[at], stats[1]);
 }
 
 // DB, before the bin gradient: per workgroup the sum of the upstream over the

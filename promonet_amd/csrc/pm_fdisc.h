@@ -29,10 +29,17 @@
 // partial goes to the workspace, and dl_reduce_kernel (pm_dlayer.h) adds the
 // partials in a fixed order in double. Their count and the pixels of each are
 // a function of the sizes alone: no float atomics, the same bits on every run.
+//
+// NON-FINITE VALUES. This header promises torch's semantics on inf and NaN
+// (DESIGN section 27): relu(NaN) is NaN and passes its upstream gradient, a
+// non-finite input or upstream reaches exactly the outputs that a tap links it
+// to, and no other element changes a bit. The object is built with
+// -fhonor-nans (Makefile), or the test of a NaN folds.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "pm_dlayer.h"
+#include "pm_nonfinite.h"
 
 #define FD_NONE 0
 #define FD_RELU 1
@@ -74,14 +81,17 @@ __device__ __forceinline__ long long fd_tap_offset(int tap, int d, int T) {
     return dl_offset((long long)(tap / 3 - 1) * d, tap % 3 - 1, T);
 }
 
+// (torch.relu keeps a NaN)
 __device__ __forceinline__ float fd_activate(float v, int act) {
-    if (act == FD_RELU) return fmaxf(v, 0.f);
+    if (act == FD_RELU) return pm_max_nan(v, 0.f);
     if (act == FD_SIGMOID) return 1.f / (1.f + expf(-v));
     return v;
 }
-// upstream * act'(y)
+// upstream * act'(y); relu as torch's threshold_backward: 0 where y <= 0, the
+// upstream elsewhere, so a NaN output passes it, and a choice, not a product:
+// an infinite upstream behind a closed gate gives 0
 __device__ __forceinline__ float fd_gate(float g, float y, int act) {
-    if (act == FD_RELU) return y > 0.f ? g : 0.f;
+    if (act == FD_RELU) return y <= 0.f ? 0.f : g;
     if (act == FD_SIGMOID) return g * (y * (1.f - y));
     return g;
 }
@@ -284,17 +294,18 @@ __global__ __launch_bounds__(FD_THREADS) void fd_gx_c1_kernel(FdArgs a) {
 //       C = 16: 9 tiles of the 16 channels at a tap, then the 18 (tap, sin /
 //               cos) pairs and, column 162, one (gb);
 //       C = 1:  (tap, x / sin / cos) = 27 columns, then one;
-//   O = 1 (C = 16): A[c][pixel] = x, B[pixel][tap] = gz at the mirrored tap;
-//     a second tile has the rows sin, cos, one (gb at the centre tap).
+//   O = 1 (C = 16): a tile a tap, A[c][pixel] = x where the mirrored tap is
+//     inside the map, B[pixel][any column] = gz at that tap; a tenth tile has
+//     the rows sin, cos, one (gb at the centre tap) and the taps as columns.
 // fd_slot: where tile m, row i, column j goes in (O, C + 2, 3, 3) | (O), or -1.
 // ---------------------------------------------------------------------------
 template <int C, int O> struct FdGw {
     static constexpr int FAN = (C + 2) * 9;
     static constexpr int N = O * FAN + O;           // floats of a partial
-    static constexpr int NM = O == 1 ? 2 : (C == 16 ? 11 : 2);
+    static constexpr int NM = O == 1 ? 10 : (C == 16 ? 11 : 2);
     __device__ static __forceinline__ int slot(int m, int i, int j) {
         if (O == 1) {
-            if (m == 0) return j < 9 ? i * 9 + j : -1;
+            if (m < 9) return j == 0 ? i * 9 + m : -1;
             if (i < 2) return j < 9 ? (16 + i) * 9 + j : -1;
             return (i == 2 && j == 4) ? FAN : -1;
         }
@@ -370,10 +381,21 @@ __global__ __launch_bounds__(FD_THREADS) void fd_gw_kernel(FdArgs a) {
             float ev = 0.f;
             if (live && j < 3)
                 ev = j == 2 ? 1.f : a.table[2 * px.h + j];
-            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                xv, gz, acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                ev, gz, acc[1], 0, 0, 0);
+            // One tile a tap, every column the tap's gz: where the tap leaves
+            // the map x is left out, not multiplied by the 0 that gz is
+            // there, or an infinite x on a border pixel would make that
+            // product a NaN. The same products in the same order as one
+            // tile with the taps as its columns, to the bit.
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                const bool in =
+                    live && fd_tap_f(px, tap, a.d, a.F, a.T, -1) >= 0;
+                acc[tap] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                    in ? xv : 0.f, __shfl(gz, (k << 4) | tap, 64), acc[tap],
+                    0, 0, 0);
+            }
+            acc[9] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                ev, gz, acc[9], 0, 0, 0);
         }
     }
     dl_gw_store<G>(acc, a.parts);

@@ -44,6 +44,11 @@
 //            count is a function of the sizes alone: no float atomics.
 // THE EDGES are plain VALU kernels: the first layer (1 -> 16 at s = 2) with
 // its gx and gW, and the last (C -> 1 at s = 1, C = 32 ... 256) likewise.
+//
+// NON-FINITE VALUES. This header promises torch's semantics on inf and NaN
+// (DESIGN section 27), with pm_fdisc.h's activation and gate: a non-finite
+// input or upstream reaches exactly the outputs that a tap links it to, and no
+// other element changes a bit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -634,11 +639,11 @@ __global__ __launch_bounds__(FD_THREADS) void fs_last_gw_kernel(FsArgs a) {
         const float sin = a.table[2 * px.h], cos = a.table[2 * px.h + 1];
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            float gz = 0.f;
-            if (fd_tap_f(px, tap, 1, a.F, a.T, -1) >= 0) {
-                const long long at = p - fd_tap_offset(tap, 1, a.T);
-                gz = fd_gate(a.g[at], a.y[at], a.act);
-            }
+            // (a tap that leaves the map adds nothing: no product of its zero
+            // with x, which an infinite x would turn into a NaN)
+            if (fd_tap_f(px, tap, 1, a.F, a.T, -1) < 0) continue;
+            const long long at = p - fd_tap_offset(tap, 1, a.T);
+            const float gz = fd_gate(a.g[at], a.y[at], a.act);
             acc[0][tap] = fmaf(gz, v.x, acc[0][tap]);
             acc[1][tap] = fmaf(gz, v.y, acc[1][tap]);
             acc[2][tap] = fmaf(gz, v.z, acc[2][tap]);

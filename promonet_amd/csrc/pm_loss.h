@@ -9,9 +9,15 @@
 // Nothing here uses a float atomic: sums go through per-workgroup partials and
 // one final pass, overlap-add is in gather form, so every output is the same
 // bits on every run.
+//
+// NON-FINITE VALUES. This header promises torch's semantics on inf and NaN
+// (DESIGN section 27): sqrt(clamp(|X|, min=1e-7)) of a NaN bin is NaN, and so
+// are its bin gradient, the two sums and the loss. The object is built with
+// -fhonor-nans (Makefile), or the test of a NaN folds.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pm_nonfinite.h"
 #include "pm_stockham.h"
 
 #define SC_FLOOR 1e-7f              // torch.clamp(magnitude, min=1e-7)
@@ -60,12 +66,12 @@ __global__ __launch_bounds__(SC_THREADS) void sc_forward_kernel(
         const long long at = base + (long long)k * p.frames + f0 + fl;
         const float2 X = sc_bin(Z + fl * p.M, tw, p.M, k);
         const float mx = sqrtf(X.x * X.x + X.y * X.y);
-        const float sx = sqrtf(fmaxf(mx, SC_FLOOR));
+        const float sx = sqrtf(pm_max_nan(mx, SC_FLOOR));
         float factor = 0.f;
         if (PAIR) {
             const float2 Y = sc_bin(Z + (count + fl) * p.M, tw, p.M, k);
             const float sy =
-                sqrtf(fmaxf(sqrtf(Y.x * Y.x + Y.y * Y.y), SC_FLOOR));
+                sqrtf(pm_max_nan(sqrtf(Y.x * Y.x + Y.y * Y.y), SC_FLOOR));
             const float d = sy - sx;
             sum1 += fabsf(d);
             sum2 += sy;
@@ -76,7 +82,9 @@ __global__ __launch_bounds__(SC_THREADS) void sc_forward_kernel(
         }
         if (a.G) {
             float2 g = make_float2(0.f, 0.f);
-            if (mx > SC_FLOOR) {
+            // (0 at and under the floor; a NaN bin keeps its NaN, as the
+            // phase X / |X| of torch's gradient does)
+            if (!(mx <= SC_FLOOR)) {
                 const float c = factor * .5f / (sx * mx);
                 g = make_float2(c * X.x, c * X.y);
             }

@@ -181,11 +181,14 @@ def layer_backward(x, weight, y, upstream, dilation, activation, defect=None,
         weight = weight.transpose(2, 3)
     channels = x.shape[1]
     if activation == 'relu':
-        mask = y > 0.
+        # torch's threshold_backward: 0 where y <= 0, the upstream elsewhere
+        # (a NaN output passes it), a choice and not a product (an infinite
+        # upstream behind a closed gate gives 0)
+        mask = ~(y <= 0.)
         if defect == 'relu_mask_from_input':
             mask = (x if channels == y.shape[1] else x[:, :1]) > 0.
             mask = mask.expand_as(y)
-        gz = upstream * mask
+        gz = torch.where(mask, upstream, torch.zeros_like(upstream))
     elif activation == 'sigmoid':
         gz = upstream if defect == 'sigmoid_gradient_left_out' \
             else upstream * y * (1. - y)

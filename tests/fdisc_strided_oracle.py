@@ -145,8 +145,10 @@ def tap_input(x, stride, kf, kt, defect=None, table=None):
     out = x.new_zeros(batch, channels + 2, rows_out, frames_out)
     picked = x[:, :, rows.clamp(0, bins - 1)][
         :, :, :, columns.clamp(0, frames - 1)]
-    mask = (row_in[:, None] & column_in[None, :]).double()
-    out[:, :channels] = picked * mask
+    # (a choice and not a product: the padding is zero whatever the clamped
+    # index holds, a non-finite value included)
+    mask = row_in[:, None] & column_in[None, :]
+    out[:, :channels] = torch.where(mask, picked, torch.zeros_like(picked))
     at = torch.arange(rows_out) if defect == 'embedding_at_output_row' \
         else rows
     sin, cos = embedding_rows(bins, at, sf, defect, table)
@@ -245,7 +247,8 @@ def layer_backward(x, weight, y, upstream, stride, activation, defect=None,
     upstream = upstream.double()
     channels = x.shape[1]
     if activation == 'relu':
-        gz = upstream * (y > 0.)
+        # torch's threshold_backward (tests/fdisc_oracle.py, layer_backward)
+        gz = torch.where(y <= 0., torch.zeros_like(upstream), upstream)
     elif activation == 'sigmoid':
         gz = upstream * y * (1. - y)
     else:
