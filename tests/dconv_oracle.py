@@ -4,9 +4,9 @@ multi-resolution discriminators (promonet/model/discriminator.py:96-127 and
     y = leaky(conv2d(x, W, b, stride (1, s), padding (1, (kw - 1) / 2)), slope)
 with the zero padding explicit and the taps an explicit loop (no conv2d), its
 gradients gz, gx, gW and gb written out by hand, and the two stacks with their
-gradients (weight norm: tests/fdisc_oracle.py). `defect` plants one wrong
-reading (DEFECTS, STACK_DEFECTS): the comparisons of the GPU tests must reject
-each of them (tests/test_cpu_dconv.py).
+gradients (the loop over the taps and weight norm: tests/conv_oracle.py).
+`defect` plants one wrong reading (DEFECTS, STACK_DEFECTS): the comparisons of
+the GPU tests must reject each of them (tests/test_cpu_dconv.py).
 
 Also the closed-form parameters of the stacks, the cases of the tests, their
 seeded inputs, the figures of the comparison and the gates.
@@ -16,8 +16,10 @@ from pathlib import Path
 
 import torch
 
-from fdisc_oracle import (  # noqa: F401 (used by the tests through here)
-    figure, integers, weight_norm, weight_norm_backward)
+import conv_oracle
+from conv_oracle import (  # noqa: F401 (used by the tests through here)
+    QUANTITIES, figure, hashed, integers, leaky, weight_norm,
+    weight_norm_backward, weight_norm_fp32_figures, weight_norm_inputs)
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -65,7 +67,6 @@ CASES = {
 # second tile, loaded while it computes the first
 EXTRA_CASES = {'walked': (32, 32, 9, 2, 2, 4097, .2)}
 ALL_CASES = {**CASES, **EXTRA_CASES}
-QUANTITIES = ('forward', 'gx', 'gW', 'gb')
 # The largest error of the reference's own arithmetic in fp32 (conv2d +
 # leaky_relu with autograd on the build host's CPU) against this oracle, per
 # case, relative to the RMS of the true quantity (fp32_figures; printed by
@@ -88,10 +89,7 @@ WEIGHT_NORM_GATES = tuple(4. * value for value in WEIGHT_NORM_RECORDED)
 
 
 def gate(quantity):
-    """4 x the largest recorded figure of the quantity over the table: the
-    project's margin for one more rounding order"""
-    index = QUANTITIES.index(quantity)
-    return 4. * max(figures[index] for figures in FP32_RECORDED.values())
+    return conv_oracle.gate(FP32_RECORDED, quantity)
 
 
 ###############################################################################
@@ -152,23 +150,13 @@ def wrong_weight(weight, defect):
     return weight
 
 
-def leaky(z, slope, defect=None):
-    if defect == 'slope_on_positive':
-        return torch.where(z > 0., z * slope, z)
-    return torch.where(z > 0., z, z * slope)
-
-
 def pre_activation(x, weight, bias, stride, defect=None):
     x, weight, bias = x.double(), weight.double(), bias.double()
     weight = wrong_weight(weight, defect)
     kernel_width = weight.shape[3]
-    source = padded_input(x, kernel_width, stride, defect)
-    z = None
-    for kh, kw, rows, columns in taps(
-            *x.shape[2:], kernel_width, stride, defect):
-        term = torch.einsum(
-            'oc,bchw->bohw', weight[:, :, kh, kw], source[:, :, rows, columns])
-        z = term if z is None else z + term
+    z = conv_oracle.conv_forward(
+        padded_input(x, kernel_width, stride, defect), weight,
+        taps(*x.shape[2:], kernel_width, stride, defect))
     return z + bias[None, :, None, None]
 
 
@@ -194,22 +182,18 @@ def layer_backward(x, weight, y, upstream, stride, slope, defect=None):
     weight = wrong_weight(weight, defect)
     kernel_width = weight.shape[3]
     source = padded_input(x, kernel_width, stride, defect)
-    spread = torch.zeros_like(source)
-    grad_weight = torch.zeros_like(weight)
     _, sw, ph, pw = geometry(kernel_width, stride, defect)
-    kept = gz
+    scatters = (lambda kh, kw: not kw % 2) \
+        if defect == 'gx_odd_taps_dropped' else None
+    kept = None
     if defect == 'gw_padded_columns_dropped':
         # the output columns whose window reaches the right padding
         inside = (torch.arange(gz.shape[3]) * sw + kernel_width - 1 - pw) < \
             x.shape[3]
         kept = gz * inside
-    for kh, kw, rows, columns in taps(
-            *x.shape[2:], kernel_width, stride, defect):
-        if not (defect == 'gx_odd_taps_dropped' and kw % 2):
-            spread[:, :, rows, columns] += torch.einsum(
-                'oc,bohw->bchw', weight[:, :, kh, kw], gz)
-        grad_weight[:, :, kh, kw] = torch.einsum(
-            'bohw,bchw->oc', kept, source[:, :, rows, columns])
+    spread, grad_weight = conv_oracle.conv_adjoint(
+        source, weight, gz,
+        taps(*x.shape[2:], kernel_width, stride, defect), scatters, kept)
     grad_weight = wrong_weight(grad_weight, defect)
     grad_x = spread[:, :, ph:ph + x.shape[2], pw:pw + x.shape[3]]
     return grad_x.contiguous(), grad_weight.contiguous(), gz.sum((0, 2, 3))
@@ -219,13 +203,6 @@ def layer_backward(x, weight, y, upstream, stride, slope, defect=None):
 # The parameters and the inputs of the stacks: closed forms of integer
 # indices, exact in fp32, the same on every machine (no RNG, no libm)
 ###############################################################################
-
-
-def hashed(count, salt):
-    """count multiples of 2^-12 in [0, 1): a multiplicative hash of the index"""
-    mixed = (torch.arange(count, dtype=torch.int64) + 7919 * (salt + 1)) \
-        * 2654435761 % 2 ** 32
-    return (mixed >> 20).double() / 4096.
 
 
 def shapes(name):
@@ -253,20 +230,8 @@ def parameters(name):
     """{key: fp32 tensor}: weight_v in [-.5, .5), bias in [-.125, .125),
     weight_g in [.5, 1.25): positive, and away from |v| (1.5, 4.9 and 8.5 at
     fan 27, 288 and 864), so that weight norm shows"""
-    out = {}
-    for salt, (key, shape) in enumerate(shapes(name).items()):
-        count = 1
-        for size in shape:
-            count *= size
-        value = hashed(count, salt + (1000 if name == 'r' else 0))
-        if key.endswith('weight_g'):
-            value = .75 * value + .5
-        elif key.endswith('bias'):
-            value = (value - .5) / 4.
-        else:
-            value = value - .5
-        out[key] = value.float().reshape(shape)
-    return out
+    return conv_oracle.hashed_parameters(
+        shapes(name), 1000 if name == 'r' else 0)
 
 
 STACK_INPUTS = {'cmb': (2, 1, 6, 513), 'r': (2, 1, 33, 21)}
@@ -285,16 +250,8 @@ def coefficients(name, shapes_of_maps):
     logits), in [-.5, .5) for the maps and in [0, 1) for the logits, whose
     bias gradient would otherwise be a cancelling sum (tests/fdisc_oracle.py,
     coefficients)"""
-    out = []
-    for index, shape in enumerate(shapes_of_maps):
-        count = 1
-        for size in shape:
-            count *= size
-        value = hashed(count, 7000 + index + (100 if name == 'r' else 0))
-        if index < len(shapes_of_maps) - 1:
-            value = value - .5
-        out.append(value.float().reshape(tuple(shape)))
-    return out
+    return conv_oracle.hashed_coefficients(
+        shapes_of_maps, 7000 + (100 if name == 'r' else 0))
 
 
 ###############################################################################
@@ -394,10 +351,8 @@ def golden_coefficients(golden, name):
     """The functional of the golden: the closed form, mended where the golden
     says"""
     kept = golden['stacks'][name]
-    out = coefficients(name, kept['map_shapes'])
-    for index, where, value in zip(*(c.tolist() for c in kept['mended'])):
-        out[index].view(-1)[where] = value
-    return out
+    return conv_oracle.golden_coefficients(
+        kept, coefficients(name, kept['map_shapes']))
 
 
 def stack_figures(golden, name, logits, maps, grad_x, gradients):
@@ -405,20 +360,8 @@ def stack_figures(golden, name, logits, maps, grad_x, gradients):
     the comparison of the GPU tests. `maps` without the logits; `gradients`
     {key: tensor}."""
     kept = golden['stacks'][name]
-    out = [('logits', 'forward', figure(logits, kept['logits']))]
-    wanted = kept['maps'].split(kept['map_counts'])
-    for index, (got, want) in enumerate(zip(maps, wanted)):
-        out.append((f'map{index}', 'forward', figure(
-            got.contiguous().flatten()[::golden['map_stride']], want)))
-    out.append(('gx', 'gx', figure(grad_x, kept['gradient_x'])))
-    keys = [key for key, _ in kept['gradient_counts']]
-    wanted = kept['gradients'].split(
-        [count for _, count in kept['gradient_counts']])
-    for key, want in zip(keys, wanted):
-        step = golden['gradient_stride'] if key.endswith('weight_v') else 1
-        out.append((key, 'gb' if key.endswith('bias') else 'gW',
-                    figure(gradients[key].flatten()[::step], want)))
-    return out
+    return conv_oracle.stack_figures(
+        golden, kept, logits, maps, grad_x, kept['gradient_x'], gradients)
 
 
 ###############################################################################
@@ -437,11 +380,10 @@ def inputs(name, seed=0):
     upstream = torch.randn(
         BATCH, out_channels, height, (width - 1) // stride + 1,
         generator=generator)
-    with torch.random.fork_rng(devices=[]):
-        torch.manual_seed(seed * 1000 + 500 + index)
-        conv = torch.nn.Conv2d(channels, out_channels, (3, kernel_width))
-    return (x, conv.weight.detach().clone(), conv.bias.detach().clone(),
-            upstream)
+    weight, bias = conv_oracle.conv_parameters(
+        torch.nn.Conv2d, seed * 1000 + 500 + index, channels, out_channels,
+        (3, kernel_width))
+    return x, weight, bias, upstream
 
 
 def reference_fp32(x, weight, bias, stride, slope, dtype=torch.float32,
@@ -462,65 +404,20 @@ def reference_fp32(x, weight, bias, stride, slope, dtype=torch.float32,
     return z.detach(), y.detach(), (x.grad, weight.grad, bias.grad)
 
 
-_TRUTH = {}
+# The truth of a case (the kink is that of a slope other than 1), the figures
+# of a result against it and those of the reference's own arithmetic in fp32
+_TRUTHS = conv_oracle.Truths(
+    inputs,
+    lambda name, x, weight, bias: pre_activation(
+        x, weight, bias, ALL_CASES[name][3]),
+    lambda name: ALL_CASES[name][6] != 1.,
+    lambda name, z: leaky(z, ALL_CASES[name][6]),
+    lambda name, x, weight, y, upstream: layer_backward(
+        x, weight, y, upstream, ALL_CASES[name][3], ALL_CASES[name][6]),
+    lambda name, x, weight, bias, dtype, upstream: reference_fp32(
+        x, weight, bias, ALL_CASES[name][3], ALL_CASES[name][6], dtype,
+        upstream))
+truth, figures = _TRUTHS.truth, _TRUTHS.figures
+fp32_figures = _TRUTHS.fp32_figures
 
 
-def truth(name):
-    """The case in float64, computed once and shared: the inputs (the upstream
-    gradient zero at the fragile elements), y, gx, gW, gb, the fragile mask.
-    An element is fragile where its pre-activation lies within 64 x the
-    largest fp32-vs-float64 error of the case around zero under a slope other
-    than 1: there the two sides of the mask cannot be told apart in fp32, so
-    it carries no upstream gradient."""
-    if name not in _TRUTH:
-        _, _, _, stride, _, _, slope = ALL_CASES[name]
-        x, weight, bias, upstream = inputs(name)
-        z = pre_activation(x, weight, bias, stride)
-        z32, _, _ = reference_fp32(x, weight, bias, stride, slope)
-        error = (z32.double() - z).abs().max()
-        fragile = (z.abs() < 64. * error) if slope != 1. \
-            else torch.zeros_like(z, dtype=torch.bool)
-        upstream = torch.where(fragile, torch.zeros_like(upstream), upstream)
-        y = leaky(z, slope)
-        gx, gw, gb = layer_backward(x, weight, y, upstream, stride, slope)
-        _TRUTH[name] = {
-            'x': x, 'weight': weight, 'bias': bias, 'upstream': upstream,
-            'z': z, 'forward': y, 'gx': gx, 'gW': gw, 'gb': gb,
-            'fragile': fragile}
-    return _TRUTH[name]
-
-
-def figures(name, forward, gx, gw, gb):
-    """The four figures of a result against the truth of the case"""
-    want = truth(name)
-    return tuple(figure(got, want[quantity]) for got, quantity in zip(
-        (forward, gx, gw, gb), QUANTITIES))
-
-
-def fp32_figures(name):
-    """The figures of the reference's own arithmetic in fp32 on this CPU"""
-    want = truth(name)
-    _, _, _, stride, _, _, slope = ALL_CASES[name]
-    _, y, gradients = reference_fp32(
-        want['x'], want['weight'], want['bias'], stride, slope,
-        upstream=want['upstream'])
-    return figures(name, y, *gradients)
-
-
-def weight_norm_inputs(shape):
-    generator = torch.Generator().manual_seed(shape[0] * 100 + shape[1])
-    g = torch.rand(shape[0], 1, 1, 1, generator=generator) + .5
-    v = torch.randn(shape, generator=generator)
-    upstream = torch.randn(shape, generator=generator)
-    return g, v, upstream
-
-
-def weight_norm_fp32_figures(shape):
-    g, v, upstream = weight_norm_inputs(shape)
-    leaf_g, leaf_v = g.clone().requires_grad_(True), \
-        v.clone().requires_grad_(True)
-    w = torch._weight_norm(leaf_v, leaf_g, 0)
-    w.backward(upstream)
-    want_g, want_v = weight_norm_backward(upstream, g, v)
-    return (figure(w.detach(), weight_norm(g, v)),
-            figure(leaf_g.grad, want_g), figure(leaf_v.grad, want_v))

@@ -17,6 +17,10 @@ from pathlib import Path
 
 import torch
 
+import conv_oracle
+from conv_oracle import (  # noqa: F401 (used by the tests through here)
+    QUANTITIES, activate, figure, integers, weight_norm, weight_norm_backward)
+
 ROOT = Path(__file__).resolve().parent.parent
 
 DEFECTS = (
@@ -54,7 +58,6 @@ CASES = {
     'large': (16, 16, 41, CONSTANTS['FD_GW_CHUNK'] // (BATCH * 41) + 3, 2,
               'relu'),
 }
-QUANTITIES = ('forward', 'gx', 'gW', 'gb')
 # The largest error of the reference's own arithmetic in fp32 (torch.cat +
 # conv2d + the activation, with autograd, on the build host's CPU) against
 # this oracle, per case, relative to the RMS of the true quantity
@@ -76,17 +79,7 @@ WEIGHT_NORM_GATES = tuple(4. * value for value in WEIGHT_NORM_RECORDED)
 
 
 def gate(quantity):
-    """4 x the largest recorded figure of the quantity over the table: the
-    project's margin for one more rounding order"""
-    index = QUANTITIES.index(quantity)
-    return 4. * max(figures[index] for figures in FP32_RECORDED.values())
-
-
-def figure(got, want):
-    """The largest error relative to the RMS of the true quantity"""
-    want = want.double()
-    return ((got.double() - want).abs().max() /
-            want.pow(2).mean().sqrt()).item()
+    return conv_oracle.gate(FP32_RECORDED, quantity)
 
 
 ###############################################################################
@@ -145,25 +138,13 @@ def taps(bins, frames, dilation, defect=None):
                    slice(kt * dt, kt * dt + out_frames))
 
 
-def activate(z, activation):
-    if activation == 'relu':
-        return z.clamp(min=0.)
-    if activation == 'sigmoid':
-        return 1. / (1. + torch.exp(-z))
-    assert activation == 'none'
-    return z
-
-
 def pre_activation(x, weight, bias, dilation, defect=None, table=None):
     x, weight, bias = x.double(), weight.double(), bias.double()
     if defect == 'taps_transposed':
         weight = weight.transpose(2, 3)
-    source = padded_input(x, dilation, defect, table)
-    z = None
-    for kf, kt, rows, columns in taps(*x.shape[2:], dilation, defect):
-        term = torch.einsum(
-            'oc,bcft->boft', weight[:, :, kf, kt], source[:, :, rows, columns])
-        z = term if z is None else z + term
+    z = conv_oracle.conv_forward(
+        padded_input(x, dilation, defect, table), weight,
+        taps(*x.shape[2:], dilation, defect))
     return z + bias[None, :, None, None]
 
 
@@ -195,13 +176,8 @@ def layer_backward(x, weight, y, upstream, dilation, activation, defect=None,
     else:
         gz = upstream
     source = padded_input(x, dilation, defect, table)
-    spread = torch.zeros_like(source)
-    grad_weight = torch.zeros_like(weight)
-    for kf, kt, rows, columns in taps(*x.shape[2:], dilation, defect):
-        spread[:, :, rows, columns] += torch.einsum(
-            'oc,boft->bcft', weight[:, :, kf, kt], gz)
-        grad_weight[:, :, kf, kt] = torch.einsum(
-            'boft,bcft->oc', gz, source[:, :, rows, columns])
+    spread, grad_weight = conv_oracle.conv_adjoint(
+        source, weight, gz, taps(*x.shape[2:], dilation, defect))
     if defect == 'taps_transposed':
         grad_weight = grad_weight.transpose(2, 3)
     if defect == 'embedding_weight_gradient_dropped':
@@ -212,41 +188,7 @@ def layer_backward(x, weight, y, upstream, dilation, activation, defect=None,
 
 
 ###############################################################################
-# Weight norm (torch._weight_norm, dim 0)
-###############################################################################
-
-
-def _norm(v, defect=None):
-    if defect == 'norm_whole_tensor':
-        return v.norm().expand(v.shape[0])
-    return v.flatten(1).norm(dim=1)
-
-
-def weight_norm(g, v, defect=None):
-    g, v = g.double(), v.double()
-    shape = (-1,) + (1,) * (v.ndim - 1)
-    return v * (g.reshape(-1) / _norm(v, defect)).reshape(shape)
-
-
-def weight_norm_backward(grad_w, g, v, defect=None):
-    """(g_g like g, g_v)"""
-    grad_w, gd, v = grad_w.double(), g.double().reshape(-1), v.double()
-    shape = (-1,) + (1,) * (v.ndim - 1)
-    norm = _norm(v, defect)
-    if defect == 'norm_whole_tensor':
-        dot = (grad_w * v).flatten(1).sum(1)
-        grad_g = dot / norm
-        grad_v = grad_w * (gd / norm).reshape(shape) - \
-            v * ((gd * dot).sum() / norm[0] ** 3)
-        return grad_g.reshape(g.shape), grad_v
-    dot = (grad_w * v).flatten(1).sum(1)
-    grad_v = (gd / norm).reshape(shape) * (
-        grad_w - v * (dot / norm ** 2).reshape(shape))
-    return (dot / norm).reshape(g.shape), grad_v
-
-
-###############################################################################
-# The stack
+# The stack (weight norm: tests/conv_oracle.py)
 ###############################################################################
 
 
@@ -305,15 +247,6 @@ def stack_backward(saved, parameters, upstreams, defect=None):
 ###############################################################################
 
 
-def conv_parameters(channels, out_channels, generator_seed):
-    """(weight, bias) of Conv2d's default initialisation, fp32, seeded without
-    touching the global generator"""
-    with torch.random.fork_rng(devices=[]):
-        torch.manual_seed(generator_seed)
-        conv = torch.nn.Conv2d(channels + 2, out_channels, 3)
-    return conv.weight.detach().clone(), conv.bias.detach().clone()
-
-
 def inputs(name, seed=0):
     """fp32: x Gaussian (16 channels) or 20 N(0, 1) - 40, decibel-like (one
     channel); weight and bias from Conv2d's default init; upstream Gaussian"""
@@ -325,8 +258,9 @@ def inputs(name, seed=0):
         x = 20. * x - 40.
     upstream = torch.randn(
         BATCH, out_channels, bins, frames, generator=generator)
-    weight, bias = conv_parameters(
-        channels, out_channels, seed * 1000 + 500 + list(CASES).index(name))
+    weight, bias = conv_oracle.conv_parameters(
+        torch.nn.Conv2d, seed * 1000 + 500 + list(CASES).index(name),
+        channels + 2, out_channels, 3)
     return x, weight, bias, upstream
 
 
@@ -354,52 +288,17 @@ def reference_fp32(x, weight, bias, dilation, activation, dtype=torch.float32,
     return z.detach(), y.detach(), (x.grad, weight.grad, bias.grad)
 
 
-_TRUTH = {}
-
-
-def truth(name):
-    """The case in float64, computed once and shared: the inputs (the
-    upstream gradient zero at the fragile elements), y, gx, gW, gb, the
-    fragile mask. An element is fragile where its pre-activation lies within
-    64 x the largest fp32-vs-float64 error of the case around zero under a
-    ReLU: there the two sides of the mask cannot be told apart in fp32, so it
-    carries no upstream gradient."""
-    if name not in _TRUTH:
-        _, _, _, _, dilation, activation = CASES[name]
-        x, weight, bias, upstream = inputs(name)
-        z = pre_activation(x, weight, bias, dilation)
-        z32, _, _ = reference_fp32(x, weight, bias, dilation, activation)
-        error = (z32.double() - z).abs().max()
-        fragile = (z.abs() < 64. * error) if activation == 'relu' \
-            else torch.zeros_like(z, dtype=torch.bool)
-        upstream = torch.where(fragile, torch.zeros_like(upstream), upstream)
-        y = activate(z, activation)
-        gx, gw, gb = layer_backward(
-            x, weight, y, upstream, dilation, activation)
-        _TRUTH[name] = {
-            'x': x, 'weight': weight, 'bias': bias, 'upstream': upstream,
-            'z': z, 'forward': y, 'gx': gx, 'gW': gw, 'gb': gb,
-            'fragile': fragile}
-    return _TRUTH[name]
-
-
-def figures(name, forward, gx, gw, gb):
-    """The four figures of a result against the truth of the case"""
-    want = truth(name)
-    return tuple(figure(got, want[quantity]) for got, quantity in zip(
-        (forward, gx, gw, gb), QUANTITIES))
-
-
-def fp32_figures(name):
-    """The figures of the reference's own arithmetic in fp32 on this CPU"""
-    want = truth(name)
-    _, _, _, _, dilation, activation = CASES[name]
-    _, y, gradients = reference_fp32(
-        want['x'], want['weight'], want['bias'], dilation, activation,
-        upstream=want['upstream'])
-    return figures(name, y, *gradients)
-
-
-def integers(shape, generator, low=-4, high=4):
-    return torch.randint(
-        low, high + 1, shape, generator=generator).to(torch.float32)
+# The truth of a case (the kink is the ReLU's), the figures of a result
+# against it and those of the reference's own arithmetic in fp32
+_TRUTHS = conv_oracle.Truths(
+    inputs,
+    lambda name, x, weight, bias: pre_activation(
+        x, weight, bias, CASES[name][4]),
+    lambda name: CASES[name][5] == 'relu',
+    lambda name, z: activate(z, CASES[name][5]),
+    lambda name, x, weight, y, upstream: layer_backward(
+        x, weight, y, upstream, *CASES[name][4:]),
+    lambda name, x, weight, bias, dtype, upstream: reference_fp32(
+        x, weight, bias, *CASES[name][4:], dtype, upstream))
+truth, figures = _TRUTHS.truth, _TRUTHS.figures
+fp32_figures = _TRUTHS.fp32_figures

@@ -5,10 +5,13 @@ discriminator's conv stacks (promonet/model/discriminator.py:320-389 at n_fft
 the embedding of FrequencyPositionalEmbedding on the layer's INPUT explicit,
 the zero padding explicit, the taps explicit loops (no conv2d), gz, gx, gW and
 gb written out by hand; the stack of six at any resolution and its gradients.
-Weight norm, `figure`, `integers` and the formula of `coefficients` are
-tests/fdisc_oracle.py's. `defect` plants one wrong reading of the layer
-(DEFECTS): the comparisons of the GPU tests must reject each of them
-(tests/test_cpu_fdisc_strided.py).
+The leaves (weight norm, `figure`, `hashed`, `integers`, the truth of a case)
+are tests/conv_oracle.py's; the formula of `coefficients` is
+tests/fdisc_oracle.py's. The loops over the taps stay here: they gather each
+tap's input by index (an embedding defect moves it per tap), gx is in gather
+form, an input row at a time, and its defects reach into that loop. `defect`
+plants one wrong reading of the layer (DEFECTS): the comparisons of the GPU
+tests must reject each of them (tests/test_cpu_fdisc_strided.py).
 
 Also the cases of the tests, their seeded inputs, the hashed parameters of the
 stacks, the figures of the comparison and the gates.
@@ -19,11 +22,12 @@ from pathlib import Path
 
 import torch
 
-import fdisc_oracle as base
+import conv_oracle
+from conv_oracle import (  # noqa: F401 (used by the tests through here)
+    QUANTITIES, activate, figure, hashed, integers, weight_norm,
+    weight_norm_backward)
 
 ROOT = Path(__file__).resolve().parent.parent
-figure, integers, weight_norm = base.figure, base.integers, base.weight_norm
-weight_norm_backward, activate = base.weight_norm_backward, base.activate
 
 DEFECTS = (
     'stride_on_time', 'half_bins', 'angle_from_output',
@@ -74,7 +78,6 @@ CASES = {
     'first-large': (1, 16, 34, EDGE // (BATCH * 17) + 1, 2, 'relu'),
     'last-large': (32, 1, 9, EDGE // (BATCH * 9) + 5, 1, 'sigmoid'),
 }
-QUANTITIES = base.QUANTITIES
 # The largest error of the reference's own arithmetic in fp32 (torch.cat +
 # conv2d + the activation, with autograd, on the build host's CPU) against
 # this oracle, per case, relative to the RMS of the true quantity
@@ -97,10 +100,7 @@ FP32_RECORDED = {
 
 
 def gate(quantity):
-    """4 x the largest recorded figure of the quantity over the table: the
-    project's margin for one more rounding order"""
-    index = QUANTITIES.index(quantity)
-    return 4. * max(figures[index] for figures in FP32_RECORDED.values())
+    return conv_oracle.gate(FP32_RECORDED, quantity)
 
 
 ###############################################################################
@@ -285,14 +285,6 @@ def plan(n_fft):
     return layers + [(1, channels, 1)]
 
 
-def hashed(count, salt):
-    """count multiples of 2^-12 in [0, 1): a multiplicative hash of the index
-    (tests/dconv_oracle.py)"""
-    mixed = (torch.arange(count, dtype=torch.int64) + 7919 * (salt + 1)) \
-        * 2654435761 % 2 ** 32
-    return (mixed >> 20).double() / 4096.
-
-
 def shapes(n_fft):
     """{key: shape} of the trained parameters, in the state_dict's order"""
     out = {}
@@ -307,17 +299,8 @@ def parameters(n_fft):
     """{key: fp32 tensor}, stored nowhere: weight_v in [-.5, .5), bias in
     [-.125, .125), weight_g in [.5, 1.25): positive, and away from |v|, so
     that weight norm shows"""
-    out = {}
-    for salt, (key, shape) in enumerate(shapes(n_fft).items()):
-        value = hashed(math.prod(shape), salt + 100 * int(math.log2(n_fft)))
-        if key.endswith('weight_g'):
-            value = .75 * value + .5
-        elif key.endswith('bias'):
-            value = (value - .5) / 4.
-        else:
-            value = value - .5
-        out[key] = value.float().reshape(shape)
-    return out
+    return conv_oracle.hashed_parameters(
+        shapes(n_fft), 100 * int(math.log2(n_fft)))
 
 
 STACK_FRAMES = 4
@@ -401,8 +384,9 @@ def inputs(name):
     upstream = torch.randn(
         BATCH, out_channels, out_bins(bins, stride), frames,
         generator=generator)
-    weight, bias = base.conv_parameters(
-        channels, out_channels, SEEDS.get(name, 0) * 1000 + 550 + index)
+    weight, bias = conv_oracle.conv_parameters(
+        torch.nn.Conv2d, SEEDS.get(name, 0) * 1000 + 550 + index,
+        channels + 2, out_channels, 3)
     return x, weight, bias, upstream
 
 
@@ -430,48 +414,20 @@ def reference_fp32(x, weight, bias, stride, activation, dtype=torch.float32,
     return z.detach(), y.detach(), (x.grad, weight.grad, bias.grad)
 
 
-_TRUTH = {}
-
-
-def truth(name):
-    """The case in float64, computed once and shared: the inputs (the
-    upstream gradient zero at the fragile elements), y, gx, gW, gb, the
-    fragile mask. An element is fragile where its pre-activation lies within
-    64 x the largest fp32-vs-float64 error of the case around zero under a
-    ReLU (tests/fdisc_oracle.py, truth)."""
-    if name not in _TRUTH:
-        _, _, _, _, stride, activation = CASES[name]
-        x, weight, bias, upstream = inputs(name)
-        z = pre_activation(x, weight, bias, stride)
-        z32, _, _ = reference_fp32(x, weight, bias, stride, activation)
-        error = (z32.double() - z).abs().max()
-        fragile = (z.abs() < 64. * error) if activation == 'relu' \
-            else torch.zeros_like(z, dtype=torch.bool)
-        upstream = torch.where(fragile, torch.zeros_like(upstream), upstream)
-        y = activate(z, activation)
-        gx, gw, gb = layer_backward(x, weight, y, upstream, stride, activation)
-        _TRUTH[name] = {
-            'x': x, 'weight': weight, 'bias': bias, 'upstream': upstream,
-            'z': z, 'forward': y, 'gx': gx, 'gW': gw, 'gb': gb,
-            'fragile': fragile}
-    return _TRUTH[name]
-
-
-def figures(name, forward, gx, gw, gb):
-    """The four figures of a result against the truth of the case"""
-    want = truth(name)
-    return tuple(figure(got, want[quantity]) for got, quantity in zip(
-        (forward, gx, gw, gb), QUANTITIES))
-
-
-def fp32_figures(name):
-    """The figures of the reference's own arithmetic in fp32 on this CPU"""
-    want = truth(name)
-    _, _, _, _, stride, activation = CASES[name]
-    _, y, gradients = reference_fp32(
-        want['x'], want['weight'], want['bias'], stride, activation,
-        upstream=want['upstream'])
-    return figures(name, y, *gradients)
+# The truth of a case (the kink is the ReLU's), the figures of a result
+# against it and those of the reference's own arithmetic in fp32
+_TRUTHS = conv_oracle.Truths(
+    inputs,
+    lambda name, x, weight, bias: pre_activation(
+        x, weight, bias, CASES[name][4]),
+    lambda name: CASES[name][5] == 'relu',
+    lambda name, z: activate(z, CASES[name][5]),
+    lambda name, x, weight, y, upstream: layer_backward(
+        x, weight, y, upstream, *CASES[name][4:]),
+    lambda name, x, weight, bias, dtype, upstream: reference_fp32(
+        x, weight, bias, *CASES[name][4:], dtype, upstream))
+truth, figures = _TRUTHS.truth, _TRUTHS.figures
+fp32_figures = _TRUTHS.fp32_figures
 
 
 def integer_case(name, which):

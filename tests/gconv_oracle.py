@@ -9,7 +9,7 @@ one wrong reading (LAYER_DEFECTS, MODULE_DEFECTS): the comparisons of the GPU
 tests must reject each of them (tests/test_cpu_gconv.py).
 
 Also the closed-form parameters of the modules (the multiplicative hash of
-tests/dconv_oracle.py), the cases of the tests, their seeded inputs, the
+tests/conv_oracle.py), the cases of the tests, their seeded inputs, the
 figures of the comparison and the gates.
 """
 import re
@@ -17,9 +17,10 @@ from pathlib import Path
 
 import torch
 
-from dconv_oracle import hashed
-from fdisc_oracle import (  # noqa: F401 (used by the tests through here)
-    figure, integers, weight_norm, weight_norm_backward)
+import conv_oracle
+from conv_oracle import (  # noqa: F401 (used by the tests through here)
+    QUANTITIES, figure, hashed, integers, leaky, weight_norm,
+    weight_norm_backward)
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -97,7 +98,6 @@ EXACT_CASES = ('form-32-3-1', 'form-64-7-3', 'form-128-11-5', 'form-256-3-5',
                'form-256-11-1', 'short-32-1', 'short-64-25', 'short-64-26',
                'large-32', 'large-128')
 EXACT_SLOPES = (.5, 1.)
-QUANTITIES = ('forward', 'gx', 'gW', 'gb')
 # The largest error of the reference's own arithmetic in fp32 (leaky_relu and
 # conv1d with autograd on the build host's CPU) against this oracle, per case,
 # the larger of the two slopes, relative to the RMS of the true quantity
@@ -157,19 +157,12 @@ DEVICE_RECORDED = (3.016e-06, 5.358e-06, 1.893e-06, 8.363e-07)
 
 
 def gate(quantity):
-    """4 x the largest recorded figure of the quantity over the table: the
-    project's margin for one more rounding order"""
-    index = QUANTITIES.index(quantity)
-    return 4. * max(figures_[index] for figures_ in FP32_RECORDED.values())
+    return conv_oracle.gate(FP32_RECORDED, quantity)
 
 
 ###############################################################################
 # The layer
 ###############################################################################
-
-
-def leaky(z, slope):
-    return torch.where(z > 0., z, z * slope)
 
 
 def padded(x, reach, defect=None):
@@ -282,13 +275,13 @@ def inputs(name, exact=False):
     x, upstream, residual = (
         torch.randn(shape, generator=generator) for _ in range(3))
     x.view(-1)[::7] = 0.
-    with torch.random.fork_rng(devices=[]):
-        torch.manual_seed(500 + index)
-        conv = torch.nn.Conv1d(channels, channels, kernel)
-    return (x, conv.weight.detach().clone(), conv.bias.detach().clone(),
-            upstream, residual)
+    weight, bias = conv_oracle.conv_parameters(
+        torch.nn.Conv1d, 500 + index, channels, channels, kernel)
+    return x, weight, bias, upstream, residual
 
 
+# (its own truth: no fragile mask, the kink is at the seeded input and not at
+# a computed pre-activation, and a case has two slopes and a residual)
 _TRUTH = {}
 
 
@@ -373,20 +366,7 @@ def residual_shapes(channels):
 def parameters(shapes, salt):
     """{key: fp32 tensor}: weight_v in [-.5, .5), bias in [-.125, .125),
     weight_g in [.5, 1.25)"""
-    out = {}
-    for index, (key, shape) in enumerate(shapes.items()):
-        count = 1
-        for size in shape:
-            count *= size
-        value = hashed(count, 3000 + 100 * salt + index)
-        if key.endswith('weight_g'):
-            value = .75 * value + .5
-        elif key.endswith('bias'):
-            value = (value - .5) / 4.
-        else:
-            value = value - .5
-        out[key] = value.float().reshape(shape)
-    return out
+    return conv_oracle.hashed_parameters(shapes, 3000 + 100 * salt)
 
 
 def module_inputs(name):

@@ -5,13 +5,13 @@ with the zero padding explicit and the taps an explicit loop (no conv2d), the
 fold of the audio (B, 1, T) into (B, 1, ceil(T / P), P) restated by index with
 its right reflect pad, the gradients gz, gx (into the audio: with the adjoint
 of the reflection), gW and gb written out by hand, and the DiscriminatorP
-stack with its gradients (weight norm: tests/fdisc_oracle.py). `defect`
-plants one wrong reading (DEFECTS, FOLD_DEFECTS, STACK_DEFECTS): the
-comparisons of the GPU tests must reject each of them
-(tests/test_cpu_pconv.py).
+stack with its gradients (the loop over the taps and weight norm:
+tests/conv_oracle.py). `defect` plants one wrong reading (DEFECTS,
+FOLD_DEFECTS, STACK_DEFECTS): the comparisons of the GPU tests must reject
+each of them (tests/test_cpu_pconv.py).
 
 Also the closed-form parameters of the stacks (the multiplicative hash of
-tests/dconv_oracle.py: one period has 8.3 M of them, stored nowhere), the
+tests/conv_oracle.py: one period has 8.3 M of them, stored nowhere), the
 cases of the tests, their seeded inputs, the figures of the comparison and the
 gates.
 """
@@ -20,9 +20,10 @@ from pathlib import Path
 
 import torch
 
-from dconv_oracle import hashed
-from fdisc_oracle import (  # noqa: F401 (used by the tests through here)
-    figure, integers, weight_norm, weight_norm_backward)
+import conv_oracle
+from conv_oracle import (  # noqa: F401 (used by the tests through here)
+    QUANTITIES, figure, hashed, integers, leaky, weight_norm,
+    weight_norm_backward, weight_norm_fp32_figures, weight_norm_inputs)
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -100,7 +101,6 @@ FOLD_CASES = {
     'audio-five': (98, 5, .1),
 }
 ALL_CASES = {**CASES, **FOLD_CASES}
-QUANTITIES = ('forward', 'gx', 'gW', 'gb')
 # The largest error of the reference's own arithmetic in fp32 (pad(reflect),
 # view, conv2d and leaky_relu with autograd on the build host's CPU) against
 # this oracle, per case, relative to the RMS of the true quantity
@@ -172,10 +172,7 @@ WEIGHT_NORM_GATES = tuple(4. * value for value in WEIGHT_NORM_RECORDED)
 
 
 def gate(quantity):
-    """4 x the largest recorded figure of the quantity over the table: the
-    project's margin for one more rounding order"""
-    index = QUANTITIES.index(quantity)
-    return 4. * max(figures[index] for figures in FP32_RECORDED.values())
+    return conv_oracle.gate(FP32_RECORDED, quantity)
 
 
 ###############################################################################
@@ -279,11 +276,11 @@ def padded_input(x, kernel, stride, defect=None):
 
 
 def taps(height, period, kernel, stride, defect=None):
-    """(tap, rows, columns) of the padded input that each tap reads"""
+    """(kh, 0, rows, columns) of the padded input that each tap reads"""
     sh, sw, _ = geometry(kernel, stride, defect)
     out_height, out_width = out_shape(height, period, kernel, stride, defect)
     for tap in range(kernel):
-        yield (tap, slice(tap, tap + (out_height - 1) * sh + 1, sh),
+        yield (tap, 0, slice(tap, tap + (out_height - 1) * sh + 1, sh),
                slice(0, (out_width - 1) * sw + 1, sw))
 
 
@@ -291,12 +288,6 @@ def wrong_weight(weight, defect):
     if defect == 'taps_flipped':
         return weight.flip(2)
     return weight
-
-
-def leaky(z, slope, defect=None):
-    if defect == 'slope_on_positive':
-        return torch.where(z > 0., z * slope, z)
-    return torch.where(z > 0., z, z * slope)
 
 
 def neighbour_columns(x, kernel, stride):
@@ -325,12 +316,9 @@ def pre_activation(x, weight, bias, stride, defect=None):
             'ock,bckhw->bohw', weight[..., 0], neighbour_columns(
                 x, kernel, stride))
         return z + bias[None, :, None, None]
-    source = padded_input(x, kernel, stride, defect)
-    z = None
-    for tap, rows, columns in taps(*x.shape[2:], kernel, stride, defect):
-        term = torch.einsum(
-            'oc,bchw->bohw', weight[:, :, tap, 0], source[:, :, rows, columns])
-        z = term if z is None else z + term
+    z = conv_oracle.conv_forward(
+        padded_input(x, kernel, stride, defect), weight,
+        taps(*x.shape[2:], kernel, stride, defect))
     return z + bias[None, :, None, None]
 
 
@@ -356,23 +344,19 @@ def layer_backward(x, weight, y, upstream, stride, slope, defect=None):
     weight = wrong_weight(weight, defect)
     kernel = weight.shape[2]
     source = padded_input(x, kernel, stride, defect)
-    spread = torch.zeros_like(source)
-    grad_weight = torch.zeros_like(weight)
     sh, _, pad = geometry(kernel, stride, defect)
-    kept = gz
+    # at stride 3 the residue classes 1 and 2 take two taps each, t and t + 3
+    scatters = (lambda kh, kw: kh < stride) \
+        if defect == 'gx_second_tap_dropped' else None
+    kept = None
     if defect == 'gw_bottom_rows_dropped':
         # the output rows whose window reaches the bottom padding
         inside = (torch.arange(gz.shape[2]) * sh + kernel - 1 - pad) < \
             x.shape[2]
         kept = gz * inside[:, None]
-    for tap, rows, columns in taps(*x.shape[2:], kernel, stride, defect):
-        # at stride 3 the residue classes 1 and 2 take two taps each, t and
-        # t + 3
-        if not (defect == 'gx_second_tap_dropped' and tap >= stride):
-            spread[:, :, rows, columns] += torch.einsum(
-                'oc,bohw->bchw', weight[:, :, tap, 0], gz)
-        grad_weight[:, :, tap, 0] = torch.einsum(
-            'bohw,bchw->oc', kept, source[:, :, rows, columns])
+    spread, grad_weight = conv_oracle.conv_adjoint(
+        source, weight, gz, taps(*x.shape[2:], kernel, stride, defect),
+        scatters, kept)
     grad_weight = wrong_weight(grad_weight, defect)
     grad_x = spread[:, :, pad:pad + x.shape[2]]
     return grad_x.contiguous(), grad_weight.contiguous(), gz.sum((0, 2, 3))
@@ -401,20 +385,7 @@ def shapes():
 def parameters(period):
     """{key: fp32 tensor}: weight_v in [-.5, .5), bias in [-.125, .125),
     weight_g in [.5, 1.25)"""
-    out = {}
-    for salt, (key, shape) in enumerate(shapes().items()):
-        count = 1
-        for size in shape:
-            count *= size
-        value = hashed(count, salt + 2000 + 30 * period)
-        if key.endswith('weight_g'):
-            value = .75 * value + .5
-        elif key.endswith('bias'):
-            value = (value - .5) / 4.
-        else:
-            value = value - .5
-        out[key] = value.float().reshape(shape)
-    return out
+    return conv_oracle.hashed_parameters(shapes(), 2000 + 30 * period)
 
 
 def stack_audio():
@@ -428,16 +399,7 @@ def coefficients(period, shapes_of_maps):
     logits), in [-.5, .5) for the maps and in [0, 1) for the logits, whose
     bias gradient would otherwise be a cancelling sum (tests/fdisc_oracle.py,
     coefficients)"""
-    out = []
-    for index, shape in enumerate(shapes_of_maps):
-        count = 1
-        for size in shape:
-            count *= size
-        value = hashed(count, 9000 + index + 10 * period)
-        if index < len(shapes_of_maps) - 1:
-            value = value - .5
-        out.append(value.float().reshape(tuple(shape)))
-    return out
+    return conv_oracle.hashed_coefficients(shapes_of_maps, 9000 + 10 * period)
 
 
 ###############################################################################
@@ -514,10 +476,8 @@ def golden_coefficients(golden, period):
     """The functional of the golden: the closed form, mended where the golden
     says"""
     kept = golden['stacks'][period]
-    out = coefficients(period, kept['map_shapes'])
-    for index, where, value in zip(*(c.tolist() for c in kept['mended'])):
-        out[index].view(-1)[where] = value
-    return out
+    return conv_oracle.golden_coefficients(
+        kept, coefficients(period, kept['map_shapes']))
 
 
 def stack_figures(golden, period, logits, maps, grad_audio, gradients):
@@ -525,20 +485,9 @@ def stack_figures(golden, period, logits, maps, grad_audio, gradients):
     the comparison of the GPU tests. `maps` without the logits; `gradients`
     {key: tensor}."""
     kept = golden['stacks'][period]
-    out = [('logits', 'forward', figure(logits, kept['logits']))]
-    wanted = kept['maps'].split(kept['map_counts'])
-    for index, (got, want) in enumerate(zip(maps, wanted)):
-        out.append((f'map{index}', 'forward', figure(
-            got.contiguous().flatten()[::golden['map_stride']], want)))
-    out.append(('gx', 'gx', figure(grad_audio, kept['gradient_audio'])))
-    keys = [key for key, _ in kept['gradient_counts']]
-    wanted = kept['gradients'].split(
-        [count for _, count in kept['gradient_counts']])
-    for key, want in zip(keys, wanted):
-        step = golden['gradient_stride'] if key.endswith('weight_v') else 1
-        out.append((key, 'gb' if key.endswith('bias') else 'gW',
-                    figure(gradients[key].flatten()[::step], want)))
-    return out
+    return conv_oracle.stack_figures(
+        golden, kept, logits, maps, grad_audio, kept['gradient_audio'],
+        gradients)
 
 
 ###############################################################################
@@ -577,11 +526,10 @@ def inputs(name, seed=0):
             BATCH, channels, CASES[name][4], period, generator=generator)
     upstream = torch.randn(
         BATCH, out_channels, out_height_of(name), period, generator=generator)
-    with torch.random.fork_rng(devices=[]):
-        torch.manual_seed(seed * 1000 + 500 + index)
-        conv = torch.nn.Conv2d(channels, out_channels, (kernel, 1))
-    return (x, conv.weight.detach().clone(), conv.bias.detach().clone(),
-            upstream)
+    weight, bias = conv_oracle.conv_parameters(
+        torch.nn.Conv2d, seed * 1000 + 500 + index, channels, out_channels,
+        (kernel, 1))
+    return x, weight, bias, upstream
 
 
 def reference_fold(audio, period):
@@ -641,66 +589,17 @@ def case_backward(name, x, weight, y, upstream, defect=None):
     return layer_backward(x, weight, y, upstream, stride, slope, defect)
 
 
-_TRUTH = {}
+# The truth of a case (the kink is that of a slope other than 1), the figures
+# of a result against it and those of the reference's own arithmetic in fp32
+_TRUTHS = conv_oracle.Truths(
+    inputs,
+    lambda name, x, weight, bias: pre_activation(
+        fold(x.double(), FOLD_CASES[name][1]) if name in FOLD_CASES else x,
+        weight, bias, form_of(name)[3]),
+    lambda name: form_of(name)[4] != 1.,
+    lambda name, z: leaky(z, form_of(name)[4]),
+    case_backward, reference_fp32)
+truth, figures = _TRUTHS.truth, _TRUTHS.figures
+fp32_figures = _TRUTHS.fp32_figures
 
 
-def truth(name):
-    """The case in float64, computed once and shared: the inputs (the upstream
-    gradient zero at the fragile elements), y, gx, gW, gb, the fragile mask.
-    An element is fragile where its pre-activation lies within 64 x the
-    largest fp32-vs-float64 error of the case around zero under a slope other
-    than 1: there the two sides of the mask cannot be told apart in fp32, so
-    it carries no upstream gradient."""
-    if name not in _TRUTH:
-        _, _, _, stride, slope = form_of(name)
-        x, weight, bias, upstream = inputs(name)
-        folded = fold(x.double(), FOLD_CASES[name][1]) \
-            if name in FOLD_CASES else x
-        z = pre_activation(folded, weight, bias, stride)
-        z32, _, _ = reference_fp32(name, x, weight, bias)
-        error = (z32.double() - z).abs().max()
-        fragile = (z.abs() < 64. * error) if slope != 1. \
-            else torch.zeros_like(z, dtype=torch.bool)
-        upstream = torch.where(fragile, torch.zeros_like(upstream), upstream)
-        y = leaky(z, slope)
-        gx, gw, gb = case_backward(name, x, weight, y, upstream)
-        _TRUTH[name] = {
-            'x': x, 'weight': weight, 'bias': bias, 'upstream': upstream,
-            'z': z, 'forward': y, 'gx': gx, 'gW': gw, 'gb': gb,
-            'fragile': fragile}
-    return _TRUTH[name]
-
-
-def figures(name, forward, gx, gw, gb):
-    """The four figures of a result against the truth of the case"""
-    want = truth(name)
-    return tuple(figure(got, want[quantity]) for got, quantity in zip(
-        (forward, gx, gw, gb), QUANTITIES))
-
-
-def fp32_figures(name):
-    """The figures of the reference's own arithmetic in fp32 on this CPU"""
-    want = truth(name)
-    _, y, gradients = reference_fp32(
-        name, want['x'], want['weight'], want['bias'],
-        upstream=want['upstream'])
-    return figures(name, y, *gradients)
-
-
-def weight_norm_inputs(shape):
-    generator = torch.Generator().manual_seed(shape[0] * 100 + shape[1])
-    g = torch.rand(shape[0], 1, 1, 1, generator=generator) + .5
-    v = torch.randn(shape, generator=generator)
-    upstream = torch.randn(shape, generator=generator)
-    return g, v, upstream
-
-
-def weight_norm_fp32_figures(shape):
-    g, v, upstream = weight_norm_inputs(shape)
-    leaf_g, leaf_v = g.clone().requires_grad_(True), \
-        v.clone().requires_grad_(True)
-    w = torch._weight_norm(leaf_v, leaf_g, 0)
-    w.backward(upstream)
-    want_g, want_v = weight_norm_backward(upstream, g, v)
-    return (figure(w.detach(), weight_norm(g, v)),
-            figure(leaf_g.grad, want_g), figure(leaf_v.grad, want_v))

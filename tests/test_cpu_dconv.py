@@ -16,7 +16,9 @@ import promonet_amd
 from promonet_amd import _lib
 from promonet_amd.model import discriminator
 
+import conv_checks
 import dconv_oracle as oracle
+from conv_checks import close
 
 ROOT = Path(__file__).resolve().parent.parent
 NAMES = list(oracle.CASES)
@@ -27,10 +29,6 @@ STACKS = ('cmb', 'r')
 @pytest.fixture(scope='module')
 def golden():
     return torch.load(ROOT / 'tests' / 'golden' / 'dconv.pt')
-
-
-def close(got, want):
-    return (got - want).abs().max() <= 1e-12 * want.abs().max()
 
 
 ###############################################################################
@@ -145,11 +143,7 @@ def test_the_module_has_the_reference_s_keys_and_shapes(golden, name):
 
 @pytest.mark.parametrize('name', ALL_NAMES)
 def test_the_fragile_share_is_small(name):
-    want = oracle.truth(name)
-    share = want['fragile'].double().mean().item()
-    print(f'{name}: fragile share {share:.1e}')
-    assert share <= 1e-3, share
-    assert not want['upstream'][want['fragile']].any()
+    conv_checks.the_fragile_share_is_small(oracle, name)
 
 
 def test_the_walked_case_has_more_tiles_than_compute_units():
@@ -183,23 +177,13 @@ def test_the_large_case_reaches_past_one_workgroup_and_one_partial():
 
 @pytest.mark.parametrize('name', NAMES)
 def test_the_gates_come_from_the_reference_arithmetic_in_fp32(name):
-    """4 x the largest recorded figure of the quantity over the table; the
-    fp32 torch arithmetic itself, run here, stays inside the gates"""
-    figures = oracle.fp32_figures(name)
-    print(f'{name}: fp32 torch ' + ' '.join(f'{v:.3e}' for v in figures) +
-          f' (recorded {oracle.FP32_RECORDED[name]})')
-    for index, quantity in enumerate(oracle.QUANTITIES):
-        assert figures[index] < oracle.gate(quantity)
-        assert oracle.gate(quantity) == 4. * max(
-            recorded[index] for recorded in oracle.FP32_RECORDED.values())
+    conv_checks.the_gates_come_from_the_reference_arithmetic_in_fp32(
+        oracle, name)
 
 
 @pytest.mark.parametrize('shape', oracle.WEIGHT_NORM_SHAPES)
 def test_the_weight_norm_gates_come_from_torch_in_fp32(shape):
-    figures = oracle.weight_norm_fp32_figures(shape)
-    print(f'{shape}: fp32 torch ' + ' '.join(f'{v:.3e}' for v in figures))
-    for value, limit in zip(figures, oracle.WEIGHT_NORM_GATES):
-        assert value < limit
+    conv_checks.the_weight_norm_gates_come_from_torch_in_fp32(oracle, shape)
 
 
 ###############################################################################
@@ -226,15 +210,10 @@ APPLIES = {
 def accepted(name, defect):
     """Would the GPU tests pass an implementation with this defect?"""
     _, _, _, stride, _, _, slope = oracle.CASES[name]
-    want = oracle.truth(name)
-    y = oracle.layer(
-        want['x'], want['weight'], want['bias'], stride, slope, defect)
-    if y.shape != want['forward'].shape:
-        return False
-    gradients = oracle.layer_backward(
-        want['x'], want['weight'], y, want['upstream'], stride, slope, defect)
-    return all(value < oracle.gate(quantity) for quantity, value in zip(
-        oracle.QUANTITIES, oracle.figures(name, y, *gradients)))
+    return conv_checks.accepted(
+        oracle, name,
+        lambda *inputs: oracle.layer(*inputs, stride, slope, defect),
+        lambda *inputs: oracle.layer_backward(*inputs, stride, slope, defect))
 
 
 def test_the_defects_are_all_listed():

@@ -14,7 +14,9 @@ import promonet_amd
 from promonet_amd import _lib
 from promonet_amd.model import discriminator
 
+import conv_checks
 import fdisc_oracle as oracle
+from conv_checks import close
 
 ROOT = Path(__file__).resolve().parent.parent
 NAMES = list(oracle.CASES)
@@ -24,10 +26,6 @@ NORM_SHAPES = [(16, 18, 3, 3), (16, 3, 3, 3), (1, 18, 3, 3)]
 @pytest.fixture(scope='module')
 def golden():
     return torch.load(ROOT / 'tests' / 'golden' / 'fdisc.pt')
-
-
-def close(got, want):
-    return (got - want).abs().max() <= 1e-12 * want.abs().max()
 
 
 ###############################################################################
@@ -149,11 +147,7 @@ def test_the_module_refuses_the_strided_resolutions(golden, n_fft):
 
 @pytest.mark.parametrize('name', NAMES)
 def test_the_fragile_share_is_small(name):
-    want = oracle.truth(name)
-    share = want['fragile'].double().mean().item()
-    print(f'{name}: fragile share {share:.1e}')
-    assert share <= 1e-3, share
-    assert not want['upstream'][want['fragile']].any()
+    conv_checks.the_fragile_share_is_small(oracle, name)
 
 
 def test_the_large_case_reaches_past_one_workgroup_and_one_partial():
@@ -177,15 +171,8 @@ def test_the_large_case_reaches_past_one_workgroup_and_one_partial():
 
 @pytest.mark.parametrize('name', NAMES)
 def test_the_gates_come_from_the_reference_arithmetic_in_fp32(name):
-    """4 x the largest recorded figure of the quantity over the table; the
-    fp32 torch arithmetic itself, run here, stays inside the gates"""
-    figures = oracle.fp32_figures(name)
-    print(f'{name}: fp32 torch ' + ' '.join(f'{v:.3e}' for v in figures) +
-          f' (recorded {oracle.FP32_RECORDED[name]})')
-    for index, quantity in enumerate(oracle.QUANTITIES):
-        assert figures[index] < oracle.gate(quantity)
-        assert oracle.gate(quantity) == 4. * max(
-            recorded[index] for recorded in oracle.FP32_RECORDED.values())
+    conv_checks.the_gates_come_from_the_reference_arithmetic_in_fp32(
+        oracle, name)
 
 
 ###############################################################################
@@ -211,17 +198,10 @@ APPLIES = {
 
 def accepted(name, defect):
     """Would the GPU tests pass an implementation with this defect?"""
-    _, _, _, _, dilation, activation = oracle.CASES[name]
-    want = oracle.truth(name)
-    y = oracle.layer(
-        want['x'], want['weight'], want['bias'], dilation, activation, defect)
-    if y.shape != want['forward'].shape:
-        return False
-    gradients = oracle.layer_backward(
-        want['x'], want['weight'], y, want['upstream'], dilation, activation,
-        defect)
-    return all(value < oracle.gate(quantity) for quantity, value in zip(
-        oracle.QUANTITIES, oracle.figures(name, y, *gradients)))
+    form = oracle.CASES[name][4:]
+    return conv_checks.accepted(
+        oracle, name, lambda *inputs: oracle.layer(*inputs, *form, defect),
+        lambda *inputs: oracle.layer_backward(*inputs, *form, defect))
 
 
 def test_the_defects_are_all_listed():

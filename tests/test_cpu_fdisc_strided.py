@@ -14,7 +14,9 @@ import torch
 from promonet_amd import _lib
 from promonet_amd.model import discriminator
 
+import conv_checks
 import fdisc_strided_oracle as oracle
+from conv_checks import close
 
 ROOT = Path(__file__).resolve().parent.parent
 NAMES = list(oracle.CASES)
@@ -30,10 +32,6 @@ def golden():
 def recorded():
     """The reference's keys and shapes at all six sizes"""
     return torch.load(ROOT / 'tests' / 'golden' / 'fdisc.pt')
-
-
-def close(got, want):
-    return (got - want).abs().max() <= 1e-12 * want.abs().max()
 
 
 ###############################################################################
@@ -116,24 +114,13 @@ def test_the_plan_of_the_oracle_is_the_module_s():
 
 @pytest.mark.parametrize('name', NAMES)
 def test_the_fragile_share_is_small(name):
-    want = oracle.truth(name)
-    share = want['fragile'].double().mean().item()
-    print(f'{name}: fragile share {share:.1e}')
-    assert share <= 1e-3, share
-    assert not want['upstream'][want['fragile']].any()
+    conv_checks.the_fragile_share_is_small(oracle, name)
 
 
 @pytest.mark.parametrize('name', NAMES)
 def test_the_gates_come_from_the_reference_arithmetic_in_fp32(name):
-    """4 x the largest recorded figure of the quantity over the table; the
-    fp32 torch arithmetic itself, run here, stays inside the gates"""
-    figures = oracle.fp32_figures(name)
-    print(f'{name}: fp32 torch ' + ' '.join(f'{v:.3e}' for v in figures) +
-          f' (recorded {oracle.FP32_RECORDED[name]})')
-    for index, quantity in enumerate(oracle.QUANTITIES):
-        assert figures[index] < oracle.gate(quantity)
-        assert oracle.gate(quantity) == 4. * max(
-            recorded[index] for recorded in oracle.FP32_RECORDED.values())
+    conv_checks.the_gates_come_from_the_reference_arithmetic_in_fp32(
+        oracle, name)
 
 
 def test_the_cases_reach_what_they_name():
@@ -221,17 +208,10 @@ EXACT = {defect: names for defect, names in APPLIES.items()
 def accepted(name, defect):
     """Would test_gpu_fdisc_strided.py pass an implementation with this
     defect?"""
-    _, _, _, _, stride, activation = oracle.CASES[name]
-    want = oracle.truth(name)
-    y = oracle.layer(
-        want['x'], want['weight'], want['bias'], stride, activation, defect)
-    if y.shape != want['forward'].shape:
-        return False
-    gradients = oracle.layer_backward(
-        want['x'], want['weight'], y, want['upstream'], stride, activation,
-        defect)
-    return all(value < oracle.gate(quantity) for quantity, value in zip(
-        oracle.QUANTITIES, oracle.figures(name, y, *gradients)))
+    form = oracle.CASES[name][4:]
+    return conv_checks.accepted(
+        oracle, name, lambda *inputs: oracle.layer(*inputs, *form, defect),
+        lambda *inputs: oracle.layer_backward(*inputs, *form, defect))
 
 
 def accepted_exactly(name, defect):

@@ -15,6 +15,7 @@ from promonet_amd import _lib
 from promonet_amd.model import hifigan_train
 
 import gconv_oracle as oracle
+from conv_checks import close
 
 ROOT = Path(__file__).resolve().parent.parent
 NAMES = list(oracle.CASES)
@@ -23,10 +24,6 @@ NAMES = list(oracle.CASES)
 @pytest.fixture(scope='module')
 def golden():
     return torch.load(ROOT / 'tests' / 'golden' / 'gconv.pt')
-
-
-def close(got, want):
-    return (got - want).abs().max() <= 1e-12 * want.abs().max()
 
 
 ###############################################################################

@@ -15,7 +15,9 @@ import promonet_amd
 from promonet_amd import _lib
 from promonet_amd.model import discriminator
 
+import conv_checks
 import pconv_oracle as oracle
+from conv_checks import close
 
 ROOT = Path(__file__).resolve().parent.parent
 NAMES = list(oracle.ALL_CASES)
@@ -24,10 +26,6 @@ NAMES = list(oracle.ALL_CASES)
 @pytest.fixture(scope='module')
 def golden():
     return torch.load(ROOT / 'tests' / 'golden' / 'pconv.pt')
-
-
-def close(got, want):
-    return (got - want).abs().max() <= 1e-12 * want.abs().max()
 
 
 ###############################################################################
@@ -238,33 +236,19 @@ def test_the_aggregate_has_the_default_configuration_s_keys_and_shapes(
 
 @pytest.mark.parametrize('name', NAMES)
 def test_the_fragile_share_is_small(name):
-    want = oracle.truth(name)
-    share = want['fragile'].double().mean().item()
-    print(f'{name}: fragile share {share:.1e}')
-    assert share <= 1e-3, share
-    assert not want['upstream'][want['fragile']].any()
+    conv_checks.the_fragile_share_is_small(oracle, name)
 
 
 @pytest.mark.parametrize('name', NAMES)
 def test_the_gates_come_from_the_reference_arithmetic_in_fp32(name):
-    """4 x the largest recorded figure of the quantity over the table; the
-    fp32 torch arithmetic itself, run here, stays inside the gates"""
-    figures = oracle.fp32_figures(name)
-    print(f'{name}: fp32 torch ' + ' '.join(f'{v:.3e}' for v in figures) +
-          f' (recorded {oracle.FP32_RECORDED[name]})')
     assert set(oracle.FP32_RECORDED) == set(oracle.ALL_CASES)
-    for index, quantity in enumerate(oracle.QUANTITIES):
-        assert figures[index] < oracle.gate(quantity)
-        assert oracle.gate(quantity) == 4. * max(
-            recorded[index] for recorded in oracle.FP32_RECORDED.values())
+    conv_checks.the_gates_come_from_the_reference_arithmetic_in_fp32(
+        oracle, name)
 
 
 @pytest.mark.parametrize('shape', oracle.WEIGHT_NORM_SHAPES)
 def test_the_weight_norm_gates_come_from_torch_in_fp32(shape):
-    figures = oracle.weight_norm_fp32_figures(shape)
-    print(f'{shape}: fp32 torch ' + ' '.join(f'{v:.3e}' for v in figures))
-    for value, limit in zip(figures, oracle.WEIGHT_NORM_GATES):
-        assert value < limit
+    conv_checks.the_weight_norm_gates_come_from_torch_in_fp32(oracle, shape)
     assert sorted(math.prod(s[1:]) for s in oracle.WEIGHT_NORM_SHAPES) == \
         [5, 160, 640, 2560, 3072, 5120]
 
@@ -310,15 +294,9 @@ APPLIES = {
 
 def accepted(name, defect):
     """Would the GPU tests pass an implementation with this defect?"""
-    want = oracle.truth(name)
-    y = oracle.case_layer(
-        name, want['x'], want['weight'], want['bias'], defect)
-    if y.shape != want['forward'].shape:
-        return False
-    gradients = oracle.case_backward(
-        name, want['x'], want['weight'], y, want['upstream'], defect)
-    return all(value < oracle.gate(quantity) for quantity, value in zip(
-        oracle.QUANTITIES, oracle.figures(name, y, *gradients)))
+    return conv_checks.accepted(
+        oracle, name, lambda *inputs: oracle.case_layer(name, *inputs, defect),
+        lambda *inputs: oracle.case_backward(name, *inputs, defect))
 
 
 def test_the_defects_are_all_listed():

@@ -19,6 +19,7 @@ import torch
 import promonet_amd
 from promonet_amd.model import discriminator, hifigan_train
 
+import conv_checks
 import gconv_oracle as oracle
 
 NAMES = list(oracle.CASES)
@@ -26,31 +27,25 @@ LARGE = ['form-32-11-5', 'form-256-11-5', 'short-64-26', 'large-32',
          'large-128']
 pytestmark = pytest.mark.gpu
 
-_RESULTS = {}
-
 
 def layer(name, x, weight, bias, slope, residual=None):
     return hifigan_train.block_conv(
         x, weight, bias, oracle.CASES[name][2], slope, residual)
 
 
-def forward_backward(device, name, slope, residual=False, rows=slice(None)):
-    """(y, gx, gW, gb) of the case on the device, on the CPU"""
-    want = oracle.truth(name, slope)
-    x = want['x'][rows].to(device).requires_grad_(True)
-    weight = want['weight'].to(device).requires_grad_(True)
-    bias = want['bias'].to(device).requires_grad_(True)
-    y = layer(name, x, weight, bias, slope,
-              want['residual'][rows].to(device) if residual else None)
-    y.backward(want['upstream'][rows].to(device))
-    return tuple(t.detach().cpu() for t in (y, x.grad, weight.grad, bias.grad))
+def case_layer(case, x, weight, bias, rows):
+    name, slope, residual = case
+    return layer(name, x, weight, bias, slope, oracle.truth(name, slope)[
+        'residual'][rows].to(x.device) if residual else None)
 
 
-def result(device, name, slope, residual=False):
-    key = (name, slope, residual)
-    if key not in _RESULTS:
-        _RESULTS[key] = forward_backward(device, name, slope, residual)
-    return _RESULTS[key]
+# a case of the shared bodies: (name, slope, with the residual)
+FAMILY = conv_checks.Family(
+    oracle, case_layer, truth=lambda case: oracle.truth(*case[:2]),
+    figures=lambda case, *got: oracle.figures(
+        *case[:2], *got, residual=case[2]),
+    recorded=lambda case: oracle.FP32_RECORDED[case[0]],
+    label=lambda case: f'{case[0]} slope {case[1]} residual {case[2]}')
 
 
 ###############################################################################
@@ -62,17 +57,8 @@ def result(device, name, slope, residual=False):
 def test_a_layer_is_within_the_gate(device, name):
     for slope in oracle.SLOPES:
         for residual in (False, True):
-            want = oracle.truth(name, slope)
-            got = result(device, name, slope, residual)
-            assert got[0].shape == want['forward'].shape
-            assert got[1].shape == want['x'].shape
-            figures = oracle.figures(name, slope, *got, residual=residual)
-            print(f'{name} slope {slope} residual {residual}: device ' +
-                  ' '.join(f'{v:.3e}' for v in figures) +
-                  ' fp32 CPU recorded ' +
-                  ' '.join(f'{v:.3e}' for v in oracle.FP32_RECORDED[name]))
-            for quantity, value in zip(oracle.QUANTITIES, figures):
-                assert value < oracle.gate(quantity), (quantity, value)
+            conv_checks.a_layer_is_within_the_gate(
+                FAMILY, device, (name, slope, residual))
 
 
 def test_the_output_is_a_view_of_channels_last_memory(device):
@@ -199,18 +185,14 @@ def test_the_state_dict_round_trips_with_hifigan(device, trainable):
 
 @pytest.mark.parametrize('name', LARGE)
 def test_two_runs_are_bit_identical(device, name):
-    first = result(device, name, oracle.SLOPE, True)
-    second = forward_backward(device, name, oracle.SLOPE, True)
-    for a, b in zip(first, second):
-        assert torch.equal(a, b)
+    conv_checks.two_runs_are_bit_identical(
+        FAMILY, device, (name, oracle.SLOPE, True))
 
 
 @pytest.mark.parametrize('name', LARGE)
 def test_a_row_alone_equals_the_row_in_its_batch(device, name):
-    whole = result(device, name, oracle.SLOPE, True)
-    alone = forward_backward(device, name, oracle.SLOPE, True, slice(1, 2))
-    assert torch.equal(alone[0], whole[0][1:2])
-    assert torch.equal(alone[1], whole[1][1:2])
+    conv_checks.a_row_alone_equals_the_row_in_its_batch(
+        FAMILY, device, (name, oracle.SLOPE, True))
 
 
 @pytest.mark.parametrize('name', LARGE)
@@ -265,7 +247,7 @@ def test_forward_and_backward_capture_into_one_graph(device, name):
 def test_the_subsets_of_the_gradients(device, needs):
     name = 'form-64-7-3'
     want = oracle.truth(name, oracle.SLOPE)
-    whole = result(device, name, oracle.SLOPE, True)
+    whole = FAMILY.result(device, (name, oracle.SLOPE, True))
     leaves = [want[key].to(device).requires_grad_(need) for key, need in zip(
         ('x', 'weight', 'bias', 'residual'), needs)]
     y = layer(name, *leaves[:3], oracle.SLOPE, leaves[3])
@@ -295,13 +277,8 @@ def test_bf16_input_returns_a_bf16_gradient(device):
 
 
 def test_autocast_computes_in_fp32(device):
-    name = 'form-128-3-1'
-    want = oracle.truth(name, oracle.SLOPE)
-    arguments = [want[k].to(device) for k in ('x', 'weight', 'bias')]
-    with torch.autocast('cuda', dtype=torch.bfloat16):
-        y = layer(name, *arguments, oracle.SLOPE)
-    assert y.dtype == torch.float32
-    assert torch.equal(y, layer(name, *arguments, oracle.SLOPE))
+    conv_checks.autocast_computes_in_fp32(
+        FAMILY, device, ('form-128-3-1', oracle.SLOPE, False))
 
 
 ###############################################################################

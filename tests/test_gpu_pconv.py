@@ -18,13 +18,12 @@ import torch
 from promonet_amd import loss
 from promonet_amd.model import discriminator
 
+import conv_checks
 import pconv_oracle as oracle
 
 ROOT = Path(__file__).resolve().parent.parent
 NAMES = list(oracle.ALL_CASES)
 pytestmark = pytest.mark.gpu
-
-_RESULTS = {}
 
 
 def layer(name, x, weight, bias):
@@ -35,21 +34,8 @@ def layer(name, x, weight, bias):
     return discriminator.period_conv(x, weight, bias, stride, slope)
 
 
-def forward_backward(device, name, rows=slice(None)):
-    """(y, gx, gW, gb) of the case on the device, on the CPU"""
-    want = oracle.truth(name)
-    x = want['x'][rows].to(device).requires_grad_(True)
-    weight = want['weight'].to(device).requires_grad_(True)
-    bias = want['bias'].to(device).requires_grad_(True)
-    y = layer(name, x, weight, bias)
-    y.backward(want['upstream'][rows].to(device))
-    return tuple(t.detach().cpu() for t in (y, x.grad, weight.grad, bias.grad))
-
-
-def result(device, name):
-    if name not in _RESULTS:
-        _RESULTS[name] = forward_backward(device, name)
-    return _RESULTS[name]
+FAMILY = conv_checks.Family(
+    oracle, lambda name, x, weight, bias, rows: layer(name, x, weight, bias))
 
 
 @pytest.fixture(scope='module')
@@ -64,34 +50,13 @@ def golden():
 
 @pytest.mark.parametrize('name', NAMES)
 def test_a_layer_is_within_the_gate(device, name):
-    want = oracle.truth(name)
-    got = result(device, name)
-    assert got[0].shape == want['forward'].shape
-    assert got[1].shape == want['x'].shape
-    figures = oracle.figures(name, *got)
-    print(f'{name}: device ' + ' '.join(f'{v:.3e}' for v in figures) +
-          ' fp32 CPU recorded ' +
-          ' '.join(f'{v:.3e}' for v in oracle.FP32_RECORDED[name]))
-    for quantity, value in zip(oracle.QUANTITIES, figures):
-        assert value < oracle.gate(quantity), (quantity, value)
+    conv_checks.a_layer_is_within_the_gate(FAMILY, device, name)
 
 
 @pytest.mark.parametrize('shape', oracle.WEIGHT_NORM_SHAPES)
 def test_weight_norm_is_within_the_gate(device, shape):
     """The existing weight norm at fan 5, 160, 640, 2560, 5120 and 3072"""
-    g, v, upstream = oracle.weight_norm_inputs(shape)
-    want = oracle.weight_norm(g, v)
-    want_g, want_v = oracle.weight_norm_backward(upstream, g, v)
-    leaf_g = g.to(device).requires_grad_(True)
-    leaf_v = v.to(device).requires_grad_(True)
-    w = discriminator.weight_norm(leaf_g, leaf_v)
-    w.backward(upstream.to(device))
-    figures = (oracle.figure(w.detach().cpu(), want),
-               oracle.figure(leaf_g.grad.cpu(), want_g),
-               oracle.figure(leaf_v.grad.cpu(), want_v))
-    print(f'{shape}: device ' + ' '.join(f'{v:.3e}' for v in figures))
-    for value, limit in zip(figures, oracle.WEIGHT_NORM_GATES):
-        assert value < limit, (value, limit)
+    conv_checks.weight_norm_is_within_the_gate(oracle, device, shape)
 
 
 ###############################################################################
@@ -179,89 +144,39 @@ def test_the_maps_reach_feature_matching_without_a_copy(device, golden):
 
 @pytest.mark.parametrize('name', NAMES)
 def test_two_runs_are_bit_identical(device, name):
-    first = result(device, name)
-    second = forward_backward(device, name)
-    for a, b in zip(first, second):
-        assert torch.equal(a, b)
+    conv_checks.two_runs_are_bit_identical(FAMILY, device, name)
 
 
 @pytest.mark.parametrize(
     'name', ['first-2', 'second-2', 'third-2', 'fifth-large', 'post-2',
              'audio-reflect'])
 def test_forward_and_backward_capture_into_one_graph(device, name):
-    want = oracle.truth(name)
-    generator = torch.Generator().manual_seed(5)
-    other = torch.randn(want['x'].shape, generator=generator)
-    static = want['x'].to(device).requires_grad_(True)
-    weight = want['weight'].to(device).requires_grad_(True)
-    bias = want['bias'].to(device).requires_grad_(True)
-    upstream = want['upstream'].to(device)
-
-    def step():
-        out = layer(name, static, weight, bias)
-        return (out,) + torch.autograd.grad(
-            out, (static, weight, bias), upstream)
-
-    side = torch.cuda.Stream(device)
-    side.wait_stream(torch.cuda.current_stream(device))
-    with torch.cuda.stream(side):
-        step()
-    torch.cuda.current_stream(device).wait_stream(side)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        outputs = step()
-    with torch.no_grad():
-        static.copy_(other.to(device))
-    graph.replay()
-    torch.cuda.synchronize(device)
-    replayed = [t.clone() for t in outputs]
-    for a, b in zip(replayed, step()):
-        assert torch.equal(a, b)
+    conv_checks.forward_and_backward_capture_into_one_graph(
+        FAMILY, device, name)
 
 
 @pytest.mark.parametrize(
     'name', ['first-1', 'second-2', 'fifth-2', 'post-2', 'audio-five'])
 def test_zero_input_gives_the_bias(device, name):
-    want = oracle.truth(name)
-    slope = oracle.form_of(name)[4]
-    bias = want['bias'].to(device)
-    y = layer(name, torch.zeros_like(want['x']).to(device),
-              want['weight'].to(device), bias)
-    expected = torch.where(bias > 0., bias, bias * slope)
-    assert torch.equal(y, expected[None, :, None, None].expand_as(y))
+    conv_checks.zero_input_gives_the_bias(
+        FAMILY, device, name, oracle.form_of(name)[4])
 
 
 @pytest.mark.parametrize(
     'name', ['first-2', 'second-2', 'third-2', 'fourth-1', 'fifth-large',
              'post-2', 'audio-reflect'])
 def test_a_row_alone_equals_the_row_in_its_batch(device, name):
-    whole = result(device, name)
-    alone = forward_backward(device, name, slice(1, 2))
-    assert torch.equal(alone[0], whole[0][1:2])
-    assert torch.equal(alone[1], whole[1][1:2])
+    conv_checks.a_row_alone_equals_the_row_in_its_batch(FAMILY, device, name)
 
 
 @pytest.mark.parametrize('name', ['second-1', 'post-0', 'audio-five'])
 def test_bf16_input_returns_a_bf16_gradient(device, name):
-    want = oracle.truth(name)
-    leaf = want['x'].to(device, torch.bfloat16).requires_grad_(True)
-    y = layer(name, leaf, want['weight'].to(device), want['bias'].to(device))
-    assert y.dtype == torch.float32
-    y.backward(want['upstream'].to(device))
-    assert leaf.grad.dtype == torch.bfloat16 and leaf.grad.shape == leaf.shape
-    exact = layer(name, leaf.detach().float(), want['weight'].to(device),
-                  want['bias'].to(device))
-    assert torch.equal(y, exact)
+    conv_checks.bf16_input_returns_a_bf16_gradient(FAMILY, device, name)
 
 
 @pytest.mark.parametrize('name', ['third-1', 'audio-five'])
 def test_autocast_computes_in_fp32(device, name):
-    want = oracle.truth(name)
-    arguments = [want[k].to(device) for k in ('x', 'weight', 'bias')]
-    with torch.autocast('cuda', dtype=torch.bfloat16):
-        y = layer(name, *arguments)
-    assert y.dtype == torch.float32
-    assert torch.equal(y, layer(name, *arguments))
+    conv_checks.autocast_computes_in_fp32(FAMILY, device, name)
 
 
 def test_the_fold_equals_the_layer_on_the_folded_map(device):
